@@ -11,9 +11,13 @@ backward -> KL -> Adam for every per-INR parameter and for the shared mappings
 BASELINE.json configs[1]: CIFAR-10 32x32, 4096 INRs per GPU, 3x32 SIREN.  Datapoints shard across
 GPUs (weak scaling); the only per-step collective is the gradient sum of the shared mappings.
 
-Prints ONE JSON line on rank 0.  `value` = INRs trained per second for the whole job at the
+Prints ONE JSON result line on rank 0 (stdout).  `value` = INRs trained per second for the whole job at the
 reference schedule (55 100 Adam steps per INR, main_prior_training.py:106-107,132); the raw
-INR-steps/s is reported beside it.
+INR-steps/s is reported beside it, and `ms_per_step` = wall time of one timed step.  The full
+report (CPU baseline, SIREN instruction census, untimed extras) is one JSON line on stderr.
+
+  --dump-outputs DIR   after the timed steps, write what the timed call returned (dump_outputs) as
+                       DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -107,7 +111,41 @@ def parse():
     ap.add_argument("--pe-fp32", action="store_true", help="store pe / dpe as fp32 instead of bf16 (bf16 mode; bit-identical)")
     ap.add_argument("--stage1-fp32", action="store_true", help="keep the stage-1 upsampling GEMMs in fp32 (bf16 mode)")
     ap.add_argument("--no-tuned-gemms", action="store_true", help="do not load the committed TunableOp GEMM selections")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed train() call returned after its last step to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
+
+
+DUMP_ROWS = 512                  # INRs of the per-INR posterior parameters kept by --dump-outputs (seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, m, lt, up):
+    """--dump-outputs: what a caller of the timed train() call receives after its last step, as float32 / float64 .npy files
+    that two builds can compare output for output: the returned ELBO of every timed step, the last step's MSE and the final
+    KL (float64), the per-INR posterior parameters (rows of a fixed, seeded sample of DUMP_ROWS INRs when there are more) and
+    the shared mappings it trained (float32).  Called before anything else runs on the model."""
+    import numpy as np
+    mse, kl, elbo = res
+    arrays = {"elbo": np.asarray(elbo, np.float64), "mse": np.asarray([mse], np.float64), "kl": np.asarray([kl], np.float64)}
+    n = m.loc.shape[0]
+    rows = None
+    if n > DUMP_ROWS:
+        rows = torch.from_numpy(np.sort(np.random.RandomState(0).choice(n, DUMP_ROWS, replace=False))).to(m.loc.device)
+    for name, p in m.named_parameters():
+        t = p.detach()
+        if rows is not None and t.shape[0] == n:
+            t = t.index_select(0, rows)
+        arrays["posterior_" + name] = t.float().cpu().numpy()
+    for prefix, mod in (("mapping_", lt), ("upsample_", up)):
+        for name, p in mod.named_parameters():
+            arrays[prefix + name] = p.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        sys.exit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _cpu_case(cfg, n, threads, seconds_target, max_steps):
@@ -831,9 +869,13 @@ def main():
         run(a.warmup)
     fence()
     t0 = time.perf_counter()
-    run(a.steps)
+    res = run(a.steps)
     fence()
     el = time.perf_counter() - t0
+    if len(res[2]) != a.steps:
+        sys.exit(f"bench.py: the timed call ran {len(res[2])} steps, --steps {a.steps}")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, res, m, lt, up)
     if ws > 1:
         tt = torch.tensor([el], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
@@ -1032,7 +1074,13 @@ def main():
         if comm is not None:
             out["comm"] = comm
         out.update(extras)
-        print(json.dumps(out))
+        # The full report (~20 KB with the CPU baseline, the census and the untimed extras) goes to stderr as one JSON line; the
+        # result line on stdout keeps the timed figures only: a line that long is cut off by callers that read an output's tail.
+        print(json.dumps(out), file=sys.stderr, flush=True)
+        line = {k: v for k, v in out.items() if k != "cpu_baseline" and k not in extras}
+        if roof is not None:
+            line["roofline"] = {k: v for k, v in roof.items() if k != "valu"}
+        print(json.dumps(line))
     if ws > 1:
         torch.distributed.destroy_process_group()
 

@@ -965,6 +965,41 @@ def gen_hier_map(out):
     print("hier_map ok", flush=True)
 
 
+def gen_ckpt_read(out):
+    """N2, product -> reference: the checkpoint tests/golden_util.py::product_checkpoint has the PRODUCT write
+    (drivers.save_checkpoint) read by the reference's main_compression.py load sequence (eight plain pickle.load calls, its
+    prior_model resolving `prior_model.*`); the reference's TestBNNmodel built from what it read runs predict().  Stored: the
+    globals the file asked the reference to resolve and the predict() output, for
+    tests/test_host_cpu.py::test_reference_unpickles_a_checkpoint_written_by_the_product."""
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tests"))
+    from golden_util import pickle_globals, product_checkpoint
+    from recombiner_amd import drivers
+    ck, X = product_checkpoint()
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "PRIOR.pkl")
+        drivers.save_checkpoint(path, ck)
+        objs, names = pickle_globals(path)
+    group_idx, gs, ge, g2p, p2g, n_groups, gk, w = objs[0]
+    prior_loc, prior_scale, kl_beta, avg_ls = objs[1]
+    linear_transform, upsample_net = objs[6], objs[7]
+    assert type(linear_transform) is ref_prior.LinearTransform and type(upsample_net) is ref_prior.Upsample
+    assert not any(k.startswith("_rcb_") for k in upsample_net.__dict__)
+    c = ref_config.configs["cifar"]
+    tm = ref_test.TestBNNmodel(c["input_dim"], c["hidden_dims"], c["output_dim"], 2, c["upsample_factors"], c["latent_dim"],
+                               c["data_dim"], c["pixel_sizes"], False, None, None, "cifar", linear_transform=linear_transform,
+                               upsample_net=upsample_net, p_loc=prior_loc.clone()[p2g],
+                               p_log_scale=torch.log(torch.exp(prior_scale * 6) - 1).clone()[p2g], init_log_scale=avg_ls[p2g],
+                               param_to_group=p2g, group_to_param=g2p, n_groups=n_groups, group_start_index=gs,
+                               group_end_index=ge, group_idx=group_idx, device="cpu", initial_beta=kl_beta)
+    with torch.no_grad():
+        y = tm.predict(X[None].repeat(2, 1, 1), random_seed=3)
+    np.savez_compressed(os.path.join(out, "ckpt_ref_read.npz"), globals=np.array(json.dumps(names)), y_ref=tnp(y),
+                        n_groups=np.int64(n_groups))
+    print("ckpt_read ok", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(os.path.dirname(__file__), "..", "tests", "golden"))
@@ -999,4 +1034,6 @@ if __name__ == "__main__":
     # round-4 addition
     if "hier" in todo:
         gen_hier_map(a.out)
+    if "ckpt_read" in todo:
+        gen_ckpt_read(a.out)
     print("done")

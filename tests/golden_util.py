@@ -217,3 +217,45 @@ def load_rd_fixture(n_test=64):
                 elif per_run:                      # repetitions of the same experiment: stacked along the run axis
                     out[k] = np.concatenate([np.asarray(out[k]), np.asarray(d[k])], 0)
     return out
+
+
+def product_checkpoint():
+    """the checkpoint of the product -> reference interchange test (drivers.save_checkpoint's eight objects: a grouping of
+    seeded KL weights, a seeded prior, seeded mappings -- the upsampling net with its fast-path cache attached, which must not
+    travel) and the predict() input of that test.  oracle/make_golden.py --only ckpt_read has the reference read it."""
+    from recombiner_amd import config, prior_model as PM, utils
+    from recombiner_amd.upsample_fast import phase_module
+    cfg = config.configs["cifar"]
+    dims = [cfg["input_dim"]] + cfg["hidden_dims"] + [cfg["output_dim"]]
+    torch.manual_seed(3)
+    lt = PM.LinearTransform(dims)
+    up = PM.Upsample(cfg["data_dim"], cfg["paddings"], cfg["layerwise_scale_factors"])
+    phase_module(up)
+    D = 3267 + 512
+    g1 = PM.get_grouping_by_kl(np.random.RandomState(0).gamma(0.7, 4.0, size=D).astype(np.float32))
+    gen = torch.Generator().manual_seed(1)
+    p_loc, p_scale = 0.01 * torch.randn(D, generator=gen), 0.02 + 0.01 * torch.rand(D, generator=gen)
+    avg_ls = -4 + 0.1 * torch.randn(D, generator=gen)
+    ck = [g1, (p_loc, p_scale, 3e-7, avg_ls), (None,) * 8, (None, None, 3e-7, None), (None,) * 8, (None, None, 3e-7, None), lt, up]
+    X, _ = utils.synthetic_inputs(cfg["pixel_sizes"], cfg["fourier_dim"], 1, 3, seed=0)
+    return ck, X
+
+
+def pickle_globals(path, resolve=None):
+    """-> (objects, sorted `module.name` globals): the file of sequential pickles read with find_class recording every global it
+    asks its reader to resolve; `resolve` maps such a name to a class of the reader's choice (else the usual lookup)."""
+    import pickle
+    seen = set()
+
+    class Recorder(pickle.Unpickler):
+        def find_class(self, module, name):
+            seen.add(module + "." + name)
+            if resolve and module + "." + name in resolve:
+                return resolve[module + "." + name]
+            return super().find_class(module, name)
+
+    objs = []
+    with open(path, "rb") as f:
+        while f.peek(1):
+            objs.append(Recorder(f).load())
+    return objs, sorted(seen)
