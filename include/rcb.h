@@ -59,8 +59,9 @@ int64_t rcb_struct_bytes(int32_t which);
  * `wvec` row g holds the layer vectors back to back, each `[bias(out) | W(in,out) row-major]`
  * (prior_model.py:125-126); rows are w_row_stride floats apart.  G = N*S; sample s of INR n is
  * row g = n*S + s; targets / xf are indexed by n = g / S.
- * Hidden width 32, 48 or 64 in the 16-bit modes; any width up to 64 in the fp32 mode (32 on the matrix cores, the others on a
- * plain-FMA parity kernel, reference prior_model.py:84-85); 1..4 hidden layers, out_dim <= 32, F + E <= 64.
+ * Hidden width 16, 24, 32, 48 or 64 in the 16-bit modes (16 / 24: one wave per row, siren_mlp_narrow.hip, F and E <= 32 each);
+ * any width up to 64 in the fp32 mode (32 on the matrix cores, the others on a plain-FMA parity kernel, reference
+ * prior_model.py:84-85); 1..4 hidden layers, out_dim <= 32, F + E <= 64.
  * precision: 0 = fp32 MFMA (exact fp32 products); 1 = bf16 operands, 2 = f16 operands (both fp32 accumulate;
  * f16 carries gradients scaled by 2^10 internally).
  * ------------------------------------------------------------------------------------------- */
@@ -71,7 +72,7 @@ typedef struct {
   int32_t fourier_dim;   /* F                                                       */
   int32_t pe_dim;        /* E                                                       */
   int32_t n_hidden;      /* number of hidden layers                                 */
-  int32_t hidden;        /* hidden width (16-bit modes: 32, 48, 64; fp32: 1 .. 64)   */
+  int32_t hidden;        /* hidden width (16-bit: 16, 24, 32, 48, 64; fp32: 1 .. 64) */
   int32_t out_dim;       /* C                                                       */
   int64_t xf_inr_stride; /* floats between INRs in xf; 0 = shared grid              */
   int64_t w_row_stride;  /* floats between rows of wvec and of dwvec                */
@@ -113,7 +114,7 @@ typedef struct {
                               * stride.  The pair is the plane operand of the A transform's data gradient (rcb_atrans_apply
                               * x_hi / x_lo): the same 4 bytes per element as the fp32 dwvec, which may then be NULL in
                               * rcb_siren_bwd / _loss_bwd (unchunked launches) and rcb_siren_reduce_chunks                */
-  uint64_t* clock_probe;     /* nullable measurement aid (width-32 16-bit kernel): workgroup b < 256 writes clock_probe[4 b ..
+  uint64_t* clock_probe;     /* nullable measurement aid (width-32 16-bit kernel; refused at widths 16 / 24): workgroup b < 256 writes clock_probe[4 b ..
                               * 4 b + 3] = {s_memtime, s_memrealtime at its start, s_memtime, s_memrealtime at its end}.  Both
                               * counters are read on the workgroup's own CU (s_memtime is not comparable between CUs), so
                               * (t2 - t0) / ((t3 - t1) / 1e8) is the SHADER CLOCK that workgroup ran at (s_memrealtime counts

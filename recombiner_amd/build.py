@@ -1,7 +1,7 @@
 """Builds librcb_hip.so (gfx950) in-tree with hipcc.  Usage: python -m recombiner_amd.build [--force]
 
 Every .hip file is compiled to its own object (in parallel, cached under recombiner_amd/lib/obj by the modification
-times of the source and the shared headers), then linked: a change to one kernel file costs one compile, not eleven."""
+times of the source and the shared headers), then linked: a change to one kernel file costs one compile, not fifteen."""
 import os
 import subprocess
 import sys
@@ -13,7 +13,8 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "librcb_hip.so")
 SOURCES = ["atrans.hip", "phase_weight.hip", "phaseconv.hip", "posterior.hip", "rec_score.hip", "siren_mlp.hip",
-           "siren_mlp_bf16.hip", "siren_mlp_wave.hip", "siren_mlp_wide.hip", "siren_mlp_generic.hip", "stage1.hip", "tiles.hip", "upconv.hip",
+           "siren_mlp_bf16.hip", "siren_mlp_wave.hip", "siren_mlp_wide.hip", "siren_mlp_generic.hip",
+           "siren_mlp_narrow.hip", "stage1.hip", "tiles.hip", "upconv.hip",
            "upconv_weff.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 

@@ -21,6 +21,14 @@ using namespace rcb;
 
 #include "siren_common.h"
 
+namespace rcb {
+// uniform hidden width 16 or 24 in the 16-bit modes (siren_mlp_narrow.hip)
+int siren_narrow_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);
+inline bool siren_narrow(const rcb_siren_desc* d) {
+  return d->precision >= 1 && (d->hidden == 16 || d->hidden == 24) && d->hidden_dims[0] == 0;
+}
+}  // namespace rcb
+
 namespace {
 
 // sin / cos of w0*z with a two-float range reduction in revolutions
@@ -379,12 +387,12 @@ int dispatch(const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
 
 int fill_args(const rcb_siren_desc* d, SirenArgs& a) {
   RCB_REQUIRE(d, RCB_ERR_ARG, "siren: null descriptor");
-  RCB_REQUIRE(d->hidden == HID || (d->precision >= 1 && (d->hidden == 48 || d->hidden == 64)) ||
+  RCB_REQUIRE(d->hidden == HID || (d->precision >= 1 && (d->hidden == 16 || d->hidden == 24 || d->hidden == 48 || d->hidden == 64)) ||
                   (d->precision == 0 && d->hidden >= 1 && d->hidden <= 64),
-              RCB_ERR_UNSUPPORTED, "siren: hidden width %d (fp32 mode: up to 64; 16-bit modes: 32, 48, 64)", d->hidden);
+              RCB_ERR_UNSUPPORTED, "siren: hidden width %d (fp32 mode: up to 64; 16-bit modes: 16, 24, 32, 48, 64)", d->hidden);
   RCB_REQUIRE(d->n_hidden >= 1 && d->n_hidden <= 4, RCB_ERR_UNSUPPORTED, "siren: n_hidden=%d", d->n_hidden);
   RCB_REQUIRE(d->hidden_dims[0] == 0 || d->precision == 0, RCB_ERR_UNSUPPORTED,
-              "siren: per-layer hidden widths exist in the fp32 mode only (the 16-bit kernels take one width: 32, 48 or 64)");
+              "siren: per-layer hidden widths exist in the fp32 mode only (the 16-bit kernels take one width: 16, 24, 32, 48 or 64)");
   RCB_REQUIRE(d->out_dim >= 1 && d->out_dim <= 32, RCB_ERR_UNSUPPORTED, "siren: out_dim=%d", d->out_dim);
   RCB_REQUIRE(d->fourier_dim >= 1 && d->pe_dim >= 0 && d->fourier_dim + d->pe_dim <= 64, RCB_ERR_UNSUPPORTED,
               "siren: F=%d E=%d", d->fourier_dim, d->pe_dim);
@@ -510,6 +518,7 @@ extern "C" int rcb_siren_fwd(const rcb_siren_desc* d, const float* xf, const voi
   a.pe = static_cast<const float*>(pe);
   a.wvec = wvec;
   a.yout = y_out;
+  if (siren_narrow(d)) return siren_narrow_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
   return dispatch<MODE_FWD>(d, a, (hipStream_t)stream);
 }
@@ -528,6 +537,7 @@ extern "C" int rcb_siren_bwd(const rcb_siren_desc* d, const float* xf, const voi
   a.yin = dy;
   a.dwvec = dwvec;
   a.dpe = static_cast<float*>(dpe);
+  if (siren_narrow(d)) return siren_narrow_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
   return dispatch<MODE_BWD>(d, a, (hipStream_t)stream);
 }
@@ -549,6 +559,7 @@ extern "C" int rcb_siren_loss_bwd(const rcb_siren_desc* d, const float* xf, cons
   a.dwvec = dwvec;
   a.dpe = static_cast<float*>(dpe);
   a.dy_scale = dy_scale;
+  if (siren_narrow(d)) return siren_narrow_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
   return dispatch<MODE_LOSS>(d, a, (hipStream_t)stream);
 }
