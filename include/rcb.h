@@ -24,7 +24,7 @@ extern "C" {
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
  * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform).  A binding compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 406
+#define RCB_VERSION 407
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -61,7 +61,9 @@ int64_t rcb_struct_bytes(int32_t which);
  * row g = n*S + s; targets / xf are indexed by n = g / S.
  * Hidden width 16, 24, 32, 48 or 64 in the 16-bit modes (16 / 24: one wave per row, siren_mlp_narrow.hip, F and E <= 32 each);
  * any width up to 64 in the fp32 mode (32 on the matrix cores, the others on a plain-FMA parity kernel, reference
- * prior_model.py:84-85); 1..4 hidden layers, out_dim <= 32, F + E <= 64.
+ * prior_model.py:84-85); 1..7 hidden layers (8 linear layers: the A transform's RCB_ATRANS_MAX_LAYERS), out_dim <= 32,
+ * F + E <= 64.  5..7 hidden layers take one width for every layer (no hidden_dims list): 16, 24 or 32 in the 16-bit modes (one
+ * wave per row, siren_mlp_deep.hip, F, E and out_dim <= 32 each), any width up to 64 in the fp32 mode (plain-FMA parity kernel).
  * precision: 0 = fp32 MFMA (exact fp32 products); 1 = bf16 operands, 2 = f16 operands (both fp32 accumulate;
  * f16 carries gradients scaled by 2^10 internally).
  * ------------------------------------------------------------------------------------------- */
@@ -71,7 +73,7 @@ typedef struct {
   int32_t n_pix;         /* P                                                       */
   int32_t fourier_dim;   /* F                                                       */
   int32_t pe_dim;        /* E                                                       */
-  int32_t n_hidden;      /* number of hidden layers                                 */
+  int32_t n_hidden;      /* number of hidden layers (1..7)                          */
   int32_t hidden;        /* hidden width (16-bit: 16, 24, 32, 48, 64; fp32: 1 .. 64) */
   int32_t out_dim;       /* C                                                       */
   int64_t xf_inr_stride; /* floats between INRs in xf; 0 = shared grid              */
@@ -107,8 +109,8 @@ typedef struct {
   int32_t pe_patch_nums[3];  /* patches per axis (first pe_grid_dims entries)                                          */
   int32_t pe_patch_size[3];  /* pixels per axis of one patch; their product is n_pix                                   */
   int64_t dw_bf16_stride;    /* elements between the rows of dw_bf16 (>= the length of a row of layer vectors)         */
-  int32_t hidden_dims[4];    /* all zero: every hidden layer is `hidden` wide.  Otherwise the widths of the n_hidden hidden
-                              * layers one by one (the reference builds its INR from any list, prior_model.py:84-85): fp32
+  int32_t hidden_dims[4];    /* all zero: every hidden layer is `hidden` wide.  Otherwise (n_hidden <= 4) the widths of the
+                              * n_hidden hidden layers one by one (the reference builds its INR from any list, prior_model.py:84-85): fp32
                               * mode only (1 .. 64 each; the plain-FMA parity kernel), `hidden` = their maximum            */
   void* dw_lo;               /* nullable, with dw_bf16 (the HIGH plane): the LOW plane bf16(dwvec - dw_bf16), same layout and
                               * stride.  The pair is the plane operand of the A transform's data gradient (rcb_atrans_apply

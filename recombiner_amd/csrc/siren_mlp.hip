@@ -25,8 +25,11 @@ namespace rcb {
 // uniform hidden width 16 or 24 in the 16-bit modes (siren_mlp_narrow.hip)
 int siren_narrow_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);
 inline bool siren_narrow(const rcb_siren_desc* d) {
-  return d->precision >= 1 && (d->hidden == 16 || d->hidden == 24) && d->hidden_dims[0] == 0;
+  return d->precision >= 1 && (d->hidden == 16 || d->hidden == 24) && d->hidden_dims[0] == 0 && d->n_hidden <= 4;
 }
+// 5 .. 7 hidden layers of one width 16, 24 or 32 in the 16-bit modes (siren_mlp_deep.hip)
+int siren_deep_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);
+inline bool siren_deep(const rcb_siren_desc* d) { return d->precision >= 1 && d->n_hidden >= 5; }
 }  // namespace rcb
 
 namespace {
@@ -353,7 +356,8 @@ int launch(const SirenArgs& a, size_t smem_bytes, hipStream_t st) {
 
 template <int MODE>
 int dispatch(const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
-  if (d->hidden != HID || d->hidden_dims[0] != 0) return siren_generic_dispatch(MODE, d, a, st);   // fp32 at other widths / per-layer widths: siren_mlp_generic.hip
+  // fp32 at other widths / per-layer widths / 5..7 hidden layers: siren_mlp_generic.hip
+  if (d->hidden != HID || d->hidden_dims[0] != 0 || d->n_hidden > 4) return siren_generic_dispatch(MODE, d, a, st);
   const int in0 = d->fourier_dim + d->pe_dim;
   const int ks = d->fourier_dim > d->pe_dim ? d->fourier_dim : d->pe_dim;
   const int nb0 = (in0 + 31) / 32;
@@ -390,7 +394,12 @@ int fill_args(const rcb_siren_desc* d, SirenArgs& a) {
   RCB_REQUIRE(d->hidden == HID || (d->precision >= 1 && (d->hidden == 16 || d->hidden == 24 || d->hidden == 48 || d->hidden == 64)) ||
                   (d->precision == 0 && d->hidden >= 1 && d->hidden <= 64),
               RCB_ERR_UNSUPPORTED, "siren: hidden width %d (fp32 mode: up to 64; 16-bit modes: 16, 24, 32, 48, 64)", d->hidden);
-  RCB_REQUIRE(d->n_hidden >= 1 && d->n_hidden <= 4, RCB_ERR_UNSUPPORTED, "siren: n_hidden=%d", d->n_hidden);
+  RCB_REQUIRE(d->n_hidden >= 1 && d->n_hidden <= 7, RCB_ERR_UNSUPPORTED,
+              "siren: n_hidden=%d (1..7 hidden layers: the A transform takes up to 8 linear layers)", d->n_hidden);
+  RCB_REQUIRE(d->n_hidden <= 4 || d->hidden_dims[0] == 0, RCB_ERR_UNSUPPORTED,
+              "siren: per-layer hidden widths exist for 1..4 hidden layers only (5..7 layers take one width)");
+  RCB_REQUIRE(d->n_hidden <= 4 || d->precision == 0 || d->hidden == 16 || d->hidden == 24 || d->hidden == HID, RCB_ERR_UNSUPPORTED,
+              "siren: hidden width %d at %d hidden layers (16-bit modes: 16, 24 or 32 beyond 4 layers)", d->hidden, d->n_hidden);
   RCB_REQUIRE(d->hidden_dims[0] == 0 || d->precision == 0, RCB_ERR_UNSUPPORTED,
               "siren: per-layer hidden widths exist in the fp32 mode only (the 16-bit kernels take one width: 16, 24, 32, 48 or 64)");
   RCB_REQUIRE(d->out_dim >= 1 && d->out_dim <= 32, RCB_ERR_UNSUPPORTED, "siren: out_dim=%d", d->out_dim);
@@ -518,6 +527,7 @@ extern "C" int rcb_siren_fwd(const rcb_siren_desc* d, const float* xf, const voi
   a.pe = static_cast<const float*>(pe);
   a.wvec = wvec;
   a.yout = y_out;
+  if (siren_deep(d)) return siren_deep_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
   if (siren_narrow(d)) return siren_narrow_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
   return dispatch<MODE_FWD>(d, a, (hipStream_t)stream);
@@ -537,6 +547,7 @@ extern "C" int rcb_siren_bwd(const rcb_siren_desc* d, const float* xf, const voi
   a.yin = dy;
   a.dwvec = dwvec;
   a.dpe = static_cast<float*>(dpe);
+  if (siren_deep(d)) return siren_deep_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
   if (siren_narrow(d)) return siren_narrow_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
   return dispatch<MODE_BWD>(d, a, (hipStream_t)stream);
@@ -559,6 +570,7 @@ extern "C" int rcb_siren_loss_bwd(const rcb_siren_desc* d, const float* xf, cons
   a.dwvec = dwvec;
   a.dpe = static_cast<float*>(dpe);
   a.dy_scale = dy_scale;
+  if (siren_deep(d)) return siren_deep_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
   if (siren_narrow(d)) return siren_narrow_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
   return dispatch<MODE_LOSS>(d, a, (hipStream_t)stream);
@@ -569,8 +581,8 @@ extern "C" int rcb_siren_reduce_chunks(const rcb_siren_desc* d, const float* dw_
   RCB_REQUIRE(d && dw_partial && ((sse_partial == nullptr) == (sse == nullptr)), RCB_ERR_ARG, "siren_reduce_chunks: null pointer");
   RCB_REQUIRE(dwvec || (d->dw_bf16 && d->dw_lo), RCB_ERR_ARG, "siren_reduce_chunks: dwvec may be NULL only when both planes are given");
   RCB_REQUIRE(d->dw_lo == nullptr || d->dw_bf16 != nullptr, RCB_ERR_ARG, "siren_reduce_chunks: dw_lo comes with dw_bf16");
-  RCB_REQUIRE(d->pixel_chunks >= 1 && d->n_rows > 0 && d->n_hidden >= 1 && d->n_hidden <= 4, RCB_ERR_SHAPE,
-              "siren_reduce_chunks: chunks=%d rows=%d", d->pixel_chunks, d->n_rows);
+  RCB_REQUIRE(d->pixel_chunks >= 1 && d->n_rows > 0 && d->n_hidden >= 1 && d->n_hidden <= 7, RCB_ERR_SHAPE,
+              "siren_reduce_chunks: chunks=%d rows=%d n_hidden=%d", d->pixel_chunks, d->n_rows, d->n_hidden);
   ReduceArgs r;
   memset(&r, 0, sizeof(r));
   r.part = dw_partial;

@@ -26,11 +26,12 @@ __device__ __forceinline__ void sincos_w0_exact(float z, float k_hi, float k_lo,
 
 constexpr int GEN_MAXW = 64;                                      // hidden width limit
 constexpr int GEN_J = (GEN_MAXW * (GEN_MAXW + 1) + 255) / 256;    // gradient entries per thread and layer
+constexpr int GEN_MAXL = 8;                                       // linear layers (7 hidden: the A transform's limit)
 
 struct GenGeo {
   int W, NH, in0, dnet;        // W = the widest hidden layer
-  int wid[MAXL];               // output width of every layer (hidden widths, then C)
-  int off[MAXL + 1];
+  int wid[GEN_MAXL];           // output width of every layer (hidden widths, then C)
+  int off[GEN_MAXL + 1];
   // LDS map (floats)
   int x0, x0s;                 // inputs [32][x0s]
   int s_base, c_base, ws;      // sin / cos [NH][32][ws]
@@ -39,7 +40,8 @@ struct GenGeo {
   int total;
 };
 
-template <int MODE>
+// ML: linear layers the loops are unrolled over (MAXL = 5 up to 4 hidden layers, GEN_MAXL beyond)
+template <int MODE, int ML>
 __global__ void __launch_bounds__(256) siren_generic_kernel(SirenArgs a, GenGeo geo) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, p = tid & 31, og = tid >> 5;
@@ -60,9 +62,9 @@ __global__ void __launch_bounds__(256) siren_generic_kernel(SirenArgs a, GenGeo 
     const float* src = a.wvec + (long long)g * a.w_stride;
     for (int i = tid; i < geo.dnet; i += 256) wl[i] = src[i];
   }
-  float gacc[MAXL][GEN_J];
+  float gacc[ML][GEN_J];
 #pragma unroll
-  for (int l = 0; l < MAXL; ++l)
+  for (int l = 0; l < ML; ++l)
 #pragma unroll
     for (int j = 0; j < GEN_J; ++j) gacc[l][j] = 0.f;
   float sse_t = 0.f;
@@ -77,9 +79,9 @@ __global__ void __launch_bounds__(256) siren_generic_kernel(SirenArgs a, GenGeo 
     for (int i = og; i < in0; i += 8)
       X0[p * x0s + i] = i < F ? a.xf[(long long)n * a.xf_stride + (long long)pc * F + i] : a.pe[((long long)g * P + pc) * E + (i - F)];
     __syncthreads();
-    // ---- forward (layer loops are unrolled over MAXL: the gradient registers are indexed statically) ------------------------
+    // ---- forward (layer loops are unrolled over ML: the gradient registers are indexed statically) ------------------------
 #pragma unroll
-    for (int l = 0; l < MAXL - 1; ++l) {
+    for (int l = 0; l < ML - 1; ++l) {
       if (l >= NH) continue;
       const float* prev = l == 0 ? X0 + p * x0s : Sb + ((l - 1) * 32 + p) * ws;
       const float* Bl = wl + geo.off[l];
@@ -136,7 +138,7 @@ __global__ void __launch_bounds__(256) siren_generic_kernel(SirenArgs a, GenGeo 
     __syncthreads();
     // ---- backward ---------------------------------------------------------------------------------------------------------
 #pragma unroll
-    for (int l = MAXL - 1; l >= 0; --l) {
+    for (int l = ML - 1; l >= 0; --l) {
       if (l >= NL) continue;
       const int ni = lin(l), no = lout(l);
       const float* prev = l == 0 ? X0 : Sb + (l - 1) * 32 * ws;        // [32][stride]
@@ -185,7 +187,7 @@ __global__ void __launch_bounds__(256) siren_generic_kernel(SirenArgs a, GenGeo 
   if (MODE == MODE_FWD) return;
   float* dst = a.dwvec + (long long)g * a.w_stride;
 #pragma unroll
-  for (int l = 0; l < MAXL; ++l) {
+  for (int l = 0; l < ML; ++l) {
     if (l >= NL) continue;
     const int size = lout(l) * (lin(l) + 1);
 #pragma unroll
@@ -205,9 +207,9 @@ __global__ void __launch_bounds__(256) siren_generic_kernel(SirenArgs a, GenGeo 
   }
 }
 
-template <int MODE>
+template <int MODE, int ML>
 int launch_generic(const SirenArgs& a, const GenGeo& geo, hipStream_t st) {
-  auto kfn = siren_generic_kernel<MODE>;
+  auto kfn = siren_generic_kernel<MODE, ML>;
   // per launch, not once per process: the attribute belongs to the (function, device) pair and a process may drive
   // several devices or call from several threads; the call is a table write
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -221,7 +223,7 @@ int launch_generic(const SirenArgs& a, const GenGeo& geo, hipStream_t st) {
 
 namespace rcb {
 int siren_generic_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
-  RCB_REQUIRE(d->precision == 0 && d->hidden >= 1 && d->hidden <= GEN_MAXW && d->n_hidden + 1 <= MAXL && d->out_dim <= 32 &&
+  RCB_REQUIRE(d->precision == 0 && d->hidden >= 1 && d->hidden <= GEN_MAXW && d->n_hidden + 1 <= GEN_MAXL && d->out_dim <= 32 &&
                   d->pixel_chunks <= 1,
               RCB_ERR_UNSUPPORTED, "siren(generic fp32): hidden=%d n_hidden=%d out_dim=%d pixel_chunks=%d", d->hidden, d->n_hidden,
               d->out_dim, d->pixel_chunks);
@@ -263,8 +265,13 @@ int siren_generic_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipS
   geo.total = f;
   RCB_REQUIRE((size_t)f * sizeof(float) <= 160 * 1024, RCB_ERR_UNSUPPORTED, "siren(generic fp32): %zu B of LDS needed",
               (size_t)f * sizeof(float));
-  if (mode == MODE_FWD) return launch_generic<MODE_FWD>(a, geo, st);
-  if (mode == MODE_BWD) return launch_generic<MODE_BWD>(a, geo, st);
-  return launch_generic<MODE_LOSS>(a, geo, st);
+  if (geo.NH + 1 > MAXL) {
+    if (mode == MODE_FWD) return launch_generic<MODE_FWD, GEN_MAXL>(a, geo, st);
+    if (mode == MODE_BWD) return launch_generic<MODE_BWD, GEN_MAXL>(a, geo, st);
+    return launch_generic<MODE_LOSS, GEN_MAXL>(a, geo, st);
+  }
+  if (mode == MODE_FWD) return launch_generic<MODE_FWD, MAXL>(a, geo, st);
+  if (mode == MODE_BWD) return launch_generic<MODE_BWD, MAXL>(a, geo, st);
+  return launch_generic<MODE_LOSS, MAXL>(a, geo, st);
 }
 }  // namespace rcb

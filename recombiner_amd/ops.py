@@ -162,6 +162,9 @@ def _siren_desc(meta: SirenMeta, wvec, xf, pe=None, dw_bf16=None, chunks=1, pe_l
     if meta.hidden_dims and len(set(meta.hidden_dims)) > 1:
         if meta.precision != 0 or len(meta.hidden_dims) != meta.n_hidden:
             raise RcbError("per-layer hidden widths: fp32 mode only, one width per hidden layer")
+        if len(meta.hidden_dims) > len(d.hidden_dims):
+            raise RcbError(f"per-layer hidden widths: up to {len(d.hidden_dims)} hidden layers "
+                           f"({len(meta.hidden_dims)} given; 5 to 7 hidden layers take one width)")
         for i, w_ in enumerate(meta.hidden_dims):
             d.hidden_dims[i] = int(w_)
     if pe_layout is not None:
