@@ -13,11 +13,16 @@ GPUs (weak scaling); the only per-step collective is the gradient sum of the sha
 
 Prints ONE JSON result line on rank 0 (stdout).  `value` = INRs trained per second for the whole job at the
 reference schedule (55 100 Adam steps per INR, main_prior_training.py:106-107,132); the raw
-INR-steps/s is reported beside it, and `ms_per_step` = wall time of one timed step.  The full
-report (CPU baseline, SIREN instruction census, untimed extras) is one JSON line on stderr.
+INR-steps/s is reported beside it, and `ms_per_step` = wall time of one timed step.  A plain run does
+only that: set-up, warm-up, the timed steps, --dump-outputs, the result line.
 
   --dump-outputs DIR   after the timed steps, write what the timed call returned (dump_outputs) as
                        DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+  --full               after the timed steps (and --dump-outputs), also measure and check everything else: the
+                       live roofline of the SIREN kernel, the communication report of a sharded run, the CPU
+                       baseline and the untimed extras (--no-cpu-baseline / --no-extras leave those two out).
+                       The result line then carries `roofline` and `comm`, and the full report (CPU baseline,
+                       SIREN instruction census, untimed extras) is one JSON line on stderr.
 """
 import argparse
 import json
@@ -97,8 +102,12 @@ def parse():
     ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16"],
                     help="bf16 = bf16 MFMA operands / fp32 accumulate / fp32 master weights (BASELINE config[1]); "
                          "fp32 = exact-parity mode (fp32 MFMA, MIOpen upsample net)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras (per-kernel table, REC roofline, PSNR@bpp run, presets table)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the SIREN kernel's roofline, a sharded run's communication, the CPU "
+                         "baseline and the untimed extras (full report on stderr)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the untimed extras (per-kernel table, REC roofline, PSNR@bpp run, presets table)")
     ap.add_argument("--frozen-mappings", action="store_true", help="training_mappings=False")
     ap.add_argument("--lowp-gemm", action="store_true", help="bf16-operand A-transform GEMMs (experimental)")
     ap.add_argument("--no-split-gemm", action="store_true", help="plain fp32 A-transform GEMMs instead of split-bf16 fwd/dgrad")
@@ -543,6 +552,144 @@ def presets_table(dev, clock_ghz=None):
     return {"prior_training": out, "test_time": tt}
 
 
+def siren_roofline(m, run, Xd, Yd, n, D, dev, rank, step_ms):
+    """--full: the roofline of the hot-path kernel (fused SIREN fwd + MSE + bwd), measured live after the timed steps.
+    -> (the `roofline` object, None off rank 0; the shader clock in GHz measured inside its launches, NaN where not measured)"""
+    from recombiner_amd import ops
+    roof = None
+    siren_clock_ghz = float("nan")
+    # The kernel is timed with events on its launch stream in the duty cycle it has inside the step: two training steps run
+    # between consecutive timed launches (on every rank: the sharded step contains collectives).  Ten back-to-back launches
+    # of this VALU-heavy kernel alone pull the clock down within a few launches (276 -> 335 us in one rocprofv3 trace),
+    # which is not the state the step runs it in.
+    reps = 10
+    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    if rank == 0:
+        meta = m._meta(Xd, 16)
+        pe = torch.randn(n, 1024, 16, device=dev) * 0.1
+        pe16 = m.precision != 0 and m.pe_bf16          # the storage type the training step uses for pe / dpe
+        if pe16:
+            pe = pe.bfloat16()
+        # launched as the step launches it: rows on 128-byte lines, and (16-bit modes) the bf16 copy of the gradient that
+        # the A transform's weight-gradient GEMM reads -- 2 D extra bytes per INR that the algorithmic figure does NOT count
+        ld = (D + 31) // 32 * 32
+        wv = torch.empty(n, ld, device=dev)[:, :D]
+        wv.copy_((torch.rand(n, D, device=dev) * 2 - 1) * 0.02)
+        want16 = bool(m.precision != 0 and m.split_gemm and not m.lowp_gemm and m.wgrad_bf16)
+        xf16 = ops.xf_bf16(Xd, m.precision) if m.precision in (1, 2) else None
+
+        probe = torch.zeros(256, 4, device=dev, dtype=torch.int64)     # per-workgroup clock stamps of the LAST launch
+
+        def launch():
+            return ops.siren_loss_bwd(Xd, pe, wv, Yd, 1.0 / 3072, meta, want_bf16=want16, xf16=xf16,
+                                      clock_probe=probe if m.precision == 1 else None)
+        for _ in range(2):
+            launch()
+    clocks = []
+    for e0, e1 in evs:
+        run(2)
+        if rank == 0:
+            # an untimed launch first: the stream is busy while the host submits e0 / kernel / e1, so the interval holds
+            # the kernel and not the host's launch latency
+            launch()
+            e0.record()
+            launch()
+            e1.record()
+            if m.precision == 1:
+                e1.synchronize()
+                clocks.append(ops.shader_clock_ghz(probe))
+    if rank == 0:
+        torch.cuda.synchronize()
+        ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / reps
+        siren_clock_ghz = (sum(clocks) / len(clocks)) if clocks else float("nan")
+        dims = m.dims
+        flops = 6.0 * 1024 * sum(dims[i] * dims[i + 1] for i in range(len(dims) - 1)) * n   # fwd + 2x bwd
+        # algorithmic HBM bytes per INR: pe read + dpe written (P*16 elements each, 2 B in bf16 storage, else 4 B),
+        # target P*C*4, wvec read + dwvec written, sse
+        alg_bytes = (2 * 1024 * 16 * (2 if pe16 else 4) + 1024 * 3 * 4 + 2 * D * 4 + 4) * n
+        t = ms * 1e-3
+        share = round(ms / step_ms, 4)
+        if m.precision == 0:
+            # fp32 MFMA path: 0.51 ms of matrix work at peak vs 0.09 ms of HBM traffic -> matrix-bound
+            ach = flops / t / 1e12
+            roof = {"kernel": "fused SIREN fwd+MSE+bwd, fp32 MFMA (rcb_siren_loss_bwd)", "bound": "mfma",
+                    "achieved": round(ach, 3), "peak": 157.3, "unit": "TFLOP/s", "frac": round(ach / 157.3, 4),
+                    "traffic": None, "avg_launch_ms": round(ms, 4), "alg_flops_per_launch": flops,
+                    "alg_bytes_per_launch": alg_bytes, "share_of_step": share}
+        else:
+            # 16-bit operand path: 0.03 ms of matrix work at peak vs 0.09 ms of HBM traffic -> HBM-bound
+            # PMC counters cannot be collected inside this run: the figure comes from the committed rocprofv3 passes over THIS
+            # kernel.  It is tied to the kernel's source: the summary records the hash of the SIREN kernel files it was
+            # measured on, and a mismatch (kernel edited since) reports no traffic instead of a stale one.
+            traffic, traffic_note = None, None
+            try:
+                with open(os.path.join(ROOT, "profiles", PMC_FILE[pe16])) as f:
+                    pmc = json.load(f)
+                if n == 4096:
+                    if pmc.get("kernel_source_sha16") == siren_source_sha16():
+                        traffic = pmc["hbm_bytes_per_launch"]
+                    else:
+                        traffic_note = "stale: the SIREN kernel sources changed since the counters were collected"
+            except (OSError, KeyError, ValueError):
+                traffic = None
+            ach = alg_bytes / t / 1e9
+            # What actually limits this kernel is neither of the two: it is vector-ISSUE bound (one sine and one cosine per
+            # hidden unit and pixel, packed conversions, the address / loss arithmetic).  `valu` prices the tile loop's
+            # instruction census (tools/siren_census.py, from the compiler's assembly of these very sources) at the SIMD's issue
+            # costs and at the shader clock MEASURED inside the timed launches (rcb_siren_desc.clock_probe: every one of the
+            # first 256 workgroups reads s_memtime and the 100 MHz s_memrealtime on its own CU at its start and end): floor =
+            # tiles per SIMD x issue cycles per tile / clock.  `bound` keeps the contract's vocabulary
+            # (the higher of the HBM and MFMA fractions); `limiter` names the real one.
+            valu = None
+            try:
+                with open(os.path.join(ROOT, "profiles", "r05_siren_isa_census.json")) as f:
+                    cen = json.load(f)
+                if cen.get("source_sha16") == siren_census_sha16():
+                    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+                    n_simd = 4 * n_cu
+                    tiles = n * (1024 // 32)
+                    cyc = cen["vector_issue_cycles_per_tile"]
+                    per = tiles / n_simd / (siren_clock_ghz * 1e9) * 1e3          # ms per (cycle per tile and SIMD)
+                    fl = cen["floors_per_tile"]
+                    # every SIMD holds two tiles (two waves); per tile and SIMD: the matrix pipe and the transcendental unit
+                    # serve both waves, the CU's one LDS serves the four SIMDs, one wave's vector issue stream is the upper
+                    # end of the vector-issue cost (two waves interleave)
+                    floors = {"matrix_pipe_ms": round(fl["matrix_pipe_per_simd"] * per, 4),
+                              "transcendental_unit_ms": round(fl["transcendental_unit_per_simd"] * per, 4),
+                              "lds_ms": round(fl["lds_per_cu_for_one_tile_on_each_simd"] * per, 4),
+                              "vector_issue_one_stream_ms": round(cyc * per, 4)}
+                    floor_ms = cyc * per
+                    valu = {"instructions_per_tile": cen["instructions"], "by_class": cen["by_class"],
+                            "vector_issue_cycles_per_tile": cyc, "transcendental_cycles_per_tile": cen["transcendental_cycles_per_tile"],
+                            "mfma_pipe_cycles_per_tile": cen["mfma_pipe_cycles_per_tile"],
+                            "lds_cycles_per_tile_and_wave": cen["lds_cycles_per_tile_and_wave"],
+                            "scratch_instructions_in_tile_loop": cen["scratch_instructions_in_tile_loop"],
+                            "tiles_per_launch": tiles, "simds": n_simd, "shader_clock_ghz_measured": round(siren_clock_ghz, 3),
+                            "floors_at_measured_clock": floors,
+                            "issue_floor_ms_at_measured_clock": round(floor_ms, 4),
+                            "issue_floor_ms_at_2.4ghz": round(tiles / n_simd * cyc / 2.4e9 * 1e3, 4),
+                            "frac_of_issue_floor": round(floor_ms / ms, 4),
+                            "frac_of_largest_pipe_floor": round(max(floors["matrix_pipe_ms"], floors["transcendental_unit_ms"], floors["lds_ms"]) / ms, 4),
+                            "source": "profiles/r05_siren_isa_census.json (tools/siren_census.py)"}
+                else:
+                    valu = {"note": "stale census: the SIREN kernel sources changed since tools/siren_census.py ran"}
+            except (OSError, KeyError, ValueError):
+                valu = None
+            busy = (valu or {}).get("frac_of_issue_floor")
+            limiter = ("vector issue" if (busy is not None and busy >= 0.8) else
+                       "no single pipe: two waves per SIMD share a matrix pipe, a transcendental unit and (with the other three SIMDs) "
+                       "the LDS, each 30-50 % busy, and the phases of the two waves overlap only partly (profiles/r05_siren_sq_pmc.json)"
+                       if busy is not None else "unknown (no census)")
+            roof = {"kernel": "fused SIREN fwd+MSE+bwd, bf16 MFMA (rcb_siren_loss_bwd)", "bound": "hbm", "limiter": limiter,
+                    "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4),
+                    "traffic": traffic, "traffic_source": "profiles/%s (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE)" % PMC_FILE[pe16],
+                    "traffic_note": traffic_note,
+                    "avg_launch_ms": round(ms, 4), "alg_bytes_per_launch": alg_bytes, "alg_flops_per_launch": flops,
+                    "mfma_tflops": round(flops / t / 1e12, 1), "mfma_frac": round(flops / t / 2.5e15, 4), "valu": valu,
+                    "share_of_step": share}
+    return roof, siren_clock_ghz
+
+
 def comm_report(m, lt, up, dev):
     """Sharded step (every rank calls this): bytes of the two per-step all-reduces (gradients of the A matrices, of the conv
     weights), their duration on their own, the duration of each captured segment of the step, and the slack = compute
@@ -814,7 +961,7 @@ def main():
         if rank == 0:
             print("bench.py: sharded step form -- " + os.environ["RCB_STEP_FORM_CHOICE"], file=sys.stderr, flush=True)
 
-    from recombiner_amd import config, ops, tuning, utils
+    from recombiner_amd import config, tuning, utils
     tuned = False if a.no_tuned_gemms else tuning.enable_tuned_gemms()
     from recombiner_amd import prior_model as PM
     cfg = config.configs["cifar"]
@@ -881,144 +1028,14 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         el = float(tt.item())
 
-    # ---- roofline of the hot-path kernel (fused SIREN fwd + MSE + bwd), measured live ----------
-    roof = None
-    # The kernel is timed with events on its launch stream in the duty cycle it has inside the step: two training steps run
-    # between consecutive timed launches (on every rank: the sharded step contains collectives).  Ten back-to-back launches
-    # of this VALU-heavy kernel alone pull the clock down within a few launches (276 -> 335 us in one rocprofv3 trace),
-    # which is not the state the step runs it in.
-    reps = 10
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
-    if rank == 0:
-        meta = m._meta(Xd, 16)
-        pe = torch.randn(n, 1024, 16, device=dev) * 0.1
-        pe16 = m.precision != 0 and m.pe_bf16          # the storage type the training step uses for pe / dpe
-        if pe16:
-            pe = pe.bfloat16()
-        # launched as the step launches it: rows on 128-byte lines, and (16-bit modes) the bf16 copy of the gradient that
-        # the A transform's weight-gradient GEMM reads -- 2 D extra bytes per INR that the algorithmic figure does NOT count
-        ld = (D + 31) // 32 * 32
-        wv = torch.empty(n, ld, device=dev)[:, :D]
-        wv.copy_((torch.rand(n, D, device=dev) * 2 - 1) * 0.02)
-        want16 = bool(m.precision != 0 and m.split_gemm and not m.lowp_gemm and m.wgrad_bf16)
-        xf16 = ops.xf_bf16(Xd, m.precision) if m.precision in (1, 2) else None
-
-        probe = torch.zeros(256, 4, device=dev, dtype=torch.int64)     # per-workgroup clock stamps of the LAST launch
-
-        def launch():
-            return ops.siren_loss_bwd(Xd, pe, wv, Yd, 1.0 / 3072, meta, want_bf16=want16, xf16=xf16,
-                                      clock_probe=probe if m.precision == 1 else None)
-        for _ in range(2):
-            launch()
-    clocks = []
-    for e0, e1 in evs:
-        run(2)
-        if rank == 0:
-            # an untimed launch first: the stream is busy while the host submits e0 / kernel / e1, so the interval holds
-            # the kernel and not the host's launch latency
-            launch()
-            e0.record()
-            launch()
-            e1.record()
-            if m.precision == 1:
-                e1.synchronize()
-                clocks.append(ops.shader_clock_ghz(probe))
-    if rank == 0:
-        torch.cuda.synchronize()
-        ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / reps
-        siren_clock_ghz = (sum(clocks) / len(clocks)) if clocks else float("nan")
-        dims = m.dims
-        flops = 6.0 * 1024 * sum(dims[i] * dims[i + 1] for i in range(len(dims) - 1)) * n   # fwd + 2x bwd
-        # algorithmic HBM bytes per INR: pe read + dpe written (P*16 elements each, 2 B in bf16 storage, else 4 B),
-        # target P*C*4, wvec read + dwvec written, sse
-        alg_bytes = (2 * 1024 * 16 * (2 if pe16 else 4) + 1024 * 3 * 4 + 2 * D * 4 + 4) * n
-        t = ms * 1e-3
-        share = round(ms / (el / a.steps * 1e3), 4)
-        if m.precision == 0:
-            # fp32 MFMA path: 0.51 ms of matrix work at peak vs 0.09 ms of HBM traffic -> matrix-bound
-            ach = flops / t / 1e12
-            roof = {"kernel": "fused SIREN fwd+MSE+bwd, fp32 MFMA (rcb_siren_loss_bwd)", "bound": "mfma",
-                    "achieved": round(ach, 3), "peak": 157.3, "unit": "TFLOP/s", "frac": round(ach / 157.3, 4),
-                    "traffic": None, "avg_launch_ms": round(ms, 4), "alg_flops_per_launch": flops,
-                    "alg_bytes_per_launch": alg_bytes, "share_of_step": share}
-        else:
-            # 16-bit operand path: 0.03 ms of matrix work at peak vs 0.09 ms of HBM traffic -> HBM-bound
-            # PMC counters cannot be collected inside this run: the figure comes from the committed rocprofv3 passes over THIS
-            # kernel.  It is tied to the kernel's source: the summary records the hash of the SIREN kernel files it was
-            # measured on, and a mismatch (kernel edited since) reports no traffic instead of a stale one.
-            traffic, traffic_note = None, None
-            try:
-                with open(os.path.join(ROOT, "profiles", PMC_FILE[pe16])) as f:
-                    pmc = json.load(f)
-                if n == 4096:
-                    if pmc.get("kernel_source_sha16") == siren_source_sha16():
-                        traffic = pmc["hbm_bytes_per_launch"]
-                    else:
-                        traffic_note = "stale: the SIREN kernel sources changed since the counters were collected"
-            except (OSError, KeyError, ValueError):
-                traffic = None
-            ach = alg_bytes / t / 1e9
-            # What actually limits this kernel is neither of the two: it is vector-ISSUE bound (one sine and one cosine per
-            # hidden unit and pixel, packed conversions, the address / loss arithmetic).  `valu` prices the tile loop's
-            # instruction census (tools/siren_census.py, from the compiler's assembly of these very sources) at the SIMD's issue
-            # costs and at the shader clock MEASURED inside the timed launches (rcb_siren_desc.clock_probe: every one of the
-            # first 256 workgroups reads s_memtime and the 100 MHz s_memrealtime on its own CU at its start and end): floor =
-            # tiles per SIMD x issue cycles per tile / clock.  `bound` keeps the contract's vocabulary
-            # (the higher of the HBM and MFMA fractions); `limiter` names the real one.
-            valu = None
-            try:
-                with open(os.path.join(ROOT, "profiles", "r05_siren_isa_census.json")) as f:
-                    cen = json.load(f)
-                if cen.get("source_sha16") == siren_census_sha16():
-                    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
-                    n_simd = 4 * n_cu
-                    tiles = n * (1024 // 32)
-                    cyc = cen["vector_issue_cycles_per_tile"]
-                    per = tiles / n_simd / (siren_clock_ghz * 1e9) * 1e3          # ms per (cycle per tile and SIMD)
-                    fl = cen["floors_per_tile"]
-                    # every SIMD holds two tiles (two waves); per tile and SIMD: the matrix pipe and the transcendental unit
-                    # serve both waves, the CU's one LDS serves the four SIMDs, one wave's vector issue stream is the upper
-                    # end of the vector-issue cost (two waves interleave)
-                    floors = {"matrix_pipe_ms": round(fl["matrix_pipe_per_simd"] * per, 4),
-                              "transcendental_unit_ms": round(fl["transcendental_unit_per_simd"] * per, 4),
-                              "lds_ms": round(fl["lds_per_cu_for_one_tile_on_each_simd"] * per, 4),
-                              "vector_issue_one_stream_ms": round(cyc * per, 4)}
-                    floor_ms = cyc * per
-                    valu = {"instructions_per_tile": cen["instructions"], "by_class": cen["by_class"],
-                            "vector_issue_cycles_per_tile": cyc, "transcendental_cycles_per_tile": cen["transcendental_cycles_per_tile"],
-                            "mfma_pipe_cycles_per_tile": cen["mfma_pipe_cycles_per_tile"],
-                            "lds_cycles_per_tile_and_wave": cen["lds_cycles_per_tile_and_wave"],
-                            "scratch_instructions_in_tile_loop": cen["scratch_instructions_in_tile_loop"],
-                            "tiles_per_launch": tiles, "simds": n_simd, "shader_clock_ghz_measured": round(siren_clock_ghz, 3),
-                            "floors_at_measured_clock": floors,
-                            "issue_floor_ms_at_measured_clock": round(floor_ms, 4),
-                            "issue_floor_ms_at_2.4ghz": round(tiles / n_simd * cyc / 2.4e9 * 1e3, 4),
-                            "frac_of_issue_floor": round(floor_ms / ms, 4),
-                            "frac_of_largest_pipe_floor": round(max(floors["matrix_pipe_ms"], floors["transcendental_unit_ms"], floors["lds_ms"]) / ms, 4),
-                            "source": "profiles/r05_siren_isa_census.json (tools/siren_census.py)"}
-                else:
-                    valu = {"note": "stale census: the SIREN kernel sources changed since tools/siren_census.py ran"}
-            except (OSError, KeyError, ValueError):
-                valu = None
-            busy = (valu or {}).get("frac_of_issue_floor")
-            limiter = ("vector issue" if (busy is not None and busy >= 0.8) else
-                       "no single pipe: two waves per SIMD share a matrix pipe, a transcendental unit and (with the other three SIMDs) "
-                       "the LDS, each 30-50 % busy, and the phases of the two waves overlap only partly (profiles/r05_siren_sq_pmc.json)"
-                       if busy is not None else "unknown (no census)")
-            roof = {"kernel": "fused SIREN fwd+MSE+bwd, bf16 MFMA (rcb_siren_loss_bwd)", "bound": "hbm", "limiter": limiter,
-                    "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4),
-                    "traffic": traffic, "traffic_source": "profiles/%s (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE)" % PMC_FILE[pe16],
-                    "traffic_note": traffic_note,
-                    "avg_launch_ms": round(ms, 4), "alg_bytes_per_launch": alg_bytes, "alg_flops_per_launch": flops,
-                    "mfma_tflops": round(flops / t / 1e12, 1), "mfma_frac": round(flops / t / 2.5e15, 4), "valu": valu,
-                    "share_of_step": share}
+    # ---- --full only from here on: what the headline figure does not need ------------------------------------------------
+    roof, siren_clock_ghz, comm, cpu, extras = None, float("nan"), None, None, {}
+    if a.full:
+        roof, siren_clock_ghz = siren_roofline(m, run, Xd, Yd, n, D, dev, rank, el / a.steps * 1e3)
     # ---- sharded runs: what the per-step collectives move, and how much compute they have to hide behind -----------------
-    comm = None
-    if ws > 1:
+    if a.full and ws > 1:
         comm = comm_report(m, lt, up, dev)
-    cpu = None
-    extras = {}
-    if rank == 0 and ws == 1 and not a.no_extras:
+    if a.full and rank == 0 and ws == 1 and not a.no_extras:
         def one_stream_table():
             # per-kernel durations are taken from the one-stream form of the same step (a second capture, dropped afterwards)
             keep = os.environ.get("RCB_FORK")
@@ -1048,7 +1065,7 @@ def main():
                 extras[key] = fn()
             except Exception as exc:            # extras never take the bench line down; the failure is visible in it
                 extras[key] = {"error": repr(exc)[:300]}
-    if rank == 0 and ws == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and ws == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(cfg)
     if rank == 0:
         inr_steps = n * ws * a.steps / el
@@ -1074,9 +1091,11 @@ def main():
         if comm is not None:
             out["comm"] = comm
         out.update(extras)
-        # The full report (~20 KB with the CPU baseline, the census and the untimed extras) goes to stderr as one JSON line; the
-        # result line on stdout keeps the timed figures only: a line that long is cut off by callers that read an output's tail.
-        print(json.dumps(out), file=sys.stderr, flush=True)
+        # With --full the full report (~20 KB with the CPU baseline, the census and the untimed extras) goes to stderr as one
+        # JSON line; the result line on stdout keeps the timed figures only: a line that long is cut off by callers that read an
+        # output's tail.
+        if a.full:
+            print(json.dumps(out), file=sys.stderr, flush=True)
         line = {k: v for k, v in out.items() if k != "cpu_baseline" and k not in extras}
         if roof is not None:
             line["roofline"] = {k: v for k, v in roof.items() if k != "valu"}

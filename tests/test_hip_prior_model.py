@@ -374,6 +374,28 @@ def test_hidden_layers_of_different_widths_fp32():
     np.testing.assert_allclose(lt.A[1].detach().cpu().numpy(), A[1].numpy(), rtol=1e-3, atol=3e-5)
 
 
+def test_bench_plain_run_reports_the_headline_only():
+    """A plain `python bench.py` run sets up, warms up, times the steps and prints the result line, nothing more: no live
+    roofline of the SIREN kernel and no full report on stderr (those, the CPU baseline and the untimed extras come with
+    --full)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RCB_DIST_BACKEND")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--inrs", "64"],
+                         env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["unit"] == "INRs trained/s" and rec["higher_is_better"] is True and rec["dtype"] == "bf16" and rec["steps"] == 3
+    assert rec["value"] == pytest.approx(64 / (rec["ms_per_step"] * 1e-3) / (200 + 549 * 100))
+    assert rec["roofline"] is None and "comm" not in rec
+    assert not any(ln.startswith("{") for ln in out.stderr.splitlines()), out.stderr[-2000:]
+
+
 def test_bench_gpus_flag_launches_ranks():
     """`python bench.py --gpus 2` (no launcher) must start two ranks itself and report n_gpus = 2 -- here over gloo with
     both ranks on the one GPU of the box (the rehearsal switch) -- and must refuse the RCCL form on a one-GPU box."""
@@ -384,7 +406,7 @@ def test_bench_gpus_flag_launches_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RCB_DIST_BACKEND")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--inrs", "64",
-           "--no-cpu-baseline", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-extras"]
     if torch.cuda.device_count() < 2:
         out = subprocess.run(cmd, env=base, capture_output=True, text=True, timeout=600)
         assert out.returncode != 0 and "--gpus 2 requested" in out.stderr
@@ -394,7 +416,7 @@ def test_bench_gpus_flag_launches_ranks():
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     rec = json.loads(line)
     assert rec["n_gpus"] == 2 and rec["config"]["inrs_per_gpu"] == 64 and rec["value"] > 0
-    # the sharded step's communication report: both buckets, every segment, mappings identical on both ranks
+    # the sharded step's communication report (--full): both buckets, every segment, mappings identical on both ranks
     comm = rec["comm"]
     assert comm["mappings_identical_across_ranks"] is True and comm["backend"] == "gloo"
     assert comm["allreduce_bytes_per_step"] == 4 * (3 * 1056 * 1056 + 99 * 99 + 251024) and len(comm["segment_ms"]) == 4
@@ -413,7 +435,7 @@ def test_bench_two_ranks_over_rccl():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RCB_DIST_BACKEND")}
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "2", "--inrs", "512",
-           "--no-cpu-baseline", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-extras"]
     out = subprocess.run(cmd, env=dict(base, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

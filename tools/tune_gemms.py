@@ -32,7 +32,7 @@ if __name__ == "__main__":
     tuning.enable_tuned_gemms(out, tune=True)
     here = os.path.dirname(os.path.abspath(__file__))
     if what == "bench":
-        sys.argv = ["bench.py", "--steps", "12", "--warmup", "4", "--no-cpu-baseline"]
+        sys.argv = ["bench.py", "--steps", "12", "--warmup", "4", "--full", "--no-cpu-baseline"]
         sys.path.insert(0, os.path.dirname(here))
         import bench
         bench.main()
