@@ -406,6 +406,25 @@ int rcb_step_end(const float* sse, int32_t n_sse, double mse_scale, const int64_
                  double* kl_log, int64_t n_log, int64_t* step, int64_t* aux_counter /* nullable: += 1 */,
                  rcb_stream_t stream);
 
+/* Combined launches of a captured training step on one rank with the mappings trained (step_fused.hip).  Each is ONE
+ * launch whose block ranges run the bodies of the separate entry points: every output is bit-identical to theirs.
+ *   rcb_step_prepare = rcb_step_begin + rcb_atrans_pack + rcb_upconv_weff_build (arguments as theirs, in that order)
+ *   rcb_step_tail    = rcb_posterior_bwd(lv, cfg) on its flat fast path + rcb_adam_multi(tensors, count, cfg) +
+ *                      rcb_step_end(sse, n_sse, mse_scale, lv->kl_accum, mse_log, kl_log, n_log, step, aux_counter).
+ *                      The log entry is written by the workgroup that finishes last; `tickets` are RCB_STEP_TAIL_TICKETS
+ *                      device uint32 that are zero on entry and zero again on exit (zero-fill them once).  lv must satisfy rcb_step_tail_eligible (the conditions of
+ *                      the flat fast path: plain level, one sample, Adam, 16-byte aligned arrays, rows * cols % 4 == 0),
+ *                      else RCB_ERR_UNSUPPORTED: the caller issues the three launches.                              */
+int rcb_step_prepare(const float* adam_table, int64_t n_steps, const int64_t* step, float* dyn, int64_t* kl_slots,
+                     const float* const* A, int32_t n_layers, const int32_t* sizes, void* packed, int32_t want_lo,
+                     const float* W1, const float* b1, const float* W2, const float* W3, void* weff1, void* b1rep,
+                     int32_t bf16_out, float* weff2, float* weff3, void* frag_pack, rcb_stream_t stream);
+#define RCB_STEP_TAIL_TICKETS 65
+int rcb_step_tail_eligible(const rcb_level_bwd* lv);
+int rcb_step_tail(const rcb_level_bwd* lv, const rcb_adam_cfg* cfg, const rcb_adam_tensor* tensors, int32_t count,
+                  const float* sse, int32_t n_sse, double mse_scale, double* mse_log, double* kl_log, int64_t n_log,
+                  int64_t* step, int64_t* aux_counter /* nullable: += 1 */, uint32_t* tickets, rcb_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K12: column moments for the closed-form prior refit (main_prior_training.py:157-172), as EXACT fixed-point sums.
  * For x = loc[rows, cols] and sigma = softplus(log_scale) / 6, every term v in {x, x^2, sigma^2} is split at 2^-30:

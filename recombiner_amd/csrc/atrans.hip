@@ -23,6 +23,7 @@
 // workgroup) and issues <= 28 MFMAs per chunk on <= 7 accumulator tiles; two waves per SIMD cover each other's LDS latency.
 // Workgroups sharing a row tile are mapped to one XCD (they re-read the same x rows through its L2).
 #include "rcb_common.h"
+#include "prepare_bodies.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -487,68 +488,8 @@ __global__ void __launch_bounds__(256) atrans_slab_sum_kernel(SlabArgs a) {
   }
 }
 
-// ---- packed images of the mappings ------------------------------------------------------------------------------------
-struct PackArgs {
-  const float* A[MAXL];
-  int L[MAXL], Lp[MAXL], tile0[MAXL + 1];     // first 32 x 32 tile of every layer
-  long long poff[MAXL];                       // element offset of the layer inside one plane
-  long long plane;                            // elements of one plane
-  __bf16* out;
-  int n_layers, want_lo;
-};
-
-__global__ void __launch_bounds__(256) atrans_pack_kernel(PackArgs a) {
-  // one 32 x 32 tile per block; a thread takes four consecutive elements of a row: one 16-byte load (layer sizes that are
-  // multiples of 4), 8-byte bf16 stores in both orientations (2-byte stores made this kernel 13 us for 40 MB)
-  __shared__ float tile[32][33];
-  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-  int l = 0;
-  while (l + 1 < a.n_layers && (int)blockIdx.x >= a.tile0[l + 1]) ++l;
-  const int L = a.L[l], Lp = a.Lp[l], nt = Lp >> 5;
-  const int tl = blockIdx.x - a.tile0[l];
-  const int k0 = (tl / nt) * 32, j0 = (tl % nt) * 32;
-  const float* __restrict__ A = a.A[l];
-  const int r = threadIdx.x >> 3, c4 = (threadIdx.x & 7) * 4;
-  __bf16* __restrict__ fwd_hi = a.out + a.poff[l];
-  __bf16* __restrict__ dg_hi = a.out + a.plane + a.poff[l];
-  __bf16* __restrict__ fwd_lo = a.out + 2 * a.plane + a.poff[l];
-  __bf16* __restrict__ dg_lo = a.out + 3 * a.plane + a.poff[l];
-  auto split_store = [&](const float (&v)[4], __bf16* hi, __bf16* lo, long long at) {
-    bf16x4 h, lw;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      h[i] = (__bf16)v[i];
-      lw[i] = (__bf16)(v[i] - (float)h[i]);
-    }
-    *reinterpret_cast<bf16x4*>(hi + at) = h;
-    if (a.want_lo) *reinterpret_cast<bf16x4*>(lo + at) = lw;
-  };
-  {
-    const int k = k0 + r, j = j0 + c4;
-    float v[4] = {0.f, 0.f, 0.f, 0.f};
-    if (k < L) {
-      if ((L & 3) == 0 && j + 3 < L) {
-        const float4 t = *reinterpret_cast<const float4*>(A + (long long)k * L + j);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (j + i < L) ? A[(long long)k * L + j + i] : 0.f;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) tile[r][c4 + i] = v[i];
-    split_store(v, dg_hi, dg_lo, (long long)k * Lp + j);                // data gradient: rows k, contraction j contiguous
-  }
-  __syncthreads();
-  {
-    float v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = tile[c4 + i][r];
-    split_store(v, fwd_hi, fwd_lo, (long long)(j0 + r) * Lp + k0 + c4);   // forward: rows j (output column), contraction k contiguous
-  }
-}
-
-inline int pad32(int v) { return (v + 31) / 32 * 32; }
+// ---- packed images of the mappings: atrans_pack_body (prepare_bodies.h) ----------------------------------------------
+__global__ void __launch_bounds__(256) atrans_pack_kernel(PackArgs a) { atrans_pack_body(a, (int)blockIdx.x); }
 
 
 struct Blk {
@@ -588,25 +529,9 @@ extern "C" int rcb_atrans_pack(const float* const* A, int32_t n_layers, const in
                                rcb_stream_t stream) {
   RCB_REQUIRE(A && sizes && packed && n_layers >= 1 && n_layers <= MAXL, RCB_ERR_ARG, "atrans_pack: bad arguments (%d layers)", n_layers);
   RCB_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, RCB_ERR_ARG, "atrans_pack: packed buffer must be 16-byte aligned");
+  for (int l = 0; l < n_layers; ++l) RCB_REQUIRE(A[l] && sizes[l] >= 1, RCB_ERR_ARG, "atrans_pack: layer %d null / empty", l);
   PackArgs a;
-  memset(&a, 0, sizeof(a));
-  long long plane = 0;
-  int tiles = 0;
-  for (int l = 0; l < n_layers; ++l) {
-    RCB_REQUIRE(A[l] && sizes[l] >= 1, RCB_ERR_ARG, "atrans_pack: layer %d null / empty", l);
-    a.A[l] = A[l];
-    a.L[l] = sizes[l];
-    a.Lp[l] = pad32(sizes[l]);
-    a.poff[l] = plane;
-    a.tile0[l] = tiles;
-    plane += (long long)a.Lp[l] * a.Lp[l];
-    tiles += (a.Lp[l] / 32) * (a.Lp[l] / 32);
-  }
-  a.tile0[n_layers] = tiles;
-  a.plane = plane;
-  a.out = reinterpret_cast<__bf16*>(packed);
-  a.n_layers = n_layers;
-  a.want_lo = want_lo;
+  const int tiles = fill_pack_args(a, A, n_layers, sizes, packed, want_lo);
   atrans_pack_kernel<<<tiles, 256, 0, (hipStream_t)stream>>>(a);
   RCB_LAUNCH_CHECK();
   return RCB_OK;

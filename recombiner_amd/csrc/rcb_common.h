@@ -108,4 +108,20 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// ---- "the workgroup that finishes last does the epilogue", without fences -----------------------------------------------
+// The textbook form (every workgroup: __threadfence(), then an atomicAdd ticket; the last one: __threadfence(), then read) is
+// ruinous on this chip: the L2 is per XCD and not coherent across XCDs, so an agent-scope release fence WRITES BACK the L2
+// and an acquire INVALIDATES it, and the fences of a launch serialise there -- measured 31-37 ns per fence and wave: +680 us
+// on a 5 400-block launch of 30 us, +150 us on a 1 024-block one.  What the last workgroup must see is little, so it is made
+// to travel past the L2 instead: data as agent-scope relaxed atomics (sc1: performed at the memory side, coherent for the
+// whole device by themselves), and the ORDER "my data, then my ticket" by waiting for the data operations' completion
+// (s_waitcnt 0: every outstanding load, store and atomic of the wave acknowledged) before the ticket atomic is issued.  A
+// workgroup that draws the last ticket therefore finds every other workgroup's data performed, and reads it with agent-scope
+// atomic loads.  Plain loads and stores of the same launch are NOT ordered by this: only what goes through these helpers.
+__device__ __forceinline__ void vmem_wait_all() { __builtin_amdgcn_s_waitcnt(0); }
+template <typename T>
+__device__ __forceinline__ void agent_store(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <typename T>
+__device__ __forceinline__ T agent_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 }  // namespace rcb

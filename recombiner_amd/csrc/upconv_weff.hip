@@ -8,150 +8,14 @@
 //   stages 2, 3 (nearest x2 -> conv 3x3 pad 1): Weff[ty,tx,ci,a,b,co] = sum_{k in K(a,ty), l in K(b,tx)} W[co,ci,k,l]
 //       with K(0,0) = {0}, K(0,1) = {1,2}, K(1,0) = {0,1}, K(1,1) = {2}      (layout of upconv.hip's weff_index)
 #include "rcb_common.h"
+#include "prepare_bodies.h"
 
 using namespace rcb;
 
 namespace {
 
-__device__ __forceinline__ int tap_of(int a, int k) { return a == 0 ? (k == 0 ? 0 : 1) : (k == 2 ? 1 : 0); }
-
-// one effective weight straight from the 3x3 taps: Weff[ty][tx][ci][a][b][co] = sum_{k in K(a,ty), l in K(b,tx)} W[co][ci][k][l]
-__device__ __forceinline__ float weff_of(const float* __restrict__ W, int ty, int tx, int ci, int a, int b, int co) {
-  const float* w = W + (co * 64 + ci) * 9;
-  // (all nine taps loaded, the ones outside (a, ty) x (b, tx) dropped by a select: a branch per tap serialises the loads)
-  float wv[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) wv[k] = w[k];
-  float acc = 0.f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int l = 0; l < 3; ++l) acc += (tap_of(a, k) == ty && tap_of(b, l) == tx) ? wv[k * 3 + l] : 0.f;
-  return acc;
-}
-
-struct WeffArgs {
-  const float* W1;   // [64][128][5][5]
-  const float* b1;   // [64]
-  const float* W2;   // [64][64][3][3]
-  const float* W3;   // [16][64][3][3]
-  void* weff1;       // [512][4096] bf16 or fp32
-  void* b1rep;       // [4096] same type: b1 tiled over the 64 output pixels
-  float* weff2;      // [2][2][64][2][2][64]
-  float* weff3;      // [2][2][64][2][2][16]
-  int bf16_out;
-  uint4* pack;       // nullable: MFMA fragment images for the phase-conv kernels (layout: include/rcb.h)
-};
-
-template <int COUT>
-__device__ __forceinline__ void build_stage(const float* __restrict__ W, float* __restrict__ out, int ci, float* w, int tid) {
-  {   // (loads first, then stores: see the stage-1 branch)
-    constexpr int NT = (COUT * 9 + 255) / 256;
-    float t3[NT];
-#pragma unroll
-    for (int k = 0; k < NT; ++k) {
-      const int e = tid + 256 * k;
-      t3[k] = e < COUT * 9 ? W[((e / 9) * 64 + ci) * 9 + e % 9] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < NT; ++k)
-      if (tid + 256 * k < COUT * 9) w[tid + 256 * k] = t3[k];
-  }
-  __syncthreads();
-  for (int e = tid; e < 16 * COUT; e += 256) {
-    const int co = e % COUT, ab = (e / COUT) & 3, tt = e / (4 * COUT);
-    const int a = ab >> 1, b = ab & 1, ty = tt >> 1, tx = tt & 1;
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-      for (int l = 0; l < 3; ++l)
-        if (tap_of(a, k) == ty && tap_of(b, l) == tx) acc += w[co * 9 + k * 3 + l];
-    out[((tt * 64 + ci) * 4 + ab) * COUT + co] = acc;
-  }
-}
-
-// blocks [0, 512): stage 1, one (input channel i, source pixel st) each; [512, 576): stage 2 per ci;
-// [576, 640): stage 3 per ci; 640: the tiled bias; [641, 641 + 88): the packed MFMA fragments (optional)
-__global__ void __launch_bounds__(256) weff_build_kernel(WeffArgs a) {
-  __shared__ float w[64 * 25];
-  const int blk = blockIdx.x, tid = threadIdx.x;
-  if (blk < 512) {
-    const int i = blk >> 2, st = blk & 3, s = st >> 1, t = st & 1;
-    {   // all loads first, then the stores (a load-store loop waits one memory round trip per trip: seven here)
-      float t7[7];
-#pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        const int e = tid + 256 * k;
-        t7[k] = e < 64 * 25 ? a.W1[((e / 25) * 128 + i) * 25 + e % 25] : 0.f;
-      }
-#pragma unroll
-      for (int k = 0; k < 7; ++k)
-        if (tid + 256 * k < 64 * 25) w[tid + 256 * k] = t7[k];
-    }
-    __syncthreads();
-    for (int rem = 2 * tid; rem < 4096; rem += 512) {         // two neighbouring output channels per thread: 4-byte bf16 stores
-      const int y = rem >> 9, x = (rem >> 6) & 7, o = rem & 63;
-      // taps whose source row y + k - 2 lies in rows [4s, 4s + 3] of the up-sampled grid (and likewise for columns)
-      const int k0 = max(0, 4 * s + 2 - y), k1 = min(4, 4 * s + 5 - y);
-      const int l0 = max(0, 4 * t + 2 - x), l1 = min(4, 4 * t + 5 - x);
-      float acc0 = 0.f, acc1 = 0.f;
-      for (int k = k0; k <= k1; ++k)
-        for (int l = l0; l <= l1; ++l) {
-          acc0 += w[o * 25 + k * 5 + l];
-          acc1 += w[(o + 1) * 25 + k * 5 + l];
-        }
-      const long long idx = ((long long)st * 128 + i) * 4096 + rem;
-      if (a.bf16_out) {
-        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-        const bf16x2 pr = {(__bf16)acc0, (__bf16)acc1};
-        *reinterpret_cast<bf16x2*>(reinterpret_cast<__bf16*>(a.weff1) + idx) = pr;
-      } else {
-        *reinterpret_cast<float2*>(reinterpret_cast<float*>(a.weff1) + idx) = make_float2(acc0, acc1);
-      }
-    }
-  } else if (blk < 576) {
-    build_stage<64>(a.W2, a.weff2, blk - 512, w, tid);
-  } else if (blk < 640) {
-    build_stage<16>(a.W3, a.weff3, blk - 576, w, tid);
-  } else if (blk == 640) {
-    for (int e = tid; e < 4096; e += 256) {
-      const float v = a.b1[e & 63];
-      if (a.bf16_out) reinterpret_cast<__bf16*>(a.b1rep)[e] = (__bf16)v;
-      else reinterpret_cast<float*>(a.b1rep)[e] = v;
-    }
-  } else if (a.pack) {
-    // one 16-byte fragment (8 bf16) per thread, each element summed straight from the conv taps
-    const int e = (blk - 641) * 256 + tid;          // < RCB_UPCONV_PACK_UINT4
-    const int lane = e & 63, q = lane & 31, h = lane >> 5;
-    union { __bf16 v[8]; uint4 u; } f;
-    if (e < 8192) {                                  // F2: stage-2 forward, [ph][mt][ty][tx][kb][lane]
-      const int s5 = e >> 6, kb = s5 & 3, tx = (s5 >> 2) & 1, ty = (s5 >> 3) & 1, mt = (s5 >> 4) & 1, ph = s5 >> 5;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f.v[j] = (__bf16)weff_of(a.W2, ty, tx, 16 * kb + 8 * h + j, ph >> 1, ph & 1, 32 * mt + q);
-    } else if (e < 16384) {                          // D2: stage-2 data gradient, [kh][mt][c][kb][lane]
-      const int s5 = (e - 8192) >> 6, kb = s5 & 3, c = (s5 >> 2) & 7, mt = (s5 >> 5) & 1, kh = s5 >> 6;
-      const int n = 8 * kh + c, ry = (n >> 2) - 1, rx = (n & 3) - 1;
-      const int pa = ry & 1, ty = (ry <= 0) ? 1 : 0, pb = rx & 1, tx = (rx <= 0) ? 1 : 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f.v[j] = (__bf16)weff_of(a.W2, ty, tx, 32 * mt + q, pa, pb, 16 * kb + 8 * h + j);
-    } else if (e < 20480) {                          // F3: stage-3 forward, [pa][pb][ty][tx][kb2][lane]: A operands of
-      //                                                 v_mfma_f32_16x16x32_bf16 (row co = lane & 15, ci = 32 kb2 + 8 (lane >> 4) + j);
-      //                                                 the second half of the region is unused
-      if (e >= 16384 + 2048) return;
-      const int s5 = (e - 16384) >> 6, kb2 = s5 & 1, tx = (s5 >> 1) & 1, ty = (s5 >> 2) & 1, pb = (s5 >> 3) & 1, pa = s5 >> 4;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f.v[j] = (__bf16)weff_of(a.W3, ty, tx, 32 * kb2 + 8 * (lane >> 4) + j, pa, pb, lane & 15);
-    } else {                                         // D3: stage-3 data gradient, [combo][mt][lane]
-      const int s5 = (e - 20480) >> 6, mt = s5 & 1, n = s5 >> 1;
-      const int ry = (n >> 2) - 1, rx = (n & 3) - 1;
-      const int pa = ry & 1, ty = (ry <= 0) ? 1 : 0, pb = rx & 1, tx = (rx <= 0) ? 1 : 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f.v[j] = (__bf16)weff_of(a.W3, ty, tx, 32 * mt + q, pa, pb, 8 * h + j);
-    }
-    a.pack[e] = f.u;
-  }
-}
+// tap_of / weff_of / build_stage and the body of the build: weff_build_body (prepare_bodies.h)
+__global__ void __launch_bounds__(256) weff_build_kernel(WeffArgs a) { weff_build_body(a, (int)blockIdx.x); }
 
 struct WeffGradArgs {
   const void* dweff1;   // [512][4096] bf16 or fp32
@@ -269,7 +133,7 @@ extern "C" int rcb_upconv_weff_build(const float* W1, const float* b1, const flo
                                      rcb_stream_t stream) {
   RCB_REQUIRE(W1 && b1 && W2 && W3 && weff1 && b1rep && weff2 && weff3, RCB_ERR_ARG, "upconv_weff_build: null pointer");
   WeffArgs a{W1, b1, W2, W3, weff1, b1rep, weff2, weff3, bf16_out ? 1 : 0, reinterpret_cast<uint4*>(frag_pack)};
-  weff_build_kernel<<<frag_pack ? 641 + RCB_UPCONV_PACK_UINT4 / 256 : 641, 256, 0, (hipStream_t)stream>>>(a);
+  weff_build_kernel<<<weff_build_blocks(frag_pack != nullptr), 256, 0, (hipStream_t)stream>>>(a);
   RCB_LAUNCH_CHECK();
   return RCB_OK;
 }

@@ -533,12 +533,11 @@ def philox_normal(n, seed: int, rng_stream: int, step, device="cuda", group_offs
     return out
 
 
-def posterior_bwd(lv: LevelSpec, p_loc, p_scale, p_is_log: bool, kl_scalar: float, d_out, eps, samples: int,
-                  beta=None, group_idx=None, n_groups=0, adam: Optional[AdamCfg] = None, state=None,
-                  want_grads=False, kl_accum=None, kl_scalar_dev=None, next_sample: Optional["NextSample"] = None):
-    """Fused gradient gather + KL gradient (+ Adam).  Returns (g_loc, g_log_scale) when requested.
-    next_sample (plain levels with Adam): also draw the next step's sample from the updated parameters."""
-    lib = _lib.load()
+def _level_bwd(lv: LevelSpec, p_loc, p_scale, p_is_log: bool, kl_scalar: float, d_out, eps, samples: int,
+               beta=None, group_idx=None, n_groups=0, adam: Optional[AdamCfg] = None, state=None,
+               want_grads=False, kl_accum=None, kl_scalar_dev=None, next_sample: Optional["NextSample"] = None):
+    """the rcb_level_bwd of a posterior update (arguments of posterior_bwd) -> (structure, g_loc, g_log_scale, workspace that
+    must outlive the launch)"""
     g_loc = g_ls = None
     if want_grads:
         g_loc = torch.empty_like(lv.loc)
@@ -586,6 +585,17 @@ def posterior_bwd(lv: LevelSpec, p_loc, p_scale, p_is_log: bool, kl_scalar: floa
         b.rng_stream = int(ns.rng_stream)
     if d_out is not None and tuple(d_out.shape) != (lv.n_inr, samples, lv.cols_out):
         raise RcbError(f"d_out must be [{lv.n_inr},{samples},{lv.cols_out}], got {tuple(d_out.shape)}")
+    return b, g_loc, g_ls, sums_ws
+
+
+def posterior_bwd(lv: LevelSpec, p_loc, p_scale, p_is_log: bool, kl_scalar: float, d_out, eps, samples: int,
+                  beta=None, group_idx=None, n_groups=0, adam: Optional[AdamCfg] = None, state=None,
+                  want_grads=False, kl_accum=None, kl_scalar_dev=None, next_sample: Optional["NextSample"] = None):
+    """Fused gradient gather + KL gradient (+ Adam).  Returns (g_loc, g_log_scale) when requested.
+    next_sample (plain levels with Adam): also draw the next step's sample from the updated parameters."""
+    lib = _lib.load()
+    b, g_loc, g_ls, _ws = _level_bwd(lv, p_loc, p_scale, p_is_log, kl_scalar, d_out, eps, samples, beta, group_idx, n_groups,
+                                    adam, state, want_grads, kl_accum, kl_scalar_dev, next_sample)
     check(lib.rcb_posterior_bwd(C.byref(b), C.byref(adam) if adam is not None else None, stream_ptr()),
           "rcb_posterior_bwd")
     return g_loc, g_ls
@@ -751,19 +761,79 @@ def step_end(step, sse=None, mse_scale=1.0, kl_slots=None, mse_log=None, kl_log=
 ADAM_MAX_TENSORS = 16
 
 
+def _adam_tensors(chunk, what):
+    arr = (AdamTensor * len(chunk))()
+    for i, (p, g, m, v) in enumerate(chunk):
+        if not (p.is_contiguous() and g.is_contiguous()) or g.numel() != p.numel():
+            raise RcbError(f"{what} needs contiguous tensors of matching size")
+        arr[i] = AdamTensor(ptr(p.detach(), f32).value, ptr(g, f32).value, ptr(m, f32).value, ptr(v, f32).value,
+                            p.numel())
+    return arr
+
+
 def adam_multi(params, grads, ms, vs, cfg: AdamCfg):
     """Adam step over a list of fp32 tensors in one launch (rcb_adam_multi); lists longer than 16 are chunked."""
     lib = _lib.load()
     items = list(zip(params, grads, ms, vs))
     for k in range(0, len(items), ADAM_MAX_TENSORS):
         chunk = items[k:k + ADAM_MAX_TENSORS]
-        arr = (AdamTensor * len(chunk))()
-        for i, (p, g, m, v) in enumerate(chunk):
-            if not (p.is_contiguous() and g.is_contiguous()) or g.numel() != p.numel():
-                raise RcbError("adam_multi needs contiguous tensors of matching size")
-            arr[i] = AdamTensor(ptr(p.detach(), f32).value, ptr(g, f32).value, ptr(m, f32).value, ptr(v, f32).value,
-                                p.numel())
-        check(lib.rcb_adam_multi(arr, len(chunk), C.byref(cfg), stream_ptr()), "rcb_adam_multi")
+        check(lib.rcb_adam_multi(_adam_tensors(chunk, "adam_multi"), len(chunk), C.byref(cfg), stream_ptr()), "rcb_adam_multi")
+
+
+def step_fused_enabled():
+    """the combined launches of the captured training step (rcb_step_prepare / rcb_step_tail): on unless RCB_STEP_FUSED=0 (a test
+    aid: the separate launches as the reference of the equality tests and of a same-box A/B) or RCB_POSTERIOR_WG_PER_CU asks
+    for the persistent form of the posterior update, which only the separate launch has"""
+    return _os.environ.get("RCB_STEP_FUSED", "1") != "0" and int(_os.environ.get("RCB_POSTERIOR_WG_PER_CU") or 0) == 0
+
+
+def step_prepare(table, step, dyn, kl_slots, atrans, A, W1, b1, W2, W3, bf16_out):
+    """step_begin(table, step, dyn, kl_slots) + atrans.prepare(A) + upconv_weff_build(W1, b1, W2, W3, bf16_out) in ONE launch
+    (rcb_step_prepare): every output bit-identical to theirs.  -> (Weff1, b1rep, Weff2, Weff3, pack) of upconv_weff_build."""
+    lib = _lib.load()
+    if table.dim() != 2 or table.shape[1] != 2 or (kl_slots is not None and kl_slots.numel() != 1024):
+        raise RcbError("step_prepare: table must be [n_steps, 2], kl_slots [1024]")
+    arr = atrans.mats_arg(A)
+    if (tuple(W1.shape), tuple(W2.shape), tuple(W3.shape)) != ((64, 128, 5, 5), (64, 64, 3, 3), (16, 64, 3, 3)):
+        raise RcbError("step_prepare: conv weight shapes of the CIFAR upsampling net expected")
+    dev, dt = W1.device, (bf16 if bf16_out else f32)
+    weff1 = torch.empty(512, 4096, device=dev, dtype=dt)
+    b1rep = torch.empty(4096, device=dev, dtype=dt)
+    weff2 = torch.empty(2, 2, 64, 2, 2, 64, device=dev, dtype=f32)
+    weff3 = torch.empty(2, 2, 64, 2, 2, 16, device=dev, dtype=f32)
+    pack = torch.empty(UPCONV_PACK_UINT4 * 16, device=dev, dtype=torch.uint8)
+    check(lib.rcb_step_prepare(ptr(table, f32), C.c_int64(table.shape[0]), ptr(step, torch.int64), ptr(dyn, f32),
+                               ptr(kl_slots, torch.int64, True), arr, len(atrans.sizes), atrans._sizes_c, ptr(atrans.packed),
+                               int(atrans.terms == 3), ptr(W1.detach(), f32), ptr(b1.detach(), f32), ptr(W2.detach(), f32),
+                               ptr(W3.detach(), f32), ptr(weff1), ptr(b1rep), int(bool(bf16_out)), ptr(weff2), ptr(weff3),
+                               ptr(pack), stream_ptr()), "rcb_step_prepare")
+    return weff1, b1rep, weff2, weff3, pack
+
+
+STEP_TAIL_TICKETS = 65
+
+
+def step_tail(level_args, level_kwargs, params, grads, ms, vs, cfg: AdamCfg, tickets, step, sse, mse_scale, mse_log, kl_log,
+              aux_counter=None):
+    """posterior_bwd(*level_args, adam=cfg, **level_kwargs) + adam_multi(params, grads, ms, vs, cfg) + step_end(step, sse,
+    mse_scale, kl_accum, mse_log, kl_log, aux_counter) in ONE launch (rcb_step_tail), bit-identical to the three.  tickets:
+    zero int32 [STEP_TAIL_TICKETS] the launch leaves zero.  Returns False -- nothing launched -- when the level does not take the flat fast
+    path of the posterior update or the tensors do not fit one Adam launch: the caller issues the separate launches."""
+    lib = _lib.load()
+    if not (1 <= len(params) <= ADAM_MAX_TENSORS) or sum(p.numel() for p in params) == 0:
+        return False
+    b, _, _, _ws = _level_bwd(*level_args, adam=cfg, **level_kwargs)
+    if not lib.rcb_step_tail_eligible(C.byref(b)):
+        return False
+    if tickets.dtype != torch.int32 or tickets.numel() != STEP_TAIL_TICKETS:
+        raise RcbError(f"step_tail: tickets must be {STEP_TAIL_TICKETS} int32")
+    arr = _adam_tensors(list(zip(params, grads, ms, vs)), "step_tail")
+    n_log = min(t.numel() for t in (mse_log, kl_log) if t is not None) if (mse_log is not None or kl_log is not None) else 0
+    check(lib.rcb_step_tail(C.byref(b), C.byref(cfg), arr, len(params), ptr(sse, f32, True), 0 if sse is None else sse.numel(),
+                            C.c_double(mse_scale), ptr(mse_log, f64, True), ptr(kl_log, f64, True), C.c_int64(n_log),
+                            ptr(step, torch.int64), ptr(aux_counter, torch.int64, True), ptr(tickets, torch.int32), stream_ptr()),
+          "rcb_step_tail")
+    return True
 
 
 def col_moments_fx(loc, log_scale):
@@ -1339,13 +1409,19 @@ class ATransform:
         self._plans = {}
         self.n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count
 
-    def prepare(self, A):
+    def mats_arg(self, A):
+        """the mappings as the pointer array rcb_atrans_pack / rcb_step_prepare take"""
         mats = [a.detach() for a in A]
+        if len(mats) != len(self.sizes):
+            raise RcbError("ATransform.prepare: one matrix per layer expected")
         for a, n in zip(mats, self.sizes):
             if tuple(a.shape) != (n, n) or a.dtype != f32 or not a.is_cuda or not a.is_contiguous():
                 raise RcbError("ATransform.prepare: contiguous fp32 GPU matrices [L_l, L_l] expected")
-        arr = (C.c_void_p * len(mats))(*[a.data_ptr() for a in mats])
-        check(_lib.load().rcb_atrans_pack(arr, len(mats), self._sizes_c, ptr(self.packed), int(self.terms == 3), stream_ptr()),
+        return (C.c_void_p * len(mats))(*[a.data_ptr() for a in mats])
+
+    def prepare(self, A):
+        arr = self.mats_arg(A)
+        check(_lib.load().rcb_atrans_pack(arr, len(self.sizes), self._sizes_c, ptr(self.packed), int(self.terms == 3), stream_ptr()),
               "rcb_atrans_pack")
 
     def _plan(self, rows):

@@ -186,13 +186,14 @@ class PriorBNNmodel(nn.Module):
             return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
         return None
 
-    def _pe(self, upsample_net, lpe, stitched=False, lpe16=None):
+    def _pe(self, upsample_net, lpe, stitched=False, lpe16=None, weff_cache=None):
         """lpe [S, N, *lat, C] -> pe [N, S, P, 16]: hand-written phase-conv kernels in the 16-bit modes
         where the geometry is instantiated, the nn.Module (MIOpen) otherwise.  `stitched`: see _pe_layout.
-        lpe16: the producer's bf16 copy of lpe [N, Dlpe] (stage-1 operand; saves the cast pass)."""
+        lpe16: the producer's bf16 copy of lpe [N, Dlpe] (stage-1 operand; saves the cast pass).
+        weff_cache: the phase-form weights of THIS step, already built (ops.step_prepare), in _UpsampleCifarFn's cache form."""
         if self.precision != 0 and hip_path_supported(upsample_net, self.pixel_sizes, self.upsample_factors, self.patch,
                                                       self.data_dim):
-            return upsample_cifar_hip(upsample_net, lpe, self.stage1_bf16, self.pe_bf16, lpe16=lpe16)
+            return upsample_cifar_hip(upsample_net, lpe, self.stage1_bf16, self.pe_bf16, frozen_cache=weff_cache, lpe16=lpe16)
         net = upsample_net
         if self.precision != 0 and tiled_2d_preferred(upsample_net, self.patch, self.data_dim):
             net = stitched2d_module(upsample_net)                  # stitched 2-D grid: phase-conv kernels on overlapping tiles
@@ -310,7 +311,8 @@ class PriorBNNmodel(nn.Module):
                world, id(linear_transform), id(upsample_net), self.precision, self.lowp_gemm, self.split_gemm, self.split_terms, self.split_dgrad_terms,
                self.wgrad_bf16, self.stage1_bf16, self.pe_bf16, self.fused_noise, self.fuse_next_sample, self.patch,
                self.operand_planes, self.redraw_noise, self.hier_rng, self.rng_row_offset, self.rng_seed_override,
-               os.environ.get("RCB_FORK", str(self.stream_forks)), self.force_segments, self.capture_collectives,
+               os.environ.get("RCB_FORK", str(self.stream_forks)), os.environ.get("RCB_STEP_FUSED", "1"),
+               os.environ.get("RCB_POSTERIOR_WG_PER_CU", "0"), self.force_segments, self.capture_collectives,
                tuple(None if q is None else tuple(q.shape) for q in priors),
                # the captured kernels read and Adam-update these STORAGES: Module.cpu()/.to() (a checkpoint written the
                # reference's way, main_prior_training.py:334-338) re-allocates param.data while id() stays equal
@@ -340,6 +342,7 @@ class PriorBNNmodel(nn.Module):
                       tab=ops.adam_table(lr, rows).to(dev), dyn=torch.zeros(2, device=dev, dtype=torch.float32),
                       step_t=torch.zeros(1, device=dev, dtype=torch.long),
                       kl_slots=torch.zeros(1024, device=dev, dtype=torch.int64),       # fixed point, 2^-24 nats
+                      tickets=torch.zeros(ops.STEP_TAIL_TICKETS, device=dev, dtype=torch.int32),     # rcb_step_tail: zero between launches
                       mse_buf=torch.zeros(rows, device=dev, dtype=torch.float64),
                       kl_buf=torch.zeros(rows, device=dev, dtype=torch.float64),
                       pri=[None if q is None else torch.empty_like(q) for q in priors],
@@ -459,9 +462,25 @@ class PriorBNNmodel(nn.Module):
         _uf.WEIGHT_SIDE_STREAM = side if (fork_mask & 4) else None
         if split is not None and not training_mappings:
             split.prepare(A)                          # fixed mappings: packed once per call, outside the captured step
+        # Combined launches (csrc/step_fused.hip) where the step is the one-rank form with the mappings trained -- the first
+        # branch of body() -- and the kernels they combine are the ones this configuration runs anyway:
+        #   head: step_begin + the pack of the A matrices + the phase-form conv weights (ops.step_prepare);
+        #   tail: the lpe level's update + Adam on the mappings + step_end (ops.step_tail), behind the join with the forked
+        #         stream (the network level's KL slots are an input).  RCB_FORK bit 16 (Adam on the third stream) and a step
+        #         whose network-level update is not on the forked stream keep the separate launches.
+        # Same bodies, same bits; RCB_STEP_FUSED=0 forces the separate launches (tests, same-box A/B).
+        fused_step = bool(ops.step_fused_enabled() and dev.type == "cuda" and fuse_next and flat is None and training_mappings)
+        fused_head = bool(fused_step and split is not None and self.precision != 0 and pe_lay is None
+                          and hip_path_supported(upsample_net, self.pixel_sizes, self.upsample_factors, self.patch, self.data_dim))
 
         def seg1a():
-            ops.step_begin(tab, step_t, dyn, kl_slots)
+            weff_cache = None
+            if fused_head:
+                c1, c2, c3 = upsample_net.conv1, upsample_net.conv2, upsample_net.conv3
+                weff_cache = {("weff", bool(self.stage1_bf16)): ops.step_prepare(tab, step_t, dyn, kl_slots, split, A, c1.weight,
+                                                                                 c1.bias, c2.weight, c3.weight, self.stage1_bf16)}
+            else:
+                ops.step_begin(tab, step_t, dyn, kl_slots)
             # ---- sample + the two forward maps.  With the fused next sample h_w was written by the previous step's posterior
             # update (the step's LAST big kernel, see body()): its A transform goes first, while h_w is still in the Infinity Cache
             # (measured: read cold, half a step later, the forward A transform takes 10 us longer)
@@ -482,7 +501,7 @@ class PriorBNNmodel(nn.Module):
                     if pe_lay is not None:                                   # stitched grids, addressed in place by the kernel
                         pe_c = self._pe(upsample_net, lpe_t, stitched=True)
                     else:
-                        pe = self._pe(upsample_net, lpe_t, lpe16=lpe16)      # [N, 1, P, E]
+                        pe = self._pe(upsample_net, lpe_t, lpe16=lpe16, weff_cache=weff_cache)      # [N, 1, P, E]
                         pe_c = pe.reshape(N, pe.shape[2], pe.shape[3]).contiguous()   # (not pe[:, 0]: select's backward
                         #                                                               materialises zeros + a copy)
                 return lpe_t, e_lpe, pe_c
@@ -522,7 +541,7 @@ class PriorBNNmodel(nn.Module):
                     h16 = h_w.to(torch.bfloat16)
                     A16 = [a.detach().to(torch.bfloat16) for a in A]
                 elif split is not None:
-                    if training_mappings:
+                    if training_mappings and not fused_head:
                         split.prepare(A)                  # the mappings change every step when they are trained
                     wvec = split.forward(h_w, split.new_rows(N))
                 else:
@@ -679,14 +698,25 @@ class PriorBNNmodel(nn.Module):
                 ops.posterior_bwd(lv, pl, ps, False, 1.0, st["dh3"], e, 1, adam=cfg, state=stt, kl_accum=kl_slots,
                                   kl_scalar_dev=beta_dev, next_sample=nxt_net)
 
-        def seg2_lpe():
+        def lpe_update():
+            """arguments of the lpe level's posterior update (ops.posterior_bwd, without adam=)"""
             nxt_lpe = None
             if fuse_lpe:
                 nxt_lpe = ops.NextSample((smp_lpe[0], smp_lpe[1], smp_lpe[2] if lpe16_want else None), rng_seed, 1, rng_ctr, 1,
                                          redraw_eps=redraw_lpe, group_offset=goff_lpe)
-            ops.posterior_bwd(lpe_lv, pri_d[2].reshape(-1), pri_d[3].reshape(-1), False, 1.0, st["d_lpe"],
-                              st["e_lpe"], 1, adam=cfg, state=lpe_state, kl_accum=kl_slots, kl_scalar_dev=beta_dev,
-                              next_sample=nxt_lpe)
+            return ((lpe_lv, pri_d[2].reshape(-1), pri_d[3].reshape(-1), False, 1.0, st["d_lpe"], st["e_lpe"], 1),
+                    dict(state=lpe_state, kl_accum=kl_slots, kl_scalar_dev=beta_dev, next_sample=nxt_lpe))
+
+        def seg2_lpe():
+            args, kwargs = lpe_update()
+            ops.posterior_bwd(*args, adam=cfg, **kwargs)
+
+        def seg_tail():
+            """seg2_lpe + seg3_adam + seg3_end in one launch; False (nothing launched) if the level does not qualify"""
+            args, kwargs = lpe_update()
+            return ops.step_tail(args, kwargs, [p.data for p in A + conv], [g.contiguous() for g in st["grads"]],
+                                 [m for m, _ in map_state], [v for _, v in map_state], cfg, ws["tickets"], step_t, st["sse"],
+                                 1.0 / (P * Cc), mse_buf, kl_buf, aux_counter=rng_ctr)
 
         def seg2():
             seg2_net()
@@ -744,6 +774,8 @@ class PriorBNNmodel(nn.Module):
                     if pending:
                         torch.cuda.current_stream().wait_stream(fork)
                         st.pop("fork_keep", None)
+                    if fused_step and pending and (fork_mask & 8) and seg_tail():
+                        return                           # (the whole tail was that one launch)
                     seg2_lpe()
                     seg3_adam()
                 if not (pending and (fork_mask & 8)):
