@@ -732,6 +732,15 @@ def adam_table(lr, n_steps, beta1=0.9, beta2=0.999):
     return torch.from_numpy(np.stack([lr / (1.0 - beta1 ** t), np.sqrt(1.0 - beta2 ** t)], 1).astype(np.float32))
 
 
+def zeroed_views(shapes, device):
+    """-> (flat, iterator over fp32 views of the given shapes into flat): ONE zero-filled buffer, every view starting on a
+    256-byte boundary (the Adam moments of a train() call: `flat.zero_()` resets all of them with one launch)"""
+    sizes = [int(np.prod(shp)) for shp in shapes]
+    offs = np.cumsum([0] + [(n + 63) // 64 * 64 for n in sizes]).tolist()
+    flat = torch.zeros(offs[-1], device=device, dtype=f32)
+    return flat, iter([flat[o:o + n].view(shp) for o, n, shp in zip(offs, sizes, shapes)])
+
+
 def adam_flat(p, g, m, v, cfg: AdamCfg):
     lib = _lib.load()
     if not (p.is_contiguous() and g.is_contiguous()):
@@ -1478,7 +1487,7 @@ class ATransform:
         ld = (self.cols + 31) // 32 * 32
         return torch.empty(rows, ld, device=self.device, dtype=f32)[:, :self.cols]
 
-    def wgrad(self, h_w, dw, h16=None, dw16=None, bf16_hi=True, part="all"):
+    def wgrad(self, h_w, dw, h16=None, dw16=None, bf16_hi=True):
         """dA[l] = h_w[:, lo:hi]^T @ dw[:, lo:hi], summed over the rows (INRs x samples).  With bf16_hi the widest layers
         (adjacent, one size, a multiple of 8) take bf16 operands in one batched GEMM with fp32 accumulation: the sum over
         thousands of rows averages the unbiased operand rounding down, unlike the per-row products of forward / dgrad.
@@ -1492,17 +1501,13 @@ class ATransform:
             dw16 = dw.hi
         if (hp or dp) and not bf16_hi:
             h_w, dw, hp, dp = (h_w.float() if hp else h_w), (dw.float() if dp else dw), False, False
-        # part: "all", or -- for callers that run the two halves on different streams -- "wide" (the batched GEMM of the widest
-        # layers: reads only the bf16 copies) / "rest" (everything else: reads the fp32 rows); entries of the other half are None
         out = [None] * len(self.sizes)
         big = max(self.sizes)
         wide = [i for i, n in enumerate(self.sizes) if n == big]
         adjacent = all(b == a + 1 for a, b in zip(wide, wide[1:]))
         rows = h_w.rows if hp else h_w.shape[0]
         wide_ok = bool(bf16_hi and big >= 256 and big % 8 == 0 and adjacent and self.slices[wide[0]][0] % 8 == 0)
-        if part == "wide" and not wide_ok:
-            return out
-        if wide_ok and part != "rest":
+        if wide_ok:
             k, lo0 = len(wide), self.slices[wide[0]][0]
 
             def view(t16, t32):
@@ -1514,11 +1519,9 @@ class ATransform:
             g = torch.bmm(view(h16, h_w).transpose(1, 2), view(dw16, dw), out_dtype=f32)
             for j, i in enumerate(wide):
                 out[i] = g[j]
-        if part == "wide":
-            return out
         lib = _lib.load()
         for i, (lo, hi) in enumerate(self.slices):
-            if out[i] is not None or (part == "rest" and wide_ok and i in wide):
+            if out[i] is not None:
                 continue
             n = hi - lo
             if n <= 256:

@@ -3,7 +3,7 @@ ELBO/KL, Adam -- the call surface of the reference's prior_model.py (same class 
 argument order and return values, cited per member) on top of hand-written HIP kernels.
 
 Where the reference chains torch ops through autograd, `train()` here runs one fused pipeline per
-step: sample (K1, in-kernel noise) -> upsampling net (hand-written phase-conv kernels in the 16-bit modes,
+step (train_step.py): sample (K1, in-kernel noise) -> upsampling net (hand-written phase-conv kernels in the 16-bit modes,
 MIOpen only in the fp32 parity mode) -> A transform (atrans.hip) -> fused SIREN fwd+MSE+bwd (K3/K4) -> A-transform
 backward -> upsampling-net backward -> fused reparam-bwd + KL-bwd + Adam (K1'/K5'/K11), replayed as one HIP graph.
 `forward()` / `calculate_kl()` stay autograd-capable through custom Functions so user code written
@@ -16,8 +16,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import dist as rdist
 from . import ops
+from . import train_step
 from .ops import LevelSpec, SirenMeta
 from .upsample_fast import (hip_path_supported, tiled_2d_preferred, phase_form_preferred, phase_module,
                             stitched2d_module, upsample_cifar_hip)
@@ -136,14 +136,13 @@ class PriorBNNmodel(nn.Module):
         self.redraw_noise = os.environ.get("RCB_REDRAW_EPS", "1") != "0"
         # three-level presets: the latent weights' noise drawn in the sampling kernel (RCB_HIER_RNG=0: three randn launches; A/B)
         self.hier_rng = os.environ.get("RCB_HIER_RNG", "1") != "0"
-        # concurrent streams inside the captured step (bit mask, see train(); 0 = one stream).  Measured on MI355X, same-box A/B of
+        # concurrent streams inside the captured step (bit mask of 2, 4 and 8, see train_step.py; 0 = one stream; RCB_FORK
+        # overrides; any other bit is a ValueError in train()).  Measured on MI355X, same-box A/B of
         # the 4096-INR CIFAR step (gpurun_out r04_ab5): one stream 1.162 ms; A-transform backward beside the upsampling net's
         # backward (2) 1.125; + the net's weight-gradient side on a third stream (6) 1.109; + the network level's posterior
         # update (HBM-bound) straight behind the A backward, i.e. beside the LDS / MFMA-bound upsampling kernels (14) 1.089:
-        # -6.2 %.  The forward fork (1) gains nothing (7: 1.113); the update EARLIER, right behind the data gradient and beside
-        # the stage-3 / stage-2 backward kernels (32; needs a second bf16 sample buffer) LOSES 7 % (46: 1.152 vs 1.079): the
-        # HBM-bound update slows the LDS-bound kernels more than it gains; the wide weight-gradient GEMM on the third stream with
-        # the update behind it and the data gradient (64) loses 2 % (78: 1.142 vs 1.116).  Same kernels, same operands: bit-identical.
+        # -6.2 %.  Same kernels, same operands: bit-identical.  (The orderings once behind the bits 1, 16, 32 and 64 gained
+        # nothing or lost 2 to 7 % and are gone: DESIGN.md section 4.5 keeps their measurements.)
         self.stream_forks = 14
         # measurement aid: take the SHARDED form of the step (four captured segments around two host-enqueued all-reduces)
         # even when `dp_group` has a single rank -- what the segmentation costs on the host, without a second GPU
@@ -186,14 +185,16 @@ class PriorBNNmodel(nn.Module):
             return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
         return None
 
-    def _pe(self, upsample_net, lpe, stitched=False, lpe16=None, weff_cache=None):
+    def _pe(self, upsample_net, lpe, stitched=False, lpe16=None, weff_cache=None, weight_side_stream=None):
         """lpe [S, N, *lat, C] -> pe [N, S, P, 16]: hand-written phase-conv kernels in the 16-bit modes
         where the geometry is instantiated, the nn.Module (MIOpen) otherwise.  `stitched`: see _pe_layout.
         lpe16: the producer's bf16 copy of lpe [N, Dlpe] (stage-1 operand; saves the cast pass).
-        weff_cache: the phase-form weights of THIS step, already built (ops.step_prepare), in _UpsampleCifarFn's cache form."""
+        weff_cache: the phase-form weights of THIS step, already built (ops.step_prepare), in _UpsampleCifarFn's cache form.
+        weight_side_stream: second stream for the weight-gradient side of the hand-written kernels' backward."""
         if self.precision != 0 and hip_path_supported(upsample_net, self.pixel_sizes, self.upsample_factors, self.patch,
                                                       self.data_dim):
-            return upsample_cifar_hip(upsample_net, lpe, self.stage1_bf16, self.pe_bf16, frozen_cache=weff_cache, lpe16=lpe16)
+            return upsample_cifar_hip(upsample_net, lpe, self.stage1_bf16, self.pe_bf16, frozen_cache=weff_cache, lpe16=lpe16,
+                                      weight_side_stream=weight_side_stream)
         net = upsample_net
         if self.precision != 0 and tiled_2d_preferred(upsample_net, self.patch, self.data_dim):
             net = stitched2d_module(upsample_net)                  # stitched 2-D grid: phase-conv kernels on overlapping tiles
@@ -284,578 +285,25 @@ class PriorBNNmodel(nn.Module):
         x = x.to(dev)
         y = y.to(dev).contiguous()
         N = y.shape[0]
-        P, Cc = y.shape[1], y.shape[2]
         priors = [prior_loc, prior_scale, prior_lpe_loc, prior_lpe_scale, prior_h_loc, prior_h_scale,
                   prior_hh_loc, prior_hh_scale]
         priors = [None if p is None else p.detach().to(dev, torch.float32).contiguous() for p in priors]
-        net, lpe_lv = self._levels()
-        A = [a for a in linear_transform.A]
-        conv = [p for p in upsample_net.parameters()]
-        slices = self._layer_slices()
-        D = self._d_net
-        # Gradients of the shared mappings are summed over ranks only when the caller asked for it by setting `dp_group`
-        # (drivers.train_prior and bench.py do): an initialised process group alone must not couple models that merely
-        # live in the same job (several priors / bit-rates trained side by side).
-        world, rank_id = 1, 0
-        if self.dp_group is not None:
-            world = torch.distributed.get_world_size(self.dp_group)
-            rank_id = torch.distributed.get_rank(self.dp_group)      # ranks must not draw the same noise
-
-        # ---- workspace -----------------------------------------------------------------------------------------
-        # Everything a captured step references lives in a workspace that survives across train() calls: Adam state
-        # (re-zeroed per call = the reference's fresh optimiser), step counter, logs, and device copies of what changes
-        # between calls (priors, beta, the noise counter).  The EM loop calls train() 550 times with 100 steps each;
-        # re-capturing the graph every call costs ~14 ms = 9 % of such a call, replaying a cached one nothing.
-        graphable = bool(self.use_graph and self.noise_source is None and dev.type == "cuda" and not verbose)
-        key = (N, P, Cc, x.data_ptr(), tuple(x.shape), tuple(x.stride()), y.data_ptr(), float(lr), bool(training_mappings),
-               world, id(linear_transform), id(upsample_net), self.precision, self.lowp_gemm, self.split_gemm, self.split_terms, self.split_dgrad_terms,
-               self.wgrad_bf16, self.stage1_bf16, self.pe_bf16, self.fused_noise, self.fuse_next_sample, self.patch,
-               self.operand_planes, self.redraw_noise, self.hier_rng, self.rng_row_offset, self.rng_seed_override,
-               os.environ.get("RCB_FORK", str(self.stream_forks)), os.environ.get("RCB_STEP_FUSED", "1"),
-               os.environ.get("RCB_POSTERIOR_WG_PER_CU", "0"), self.force_segments, self.capture_collectives,
-               tuple(None if q is None else tuple(q.shape) for q in priors),
-               # the captured kernels read and Adam-update these STORAGES: Module.cpu()/.to() (a checkpoint written the
-               # reference's way, main_prior_training.py:334-338) re-allocates param.data while id() stays equal
-               tuple(q.data_ptr() for q in A + conv), tuple(q.data_ptr() for q in self.parameters()))
-        ws = self._ws if graphable else None
-        if ws is not None and (ws["key"] != key or ws["rows"] < n_epoch):
-            ws = None
-        if ws is None:
-            # all Adam moments (per-INR levels and shared mappings) as views of ONE zero-filled buffer: a train() call resets
-            # them with one launch instead of ~30 (the reference creates a fresh optimiser per call: main_prior_training.py)
-            shapes = [lv.loc.shape for lv in net for _ in range(4)] + [lpe_lv.loc.shape] * 4
-            if training_mappings:
-                shapes += [q.shape for q in A + conv for _ in range(2)]
-            offs, tot = [], 0
-            for shp in shapes:
-                offs.append(tot)
-                tot += (int(np.prod(shp)) + 63) // 64 * 64          # every view starts on a 256-byte boundary
-            state_flat = torch.zeros(tot, device=dev, dtype=torch.float32)
-            views = iter([state_flat[o:o + int(np.prod(shp))].view(shp) for o, shp in zip(offs, shapes)])
-
-            def st4(lv):
-                return {k: next(views) for k in ("m_loc", "v_loc", "m_ls", "v_ls")}
-            rows = max(n_epoch, 256) if graphable else n_epoch
-            self._train_calls += 1
-            ws = dict(key=key, rows=rows, state_flat=state_flat, net_state=[st4(lv) for lv in net], lpe_state=st4(lpe_lv),
-                      map_state=[(next(views), next(views)) for q in A + conv] if training_mappings else None,
-                      tab=ops.adam_table(lr, rows).to(dev), dyn=torch.zeros(2, device=dev, dtype=torch.float32),
-                      step_t=torch.zeros(1, device=dev, dtype=torch.long),
-                      kl_slots=torch.zeros(1024, device=dev, dtype=torch.int64),       # fixed point, 2^-24 nats
-                      tickets=torch.zeros(ops.STEP_TAIL_TICKETS, device=dev, dtype=torch.int32),     # rcb_step_tail: zero between launches
-                      mse_buf=torch.zeros(rows, device=dev, dtype=torch.float64),
-                      kl_buf=torch.zeros(rows, device=dev, dtype=torch.float64),
-                      pri=[None if q is None else torch.empty_like(q) for q in priors],
-                      beta_dev=torch.zeros(1, device=dev, dtype=torch.float32),
-                      rng_ctr=torch.full((1,), int(self._rng_ctr_init), device=dev, dtype=torch.long), graphs=None,
-                      seed=(int(self.random_seed) * 0x9E3779B97F4A7C15 + int(torch.initial_seed()) * 0xBF58476D1CE4E5B9
-                            + self._train_calls * 0x94D049BB133111EB + rank_id * 0xD6E8FEB86659FD93) & (2 ** 64 - 1),
-                      # sharded: the mapping gradients of a step travel in two buckets of one flat buffer (dist.GradBuckets)
-                      flat=(rdist.GradBuckets([q.shape for q in A], [q.shape for q in conv], dev, self.dp_group)
-                            if (training_mappings and (world > 1 or (self.force_segments and self.dp_group is not None))) else None),
-                      # the bf16 copy of the coordinate grid the captured SIREN launches read: owned by the workspace,
-                      # i.e. alive exactly as long as the graphs that reference its address
-                      xf16=ops.xf_bf16(x, self.precision) if (self.precision in (1, 2) and dev.type == "cuda") else None)
-            # 16-bit modes: the A transform on the hand-written kernels of atrans.hip (every geometry)
-            ws["split"] = (ops.ATransform(slices, dev, self.split_terms, self.split_dgrad_terms)
-                           if (self.split_gemm and self.precision != 0 and not self.lowp_gemm) else None)
-            if graphable:
-                self._ws = ws
-        else:
-            ws["state_flat"].zero_()
-        n_a = sum(q.numel() for q in A)                     # the A matrices come first in the gradient bucket
-        net_state, lpe_state, map_state = ws["net_state"], ws["lpe_state"], ws["map_state"]
-        tab, dyn, step_t, kl_slots = ws["tab"], ws["dyn"], ws["step_t"], ws["kl_slots"]
-        mse_buf, kl_buf, beta_dev, rng_ctr, flat, split = (ws["mse_buf"], ws["kl_buf"], ws["beta_dev"], ws["rng_ctr"],
-                                                         ws["flat"], ws["split"])
-        step_t.zero_()
-        beta_dev.fill_(float(kl_beta))
-        for dst, src in zip(ws["pri"], priors):
-            if dst is not None:
-                dst.copy_(src)
-        pri_d = ws["pri"]              # what the kernels read (stable addresses); `priors` = this call's values
-        net_priors = [(pri_d[0], pri_d[1])] + ([(pri_d[4], pri_d[5]), (pri_d[6], pri_d[7])] if self.patch else [])
-        # per-step Adam scalars and the step counter live on the device, so that one captured HIP graph of the
-        # step body can be replayed for every step (the host launch cost of ~60 kernels is ~2 ms per step)
-        cfg = ops.adam_cfg(lr, 1, dyn=dyn)
-
-        # The step runs as four segments so that, under data-parallel sharding, the gradient bucket of the shared
-        # mappings is all-reduced asynchronously BETWEEN captured graphs while work that does not depend on it proceeds:
-        #   seg1a: sample .. SIREN .. A-transform backward | all-reduce(A grads, 13.4 MB) ||
-        #   seg1b: upsampling-net backward | all-reduce(conv grads, 1 MB) || seg2: posterior update | wait |
-        #   seg3: Adam on the mappings + bookkeeping.
-        st = {}
-        # in-kernel noise: a pure function of (seed, stream, counter, element); the counter lives in the workspace and is
-        # never reset, so every step of every train() call draws fresh noise, replayed or not
-        # (the lpe is a single plain level in every preset; the latent weights are one only without patches: the three-level
-        # presets keep stored noise for the weights and draw the lpe's -- two thirds of what they sample -- in the kernels)
-        rng_lpe = bool(self.fused_noise and self.noise_source is None and ops.rng_eligible(lpe_lv))
-        use_rng = rng_lpe and len(net) == 1 and ops.rng_eligible(net[0])
-        rng_seed = ws["seed"] if self.rng_seed_override is None else int(self.rng_seed_override) & (2 ** 64 - 1)
-        # three levels of latent weights (patched presets): every level's noise drawn in the sampling kernel (Philox streams 0, 2, 3
-        # at the element index of the [N, D] noise arrays: independent of torch's generator and of how the rows are sharded) and
-        # written for the posterior updates, instead of three randn launches read back by the kernel
-        rng_hier = bool(self.hier_rng and rng_lpe and not use_rng and ops.hier_rng_eligible(net) and (N * D) % 4 == 0
-                        and (self.rng_row_offset * D) % 4 == 0)
-        goff_net = ops.rng_group_offset(self.rng_row_offset, D) if (use_rng or rng_hier) else 0
-        goff_lpe = ops.rng_group_offset(self.rng_row_offset, self._d_lpe) if rng_lpe else 0
-
-        want16 = split is not None and training_mappings and self.wgrad_bf16     # bf16 operands of the weight gradient
-        lpe16_want = bool(use_rng and self.stage1_bf16 and self.precision != 0 and not self.patch)
-        # (the fused form lives on the posterior update's flat path: element counts divisible by 4)
-        fuse_next = bool(use_rng and self.fuse_next_sample and (N * D) % 4 == 0 and (N * self._d_lpe) % 4 == 0)
-        # the A transform's operands as (hi, lo) planes written by their producers (single-level presets with in-kernel noise;
-        # layers must start at multiples of 8 columns for the 16-byte LDS-DMA pieces)
-        planes = bool(split is not None and use_rng and self.operand_planes
-                      and all(lo % 8 == 0 for (lo, hi) in slices if (hi - lo) % 8 == 0))
-        fuse_lpe = bool(fuse_next or (rng_lpe and self.fuse_next_sample and (N * self._d_lpe) % 4 == 0))
-        redraw = bool(fuse_next and self.redraw_noise)
-        redraw_lpe = bool(fuse_lpe and self.redraw_noise)
-        smp_net = smp_lpe = None
-        if fuse_next:
-            if "smp_net" not in ws:
-                ws["smp_net"] = ops.sample_buffers(net[0], True, planes=planes, want_eps=not redraw)
-                ws["smp_lpe"] = ops.sample_buffers(lpe_lv, True, want_eps=not redraw)
-            smp_net, smp_lpe = ws["smp_net"], ws["smp_lpe"]
-        elif fuse_lpe:
-            if "smp_lpe" not in ws:
-                ws["smp_lpe"] = ops.sample_buffers(lpe_lv, lpe16_want, want_eps=not redraw_lpe)
-            smp_lpe = ws["smp_lpe"]
-        elif planes and "smp_net" not in ws:
-            ws["smp_net"] = ops.sample_buffers(net[0], planes=True)
-        if fuse_next and not planes and "h16_next" not in ws and smp_net[2] is not None:
-            ws["h16_next"] = torch.empty_like(smp_net[2])
-
-        def prime():
-            """the sample of the call's first step (every later one comes out of the previous step's posterior update)"""
-            if fuse_next:
-                ops.reparam_rng(net[0], rng_seed, 0, rng_ctr, want_bf16=want16, buffers=smp_net, group_offset=goff_net)
-            ops.reparam_rng(lpe_lv, rng_seed, 1, rng_ctr, want_bf16=lpe16_want, buffers=smp_lpe, group_offset=goff_lpe)
-
-        pe_lay = self._pe_layout()
-        # sharded step: with RCCL the two all-reduces are CAPTURED inside the one step graph (measured on this stack: an
-        # all-reduce captures and replays correctly from the capturing stream and from a forked one, tools/rccl_capture_probe.py;
-        # the four-segment form costs 142 us of host work per 1.09 ms step, bench.py `sharded_step_host_cost`); other
-        # backends (gloo: the CPU rehearsals) keep the four captured segments around host-enqueued collectives
-        # Default (capture_collectives None): captured on a ONE-rank RCCL communicator only -- that is all this form has ever
-        # run on (the pool has one GPU per box).  With more ranks the four-segment form runs unless RCB_CAPTURE_COLLECTIVES=1
-        # (or capture_collectives=True) opts in; bench.py's launcher sets it after an N-rank tools/rccl_capture_probe.py run
-        # succeeded within its timeout, so that the first N > 1 execution of the captured form is never the measured one.
-        capture_coll = bool(flat is not None and self.capture_collectives is not False
-                            and (self.capture_collectives is True
-                                 or (torch.distributed.get_backend(self.dp_group) == "nccl"
-                                     and torch.distributed.get_world_size(self.dp_group) == 1)))
-        # stream forks inside the (captured) step -- bit mask, same kernels on the same operands, so results are identical:
-        #   1: the A transform's forward beside the upsampling net's forward;  2: the A transform's backward beside the
-        #   upsampling net's backward;  4: the weight-gradient side of the upsampling net's backward beside its data path
-        #   (upsample_fast.WEIGHT_SIDE_STREAM);  8: the network level's posterior update right behind the A transform's backward
-        #   on the forked stream (it only needs dh);  16: Adam on the mappings on the third stream beside the lpe level's update;
-        #   32 (with 2 and 8, one rank): that update right behind the data gradient, the wide weight-gradient GEMM on the third stream;
-        #   64 (with 2 and 8, one rank): the wide GEMM on the third stream, the update behind it AND the data gradient
-        fork_mask = int(os.environ.get("RCB_FORK", str(self.stream_forks))) if dev.type == "cuda" else 0
-        fork = side = None
-        if fork_mask:
-            if "fork_stream" not in ws:
-                ws["fork_stream"], ws["side_stream"] = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-            fork, side = ws["fork_stream"], ws["side_stream"]
-        from . import upsample_fast as _uf
-        _uf.WEIGHT_SIDE_STREAM = side if (fork_mask & 4) else None
-        if split is not None and not training_mappings:
-            split.prepare(A)                          # fixed mappings: packed once per call, outside the captured step
-        # Combined launches (csrc/step_fused.hip) where the step is the one-rank form with the mappings trained -- the first
-        # branch of body() -- and the kernels they combine are the ones this configuration runs anyway:
-        #   head: step_begin + the pack of the A matrices + the phase-form conv weights (ops.step_prepare);
-        #   tail: the lpe level's update + Adam on the mappings + step_end (ops.step_tail), behind the join with the forked
-        #         stream (the network level's KL slots are an input).  RCB_FORK bit 16 (Adam on the third stream) and a step
-        #         whose network-level update is not on the forked stream keep the separate launches.
-        # Same bodies, same bits; RCB_STEP_FUSED=0 forces the separate launches (tests, same-box A/B).
-        fused_step = bool(ops.step_fused_enabled() and dev.type == "cuda" and fuse_next and flat is None and training_mappings)
-        fused_head = bool(fused_step and split is not None and self.precision != 0 and pe_lay is None
-                          and hip_path_supported(upsample_net, self.pixel_sizes, self.upsample_factors, self.patch, self.data_dim))
-
-        def seg1a():
-            weff_cache = None
-            if fused_head:
-                c1, c2, c3 = upsample_net.conv1, upsample_net.conv2, upsample_net.conv3
-                weff_cache = {("weff", bool(self.stage1_bf16)): ops.step_prepare(tab, step_t, dyn, kl_slots, split, A, c1.weight,
-                                                                                 c1.bias, c2.weight, c3.weight, self.stage1_bf16)}
-            else:
-                ops.step_begin(tab, step_t, dyn, kl_slots)
-            # ---- sample + the two forward maps.  With the fused next sample h_w was written by the previous step's posterior
-            # update (the step's LAST big kernel, see body()): its A transform goes first, while h_w is still in the Infinity Cache
-            # (measured: read cold, half a step later, the forward A transform takes 10 us longer)
-            def pe_forward():
-                # ---- sample ---------------------------------------------------------------------------------
-                lpe16 = None
-                if fuse_lpe:                 # written by the previous step's posterior update (or by prime() before the first)
-                    lpe, e_lpe, lpe16 = smp_lpe[0], smp_lpe[1], (smp_lpe[2][:, :lpe_lv.cols] if lpe16_want else None)
-                elif rng_lpe and lpe16_want:
-                    lpe, e_lpe, lpe16 = ops.reparam_rng(lpe_lv, rng_seed, 1, rng_ctr, want_bf16=True, group_offset=goff_lpe)   # bf16 copy: stage-1 operand
-                elif rng_lpe:
-                    lpe, e_lpe = ops.reparam_rng(lpe_lv, rng_seed, 1, rng_ctr, group_offset=goff_lpe)
-                else:
-                    e_lpe = self._noise((N, 1, self._d_lpe))
-                    lpe = ops.reparam_fwd([lpe_lv], [e_lpe], 1)
-                lpe_t = lpe.view(1, N, *self._lat, self.latent_dim).requires_grad_(True)
-                with torch.enable_grad():
-                    if pe_lay is not None:                                   # stitched grids, addressed in place by the kernel
-                        pe_c = self._pe(upsample_net, lpe_t, stitched=True)
-                    else:
-                        pe = self._pe(upsample_net, lpe_t, lpe16=lpe16, weff_cache=weff_cache)      # [N, 1, P, E]
-                        pe_c = pe.reshape(N, pe.shape[2], pe.shape[3]).contiguous()   # (not pe[:, 0]: select's backward
-                        #                                                               materialises zeros + a copy)
-                return lpe_t, e_lpe, pe_c
-
-            def net_forward():
-                h16 = None
-                if planes:                   # h_w as its (hi, lo) planes: from the previous step's update, or sampled here
-                    if not fuse_next:
-                        ops.reparam_rng(net[0], rng_seed, 0, rng_ctr, buffers=ws["smp_net"], group_offset=goff_net)
-                    h_w, eps = ws["smp_net"][2], [ws["smp_net"][1]]
-                elif fuse_next:
-                    h_w, e0, h16 = smp_net[0], smp_net[1], (smp_net[2][:, :D] if want16 else None)
-                    eps, h_w = [e0], h_w.view(N, D)
-                elif use_rng:
-                    if want16:
-                        h_w, e0, h16 = ops.reparam_rng(net[0], rng_seed, 0, rng_ctr, want_bf16=True, group_offset=goff_net)
-                    else:
-                        h_w, e0 = ops.reparam_rng(net[0], rng_seed, 0, rng_ctr, group_offset=goff_net)
-                    eps, h_w = [e0], h_w.view(N, D)
-                elif rng_hier:
-                    if "hier_eps" not in ws:
-                        ws["hier_eps"] = [torch.empty(N, 1, D, device=dev, dtype=torch.float32) for _ in net]
-                    eps = ws["hier_eps"]
-                    h_w = ops.reparam_hier_rng(net, eps, rng_seed, (0, 2, 3)[:len(net)], rng_ctr, goff_net).view(N, D)
-                else:
-                    eps = [self._noise((N, 1, D)) for _ in net]
-                    h_w = ops.reparam_fwd(net, eps, 1).view(N, D)
-                # ---- A transform (dense GEMMs) --------------------------------------------------------------
-                lowp = self.lowp_gemm and self.precision != 0
-                if lowp:
-                    # forward: f16 operands (11-bit mantissa; A pre-scaled by 2^10 so that the ~1e-4 products of
-                    # h_w @ A stay in f16's normal range) -- finer than the bf16 rounding the MLP kernel applies to
-                    # its weights anyway; backward GEMMs: bf16 operands (range-safe, gradients only)
-                    hf = h_w.to(torch.float16)
-                    wvec = torch.cat([torch.mm(hf[:, lo:hi], (a.detach() * 1024.0).to(torch.float16))
-                                      for (lo, hi), a in zip(slices, A)], 1).float() * (1.0 / 1024.0)
-                    h16 = h_w.to(torch.bfloat16)
-                    A16 = [a.detach().to(torch.bfloat16) for a in A]
-                elif split is not None:
-                    if training_mappings and not fused_head:
-                        split.prepare(A)                  # the mappings change every step when they are trained
-                    wvec = split.forward(h_w, split.new_rows(N))
-                else:
-                    wvec = torch.empty(N, D, device=dev, dtype=torch.float32)
-                    for (lo, hi), a in zip(slices, A):
-                        torch.mm(h_w[:, lo:hi], a.detach(), out=wvec[:, lo:hi])
-                return h_w, h16, eps, wvec, (A16 if lowp else None)
-
-            if fuse_next and fork is not None and (fork_mask & 1):
-                # experiment (RCB_FORK bit 1, same-box A/B only): the A transform of the sample on a second stream beside the
-                # upsampling net's forward -- the two are independent until the SIREN kernel
-                cur = torch.cuda.current_stream()
-                fork.wait_stream(cur)
-                with torch.cuda.stream(fork):
-                    h_w, h16, eps, wvec, A16 = net_forward()
-                lpe_t, e_lpe, pe_c = pe_forward()
-                cur.wait_stream(fork)
-            elif fuse_next:
-                h_w, h16, eps, wvec, A16 = net_forward()
-                lpe_t, e_lpe, pe_c = pe_forward()
-            else:
-                lpe_t, e_lpe, pe_c = pe_forward()
-                h_w, h16, eps, wvec, A16 = net_forward()
-            lowp = self.lowp_gemm and self.precision != 0
-            # ---- fused SIREN forward + MSE + backward ---------------------------------------------------
-            meta = self._meta(x, pe_c.shape[-1])
-            dw16 = None
-            if planes:        # the gradient leaves the kernel as its (hi, lo) planes: the A transform's operand form
-                sse, _, dpe, dw = ops.siren_loss_bwd(x, pe_c.detach(), wvec, y, 1.0 / (P * Cc), meta, want_planes=True,
-                                                    pe_layout=pe_lay, xf16=ws["xf16"])
-            elif want16:        # the kernel's epilogue also writes the bf16 copy of the gradient
-                sse, dw, dpe, dw16 = ops.siren_loss_bwd(x, pe_c.detach(), wvec, y, 1.0 / (P * Cc), meta, want_bf16=True,
-                                                        pe_layout=pe_lay, xf16=ws["xf16"])
-            else:
-                sse, dw, dpe = ops.siren_loss_bwd(x, pe_c.detach(), wvec, y, 1.0 / (P * Cc), meta, pe_layout=pe_lay,
-                                                  xf16=ws["xf16"])
-            # ---- backward through the A transform (first: its gradients are the bulk of the all-reduce bucket) -------
-            gA = []
-            fork_bwd = fork is not None and (fork_mask & 2) and split is not None and (flat is None or capture_coll) and fuse_next
-            early = bool(fork_bwd and (fork_mask & 32) and (fork_mask & 8) and flat is None and training_mappings and want16 and not planes
-                         and self.wgrad_bf16 and side is not None and h16 is not None and dw16 is not None)
-            split_w = bool(fork_bwd and (fork_mask & 64) and not (fork_mask & 32) and (fork_mask & 8) and flat is None and training_mappings
-                           and want16 and not planes and self.wgrad_bf16 and side is not None and h16 is not None and dw16 is not None)
-            if split_w:
-                # bit 64: the wide layers' weight-gradient GEMM on the third stream right behind the SIREN kernel; the forked
-                # stream runs the narrow layers' kernels and the data gradient, then WAITS for that GEMM (it reads the bf16 sample
-                # the update overwrites) before the network level's posterior update: the update starts as soon as both are done
-                # instead of behind the GEMM on its own stream
-                cur = torch.cuda.current_stream()
-                side.wait_stream(cur)
-                fork.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    g_wide = split.wgrad(h_w, dw, h16, dw16, True, part="wide")
-                    st["ev_wide"] = torch.cuda.Event()
-                    st["ev_wide"].record(side)
-                with torch.cuda.stream(fork):
-                    g_rest = split.wgrad(h_w, dw, h16, dw16, True, part="rest")
-                    dh = split.dgrad(dw, torch.empty(N, D, device=dev, dtype=torch.float32))
-                gA = [a_ if a_ is not None else b_ for a_, b_ in zip(g_wide, g_rest)]
-                st["fork_pending"] = st["side_pending"] = True
-                st["fork_keep"] = (dw, dw16, h_w, h16)
-            elif early:
-                # bit 32: the network level's posterior update as EARLY as possible -- right behind the data gradient -- so that
-                # this HBM-bound kernel runs beside the LDS / MFMA-bound upsampling backward instead of beside the step's last
-                # small GEMMs (measured: two 30 us GEMMs took 170 us each next to it).  What kept it late was a hazard: it
-                # writes the next step's sample over the buffers the weight gradient still reads.  The wide layers' GEMM
-                # (bf16 copies only) goes to the third stream and the update writes the next bf16 copy into a SECOND buffer,
-                # copied over at the end of the step (27 MB); the narrow layers' kernels (fp32 rows) run in front of the update.
-                cur = torch.cuda.current_stream()
-                side.wait_stream(cur)
-                fork.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    g_wide = split.wgrad(h_w, dw, h16, dw16, True, part="wide")
-                with torch.cuda.stream(fork):
-                    g_rest = split.wgrad(h_w, dw, h16, dw16, True, part="rest")
-                    dh = split.dgrad(dw, torch.empty(N, D, device=dev, dtype=torch.float32))
-                gA = [a_ if a_ is not None else b_ for a_, b_ in zip(g_wide, g_rest)]
-                st["fork_pending"] = st["early"] = True
-                st["fork_keep"] = (dw, dw16, h_w, h16)
-            elif fork_bwd:      # the A transform's backward on the second stream beside the upsampling net's backward
-                fork.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(fork):
-                    dh = split.dgrad(dw, torch.empty(N, D, device=dev, dtype=torch.float32))
-                    if training_mappings:
-                        gA = split.wgrad(h_w, dw, h16, dw16, self.wgrad_bf16)
-                        if capture_coll:                # bucket 0 (13.4 of the 14.4 MB) leaves from this stream, inside the graph
-                            gA = flat.pack(0, gA)
-                            st["h0"] = flat.reduce(0, async_op=True)
-                    if fork_mask & 16:                  # the mapping gradients are complete here (Adam may start on another stream)
-                        st["ev_gA"] = torch.cuda.Event()
-                        st["ev_gA"].record(fork)
-                st["fork_pending"] = True
-                # dw (and its bf16 copy) were allocated on the main stream and are READ on the forked one: they must stay
-                # allocated until the streams have joined, or the caching allocator hands their memory to the next main-stream
-                # allocation (the upsampling net's backward) while the A transform is still reading it
-                st["fork_keep"] = (dw, dw16, h_w, h16)
-            elif lowp:
-                dw16 = dw.to(torch.bfloat16)
-                dh = torch.cat([torch.mm(dw16[:, lo:hi], a16.t()) for (lo, hi), a16 in zip(slices, A16)], 1).float()
-                if training_mappings:
-                    gA = [torch.mm(h16[:, lo:hi].t(), dw16[:, lo:hi]).float() for (lo, hi) in slices]
-            elif split is not None:
-                dh = split.dgrad(dw, torch.empty(N, D, device=dev, dtype=torch.float32))
-                if training_mappings:
-                    gA = split.wgrad(h_w, dw, h16, dw16, self.wgrad_bf16)
-            else:
-                dh = torch.empty(N, D, device=dev, dtype=torch.float32)
-                for (lo, hi), a in zip(slices, A):
-                    torch.mm(dw[:, lo:hi], a.detach().t(), out=dh[:, lo:hi])
-                    if training_mappings:
-                        gA.append(torch.mm(h_w[:, lo:hi].t(), dw[:, lo:hi]))
-            st.update(sse=sse, dh3=dh.view(N, 1, D), eps=eps, e_lpe=e_lpe, pe_c=pe_c, lpe_t=lpe_t, dpe=dpe)
-            if training_mappings:
-                if flat is not None and "h0" not in st:
-                    gA = flat.pack(0, gA)
-                    if capture_coll:
-                        st["h0"] = flat.reduce(0, async_op=True)
-                st["gA"] = gA
-
-        def seg1b():
-            # ---- backward through the upsampling net -----------------------------------------------------------
-            inputs = [st["lpe_t"]] + (conv if training_mappings else [])
-            g_in = torch.autograd.grad(st["pe_c"], inputs, st["dpe"])
-            st["d_lpe"] = g_in[0].reshape(N, 1, self._d_lpe).contiguous()
-            if training_mappings:
-                gc = [g.contiguous() for g in g_in[1:]]
-                if flat is not None:
-                    gc = flat.pack(1, gc)
-                    if capture_coll:
-                        st["h1"] = flat.reduce(1, async_op=True)
-                st["grads"] = st["gA"] + gc
-            # the autograd graph of this step must not outlive it: a graph kept alive from an eager warm-up step (default
-            # stream) into the capture (side stream) makes its AccumulateGrad nodes cross streams and breaks the capture
-            for k_ in ("pe_c", "lpe_t", "dpe"):
-                st.pop(k_, None)
-
-        def comm(part):
-            """sum of the mapping gradients over the ranks (the only per-step collectives): part 0 = the A matrices (13.4 of
-            the 14.4 MB, ready before the upsampling backward starts), part 1 = the conv weights; returns the async handle"""
-            if flat is None:
-                return None
-            return flat.reduce(part, async_op=True)
-
-        def seg2_net():
-            # fused posterior update (also accumulates the pre-update KL for the ELBO log)
-            nxt_net = None
-            if fuse_next:            # the next step sees the noise counter + 1 (rcb_step_end increments it after this segment)
-                o16_ = smp_net[2] if (want16 or planes) else None
-                if st.get("early"):                  # (bit 32: the next bf16 copy goes to the second buffer, see seg1a)
-                    o16_ = ws["h16_next"]
-                nxt_net = ops.NextSample((smp_net[0], smp_net[1], o16_), rng_seed, 0, rng_ctr, 1,
-                                         redraw_eps=redraw, group_offset=goff_net)
-            for lv, (pl, ps), e, stt in zip(net, net_priors, st["eps"], net_state):
-                ops.posterior_bwd(lv, pl, ps, False, 1.0, st["dh3"], e, 1, adam=cfg, state=stt, kl_accum=kl_slots,
-                                  kl_scalar_dev=beta_dev, next_sample=nxt_net)
-
-        def lpe_update():
-            """arguments of the lpe level's posterior update (ops.posterior_bwd, without adam=)"""
-            nxt_lpe = None
-            if fuse_lpe:
-                nxt_lpe = ops.NextSample((smp_lpe[0], smp_lpe[1], smp_lpe[2] if lpe16_want else None), rng_seed, 1, rng_ctr, 1,
-                                         redraw_eps=redraw_lpe, group_offset=goff_lpe)
-            return ((lpe_lv, pri_d[2].reshape(-1), pri_d[3].reshape(-1), False, 1.0, st["d_lpe"], st["e_lpe"], 1),
-                    dict(state=lpe_state, kl_accum=kl_slots, kl_scalar_dev=beta_dev, next_sample=nxt_lpe))
-
-        def seg2_lpe():
-            args, kwargs = lpe_update()
-            ops.posterior_bwd(*args, adam=cfg, **kwargs)
-
-        def seg_tail():
-            """seg2_lpe + seg3_adam + seg3_end in one launch; False (nothing launched) if the level does not qualify"""
-            args, kwargs = lpe_update()
-            return ops.step_tail(args, kwargs, [p.data for p in A + conv], [g.contiguous() for g in st["grads"]],
-                                 [m for m, _ in map_state], [v for _, v in map_state], cfg, ws["tickets"], step_t, st["sse"],
-                                 1.0 / (P * Cc), mse_buf, kl_buf, aux_counter=rng_ctr)
-
-        def seg2():
-            seg2_net()
-            seg2_lpe()
-
-        def seg3_adam():
-            for k_ in ("h0", "h1"):             # captured collectives: the stream that runs Adam waits for both buckets
-                h_ = st.pop(k_, None)
-                if h_ is not None:
-                    h_.wait()
-            if training_mappings:
-                ops.adam_multi([p.data for p in A + conv], [g.contiguous() for g in st["grads"]],
-                               [m for m, _ in map_state], [v for _, v in map_state], cfg)
-
-        def seg3_end():
-            ops.step_end(step_t, st["sse"], 1.0 / (P * Cc), kl_slots, mse_buf, kl_buf, aux_counter=rng_ctr)
-
-        def seg3():
-            seg3_adam()
-            seg3_end()
-
-        def body():
-            if (fuse_next and flat is None) or capture_coll:
-                # one rank (or collectives inside the graph): the network level's update -- which writes the next step's h_w -- is the step's last big kernel, so
-                # that the next step's A transform (its first) finds h_w in the Infinity Cache
-                seg1a()
-                pending = st.pop("fork_pending", False)
-                if pending and (fork_mask & 8):
-                    with torch.cuda.stream(fork):      # the network level's update needs dh only: straight behind the A backward
-                        ev_w = st.pop("ev_wide", None)
-                        if ev_w is not None:
-                            fork.wait_event(ev_w)
-                        seg2_net()
-                seg1b()
-                if st.pop("side_pending", False):
-                    torch.cuda.current_stream().wait_stream(side)
-                if st.pop("early", False):
-                    # join both streams, then the next step's bf16 copy moves into the buffer the step reads (see seg1a)
-                    torch.cuda.current_stream().wait_stream(fork)
-                    torch.cuda.current_stream().wait_stream(side)
-                    smp_net[2].copy_(ws["h16_next"])
-                ev = st.pop("ev_gA", None)
-                if pending and ev is not None and side is not None:
-                    # bit 16: Adam on the mappings on the third stream (it needs the A gradients -- the event -- and the
-                    # upsampling net's weight gradients, which that stream produced itself) beside the lpe level's update
-                    side.wait_stream(torch.cuda.current_stream())
-                    side.wait_event(ev)
-                    with torch.cuda.stream(side):
-                        seg3_adam()
-                    seg2_lpe()
-                    torch.cuda.current_stream().wait_stream(fork)
-                    torch.cuda.current_stream().wait_stream(side)
-                    st.pop("fork_keep", None)
-                else:
-                    if pending:
-                        torch.cuda.current_stream().wait_stream(fork)
-                        st.pop("fork_keep", None)
-                    if fused_step and pending and (fork_mask & 8) and seg_tail():
-                        return                           # (the whole tail was that one launch)
-                    seg2_lpe()
-                    seg3_adam()
-                if not (pending and (fork_mask & 8)):
-                    seg2_net()
-                seg3_end()
-                return
-            seg1a()
-            w0 = comm(0)
-            seg1b()
-            w1 = comm(1)
-            seg2()
-            for w_ in (w0, w1):
-                if w_ is not None:
-                    w_.wait()
-            seg3()
-
-        n_warm = 3
-
-        def replay(k):
-            kind, gr = ws["graphs"]
-            for _ in range(k):
-                if kind == "one":
-                    gr.replay()
-                else:
-                    gr[0].replay()
-                    w0 = comm(0)
-                    gr[1].replay()
-                    w1 = comm(1)
-                    gr[2].replay()
-                    w0.wait()
-                    w1.wait()
-                    gr[3].replay()
-
-        if fuse_lpe:
-            prime()
-        if graphable and (ws["graphs"] is not None or n_epoch > n_warm):
+        # the step itself -- what it launches (StepPlan), the workspace `self._ws` with its captured graphs, the segments -- lives
+        # in train_step.py; a workspace whose key still holds is found again here, else a new one is built
+        step = train_step.PriorTrainStep(self, n_epoch, lr, x, y, priors, linear_transform, upsample_net, training_mappings,
+                                         verbose)
+        ws = step.ws
+        step.prime(kl_beta, priors)
+        if step.plan.graphable and (ws["graphs"] is not None or n_epoch > train_step.N_WARM):
             left = n_epoch
             failure = None
             if ws["graphs"] is None:               # first call with this workspace: warm up eagerly, then capture
-                for _ in range(n_warm):
-                    body()
-                left -= n_warm
-                torch.cuda.synchronize()
-                try:
-                    if flat is None or capture_coll:   # one rank / frozen mappings / captured collectives: the whole step is one graph
-                        graph = torch.cuda.CUDAGraph()
-                        # (thread_local: the process group's watchdog thread must not be able to invalidate the capture)
-                        with torch.cuda.graph(graph, capture_error_mode="thread_local" if flat is not None else "global"):
-                            body()                         # records the step; nothing executes during capture
-                        ws["graphs"] = ("one", graph)
-                    else:                               # sharded: four graphs around the two eager, asynchronous all-reduces
-                        pool = torch.cuda.graph_pool_handle()
-                        graphs = []
-                        for seg in (seg1a, seg1b, seg2, seg3):
-                            g = torch.cuda.CUDAGraph()
-                            # thread_local: the process group's own threads (RCCL watchdog: event queries) must not be able
-                            # to invalidate a capture in progress on this thread
-                            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                                seg()
-                            graphs.append(g)
-                        ws["graphs"] = ("segments", graphs)
-                except Exception as exc:     # capture is an optimisation: fall back to eager stepping
-                    failure = exc
-                    torch.cuda.synchronize()
-                    # a body that aborted in mid-capture leaves its per-step state behind (pending fork / side-stream
-                    # flags, the Work handles of collectives that were only RECORDED): an eager step that found them would
-                    # skip its own all-reduce and wait on a handle of the dead capture
-                    st.clear()
-                if flat is not None:
-                    # every rank must take the same route from here on: replayed segments and eager steps issue the same
-                    # collectives, but a rank that alone drops to eager would also alone flip `use_graph` for later calls.
-                    # No collective has EXECUTED during the capture attempt -- in the four-segment form they sit between the
-                    # segments, in the captured form they were recorded into a graph that is dropped -- so the ranks are
-                    # still aligned and can agree here.
-                    ok = torch.tensor([0 if failure is not None else 1], device=dev, dtype=torch.int32)
-                    torch.distributed.all_reduce(ok, op=torch.distributed.ReduceOp.MIN, group=self.dp_group)
-                    if int(ok.item()) == 0 and failure is None:
-                        failure = RuntimeError("capture failed on another rank")
+                for _ in range(train_step.N_WARM):
+                    step.body()
+                left -= train_step.N_WARM
+                failure = step.capture()
             if failure is None:
-                replay(left)
+                step.replay(left)
             else:
                 import warnings
                 warnings.warn(f"HIP graph capture of the training step failed ({failure}); running eagerly")
@@ -863,16 +311,15 @@ class PriorBNNmodel(nn.Module):
                 self._ws = None
                 self.use_graph = False
                 for _ in range(left):
-                    body()
+                    step.body()
         else:
             it = range(n_epoch)
             if verbose:
                 from tqdm import tqdm
                 it = tqdm(it)
             for _ in it:
-                body()
-        _uf.WEIGHT_SIDE_STREAM = None       # (a module-level switch: never left set behind this call)
-        mse_buf, kl_buf = mse_buf[:n_epoch], kl_buf[:n_epoch]
+                step.body()
+        mse_buf, kl_buf = ws["mse_buf"][:n_epoch], ws["kl_buf"][:n_epoch]
         kl_final = self._kl_value(priors)
         # one transfer (one synchronisation) for everything the call returns: [elbo per step ..., last MSE, final KL]
         out_h = torch.cat([-(mse_buf + kl_buf * float(kl_beta)), mse_buf[-1:], kl_final.reshape(1)]).cpu()

@@ -507,12 +507,7 @@ class TestBNNmodel(nn.Module):
             # the Adam moments of all levels as views of one buffer: a fine-tune call (a few steps each, thousands of them
             # per compression run) resets them with one launch
             shapes = [lv.loc.shape for lv in self._levels for _ in range(4)]
-            offs, tot = [], 0
-            for shp in shapes:
-                offs.append(tot)
-                tot += (int(np.prod(shp)) + 63) // 64 * 64
-            state_flat = torch.zeros(tot, device=dev, dtype=torch.float32)
-            views = iter([state_flat[o:o + int(np.prod(shp))].view(shp) for o, shp in zip(offs, shapes)])
+            state_flat, views = ops.zeroed_views(shapes, dev)
             ws = dict(key=key, tab=ops.adam_table(lr, max(n_epochs, 2048)).to(dev), state_flat=state_flat,
                       dyn=torch.zeros(2, device=dev), step_t=torch.zeros(1, device=dev, dtype=torch.long),
                       states=[{k: next(views) for k in ("m_loc", "v_loc", "m_ls", "v_ls")} for lv in self._levels],

@@ -438,17 +438,15 @@ def hip_path_supported(net, pixel_sizes, upsample_factors, patch, data_dim):
     return ok
 
 
-WEIGHT_SIDE_STREAM = None        # see _UpsampleCifarFn.backward
-
-
 class _UpsampleCifarFn(torch.autograd.Function):
     """lpe [B, 512] (channel-last 2x2x128) -> pe [B, 1024, 16].  Stage 1 is one dense GEMM against the
     pre-summed 512 x 4096 weight (hipBLASLt); stages 2 and 3 are the rcb_upconv_* kernels."""
 
     @staticmethod
-    def forward(ctx, lpe, W1, b1, W2, b2, W3, b3, stage1_bf16, pe_bf16, cache=None, lpe16=None):
+    def forward(ctx, lpe, W1, b1, W2, b2, W3, b3, stage1_bf16, pe_bf16, cache=None, lpe16=None, weight_side_stream=None):
         from . import ops
         B = lpe.shape[0]
+        ctx.weight_side_stream = weight_side_stream          # see backward
         # effective (phase-form) weights of all three stages in one launch; bf16 stage 1 = bf16 operands and a bf16 z1
         # (stage 2 rounds z1 to bf16 for its MFMA operand anyway).  `cache`: a dict owned by a caller whose mappings are
         # frozen for its lifetime (TestBNNmodel): built once instead of every step
@@ -480,14 +478,12 @@ class _UpsampleCifarFn(torch.autograd.Function):
             dz2, dWeff3, db3 = ops.upconv_bwd_fused(dpe, Weff3, h2, 16, 16, pack=pack)
         else:
             dz2 = ops.upconv_dgrad(dpe, Weff3, h2, 16, 16, pack=pack)      # bf16 [B,16,16,64]
-        # WEIGHT_SIDE_STREAM (set by PriorBNNmodel.train when its stream fork is on): the weight-gradient side of the backward
+        # weight_side_stream (given by the training step when its stream fork is on): the weight-gradient side of the backward
         # (stage-2 weight gradient, stage-1 weight-gradient GEMM, the map back onto the conv weights) runs on a second stream
         # beside the data path (stage-2 data gradient -> stage-1 data-gradient GEMM): the two only share their inputs, and
         # the library GEMMs (160 macro-tiles) leave a third of the chip idle on their own.  Same kernels, same operands:
         # identical results.
-        side = WEIGHT_SIDE_STREAM if (need_w and fused3) else None
-        if side is not None and side.device != dz2.device:      # (a stream left behind by a model on another device)
-            side = None
+        side = ctx.weight_side_stream if (need_w and fused3) else None
         main = torch.cuda.current_stream() if side is not None else None
         if side is not None:
             side.wait_stream(main)                       # dz2 is complete
@@ -505,9 +501,9 @@ class _UpsampleCifarFn(torch.autograd.Function):
             dlpe = torch.mm(dz1f, Weff1.t(), out_dtype=torch.float32) if dz1f.dtype == torch.bfloat16 else dz1f @ Weff1.t()
         if side is not None:
             main.wait_stream(side)
-            return dlpe, dW1, db1, dW2, db2, dW3, db3, None, None, None, None
+            return dlpe, dW1, db1, dW2, db2, dW3, db3, None, None, None, None, None
         if not need_w:
-            return dlpe, None, None, None, None, None, None, None, None, None, None
+            return dlpe, None, None, None, None, None, None, None, None, None, None, None
         if not fused3:
             dWeff3, db3 = ops.upconv_wgrad(h2, dpe, 16, 16)
         dWeff2, db2 = ops.upconv_wgrad(z1, dz2, 8, 64, preact=True)
@@ -515,19 +511,20 @@ class _UpsampleCifarFn(torch.autograd.Function):
         # rcb_upconv_weff_grad is the faster one: 7.7 vs 11.1 us)
         dWeff1 = (torch.mm(lpe.t(), dz1f, out_dtype=torch.float32) if dz1f.dtype == torch.bfloat16 else lpe.t() @ dz1f)
         dW1, dW2, dW3, db1 = ops.upconv_weff_grad(dWeff1, dWeff2, dWeff3, db1_part)
-        return dlpe, dW1, db1, dW2, db2, dW3, db3, None, None, None, None
+        return dlpe, dW1, db1, dW2, db2, dW3, db3, None, None, None, None, None
 
 
-def upsample_cifar_hip(net, lpe, stage1_bf16=True, pe_bf16=True, frozen_cache=None, lpe16=None):
+def upsample_cifar_hip(net, lpe, stage1_bf16=True, pe_bf16=True, frozen_cache=None, lpe16=None, weight_side_stream=None):
     """lpe [S, N, 2, 2, 128] -> pe [N, S, 1024, 16] (contiguous) through the HIP phase-conv kernels.
     `stage1_bf16` runs the stage-1 library GEMMs (fwd, dgrad, wgrad) with bf16 operands / fp32 accumulation and keeps
     z1 in bf16.  `pe_bf16` stores pe (and hence its gradient) as bf16: the 16-bit SIREN kernels and the stage-3
     gradient kernels round both to bf16 for their MFMA operands anyway, so the results are bit-identical to fp32
-    storage at half the traffic.  The (small) lpe is reordered to INR-major so that pe needs no transpose."""
+    storage at half the traffic.  The (small) lpe is reordered to INR-major so that pe needs no transpose.
+    `weight_side_stream`: a second stream for the weight-gradient side of the backward (_UpsampleCifarFn.backward)."""
     S, N = lpe.shape[:2]
     pe = _UpsampleCifarFn.apply(lpe.permute(1, 0, 2, 3, 4).reshape(N * S, 512), net.conv1.weight, net.conv1.bias,
                                 net.conv2.weight, net.conv2.bias, net.conv3.weight, net.conv3.bias, bool(stage1_bf16),
-                                bool(pe_bf16), frozen_cache, lpe16 if S == 1 else None)
+                                bool(pe_bf16), frozen_cache, lpe16 if S == 1 else None, weight_side_stream)
     return pe.view(N, S, 1024, 16)
 
 

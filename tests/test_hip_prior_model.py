@@ -248,6 +248,33 @@ def test_every_preset_captures_and_replays_in_the_throughput_mode(name, n_data):
     assert np.mean(e2) > np.mean(e1)                          # ELBO = -(loss): the second call continues to improve
 
 
+def test_removed_stream_fork_bits_are_refused_and_a_remaining_one_replays():
+    """`stream_forks` takes combinations of the bits 2, 4 and 8 only: a removed ordering (32) is a ValueError before anything
+    is built or captured, and a single remaining bit (2) trains as a replayed graph."""
+    from recombiner_amd import config, utils
+    cfg, n = config.configs["cifar"], 8
+    X, Y = utils.synthetic_inputs(cfg["pixel_sizes"], cfg["fourier_dim"], n, cfg["output_dim"], seed=0)
+    m = PM.PriorBNNmodel(cfg["input_dim"], cfg["hidden_dims"], cfg["output_dim"], n, cfg["data_dim"], cfg["pixel_sizes"],
+                         cfg["upsample_factors"], cfg["latent_dim"], cfg["patch"], cfg["patch_nums"],
+                         cfg["hierarchical_patch_nums"], random_seed=42, device=DEV)
+    m.precision = 1
+    torch.manual_seed(1)
+    lt = PM.LinearTransform(m.dims).to(DEV)
+    up = PM.Upsample(cfg["data_dim"], cfg["paddings"], cfg["layerwise_scale_factors"]).to(DEV)
+    D, s0, lat = m._d_net, 0.0211547, list(m.lpe_loc.shape[1:])
+    pri = [torch.zeros(D, device=DEV), torch.full((D,), s0, device=DEV), torch.zeros(lat, device=DEV), torch.full(lat, s0, device=DEV)]
+    pri += [None] * 4
+    Xd, Yd = X.to(DEV)[None].expand(n, -1, -1), Y.to(DEV)
+    m.stream_forks = 32
+    with pytest.raises(ValueError, match="2.*4.*8.*DESIGN.md"):
+        m.train(12, 1e-3, Xd, Yd, *pri, lt, up, 1e-8, training_mappings=True)
+    assert m._ws is None
+    m.stream_forks = 2
+    _, _, elbo = m.train(12, 1e-3, Xd, Yd, *pri, lt, up, 1e-8, training_mappings=True)
+    assert m._ws is not None and m._ws["graphs"] is not None and m._ws["graphs"][0] == "one"
+    assert len(elbo) == 12 and np.isfinite(elbo).all()
+
+
 @pytest.mark.parametrize("name,width,prec", [("patch2d", 48, 1), ("patch3d", 64, 2), ("patch1d", 64, 1), ("cifar", 64, 1),
                                              ("cifar", 48, 2)])
 def test_wide_siren_variants_train_like_the_oracle(name, width, prec):
