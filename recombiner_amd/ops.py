@@ -1391,6 +1391,14 @@ def upconv_weff_grad(dweff1, dweff2, dweff3, db1_partial=None):
     return (dW1, dW2, dW3) if db1_partial is None else (dW1, dW2, dW3, db1)
 
 
+def a_transform_mm(src, A, slices, out, transpose=False):
+    """the A transform of the fp32 mode, one library GEMM per layer into the columns of `out`:
+    out[:, lo:hi] = src[:, lo:hi] @ A[l] (forward), or @ A[l]^T (`transpose`: the data gradient)"""
+    for (lo, hi), a in zip(slices, A):
+        torch.mm(src[:, lo:hi], a.detach().t() if transpose else a.detach(), out=out[:, lo:hi])
+    return out
+
+
 class ATransform:
     """The A transform `wvec[:, lo:hi] = h_w[:, lo:hi] @ A[l]` (prior_model.py:173-174, test_model.py:348-349), its data
     gradient `dh[:, lo:hi] = dw[:, lo:hi] @ A[l]^T` and its weight gradient on the hand-written kernels of atrans.hip:

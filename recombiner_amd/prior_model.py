@@ -67,7 +67,50 @@ class Upsample(nn.Module):
         return {k: v for k, v in self.__dict__.items() if not k.startswith("_rcb_")}
 
 
-class PriorBNNmodel(nn.Module):
+class InrGeometry:
+    # what PriorBNNmodel and TestBNNmodel share: the geometry of one INR (a mixin: the models set the members read here)
+
+    def _pe_layout(self):
+        # the patched presets in the 16-bit modes hand the SIREN kernel the upsampling net's output on the stitched grids
+        # as it is (ops.PeLayout); None: pe is cut back into [N, S, P, 16]
+        if self.precision != 0 and self.patch and self.stitched_pe:
+            return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
+        return None
+
+    def _pe(self, upsample_net, lpe, stitched=False, lpe16=None, weff_cache=None, weight_side_stream=None):
+        """lpe [S, N, *lat, C] -> pe [N, S, P, 16]: hand-written phase-conv kernels in the 16-bit modes
+        where the geometry is instantiated, the nn.Module (MIOpen) otherwise.  `stitched`: see _pe_layout.
+        lpe16: the producer's bf16 copy of lpe [N, Dlpe] (stage-1 operand; saves the cast pass).
+        weff_cache: the phase-form weights in _UpsampleCifarFn's cache form: of THIS step (ops.step_prepare), or of frozen mappings.
+        weight_side_stream: second stream for the weight-gradient side of the hand-written kernels' backward."""
+        if self.precision != 0 and hip_path_supported(upsample_net, self.pixel_sizes, self.upsample_factors, self.patch, self.data_dim):
+            return upsample_cifar_hip(upsample_net, lpe, self.stage1_bf16, self.pe_bf16, frozen_cache=weff_cache, lpe16=lpe16,
+                                      weight_side_stream=weight_side_stream)
+        net = upsample_net
+        if self.precision != 0 and tiled_2d_preferred(upsample_net, self.patch, self.data_dim):
+            net = stitched2d_module(upsample_net)                  # stitched 2-D grid: phase-conv kernels on overlapping tiles
+        elif self.precision != 0 and phase_form_preferred(self.data_dim, self.patch):
+            net = phase_module(upsample_net) or upsample_net       # torch-level phase form: same function, fewer flops
+        return map_lpe_to_inr_inputs(net, lpe, self.latent_dim, self.pixel_sizes, self.upsample_factors,
+                                     self.patch, self.patch_nums, self.data_dim, stitched=stitched)
+
+    def _meta(self, x, pe_dim, samples=1):
+        return SirenMeta(samples=samples, n_pix=x.shape[-2], fourier_dim=x.shape[-1], pe_dim=pe_dim,
+                         n_hidden=self.n_layers - 1, hidden=max(self.dims[1:-1]), out_dim=self.dims[-1], w0=self.w0,
+                         precision=self.precision,
+                         hidden_dims=tuple(self.dims[1:-1]) if len(set(self.dims[1:-1])) > 1 else None)
+
+    def _layer_slices(self):
+        cum = self.cum_param_sizes
+        return [(0 if i == 0 else int(cum[i - 1]), int(cum[i])) for i in range(self.n_layers)]
+
+    def group_to_layer(self, param, layer_idx):
+        # reference API: the slice of a layer-vector row (.. x D_net) that belongs to layer `layer_idx`
+        lo, hi = self._layer_slices()[layer_idx]
+        return param[..., lo:hi]
+
+
+class PriorBNNmodel(nn.Module, InrGeometry):
     """Training-set posteriors + batched INR evaluation (prior_model.py:62-262)."""
 
     def __init__(self, in_dim, hidden_dims, out_dim, train_size, data_dim, pixel_sizes, upsample_factors,
@@ -178,52 +221,13 @@ class PriorBNNmodel(nn.Module):
                         self._d_lpe, self.train_size)
         return c["net"], lpe
 
-    def _pe_layout(self):
-        """the patched presets in the 16-bit modes hand the SIREN kernel the upsampling net's output on the stitched grids
-        as it is (ops.PeLayout); None: pe is cut back into [N, S, P, 16]"""
-        if self.precision != 0 and self.patch and self.stitched_pe:
-            return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
-        return None
-
-    def _pe(self, upsample_net, lpe, stitched=False, lpe16=None, weff_cache=None, weight_side_stream=None):
-        """lpe [S, N, *lat, C] -> pe [N, S, P, 16]: hand-written phase-conv kernels in the 16-bit modes
-        where the geometry is instantiated, the nn.Module (MIOpen) otherwise.  `stitched`: see _pe_layout.
-        lpe16: the producer's bf16 copy of lpe [N, Dlpe] (stage-1 operand; saves the cast pass).
-        weff_cache: the phase-form weights of THIS step, already built (ops.step_prepare), in _UpsampleCifarFn's cache form.
-        weight_side_stream: second stream for the weight-gradient side of the hand-written kernels' backward."""
-        if self.precision != 0 and hip_path_supported(upsample_net, self.pixel_sizes, self.upsample_factors, self.patch,
-                                                      self.data_dim):
-            return upsample_cifar_hip(upsample_net, lpe, self.stage1_bf16, self.pe_bf16, frozen_cache=weff_cache, lpe16=lpe16,
-                                      weight_side_stream=weight_side_stream)
-        net = upsample_net
-        if self.precision != 0 and tiled_2d_preferred(upsample_net, self.patch, self.data_dim):
-            net = stitched2d_module(upsample_net)                  # stitched 2-D grid: phase-conv kernels on overlapping tiles
-        elif self.precision != 0 and phase_form_preferred(self.data_dim, self.patch):
-            net = phase_module(upsample_net) or upsample_net       # torch-level phase form: same function, fewer flops
-        return map_lpe_to_inr_inputs(net, lpe, self.latent_dim, self.pixel_sizes, self.upsample_factors,
-                                     self.patch, self.patch_nums, self.data_dim, stitched=stitched)
-
     def _noise(self, shape):
         if self.noise_source is not None:
             e = self.noise_source(tuple(shape))
             return e.to(self.loc.device, torch.float32).reshape(shape).contiguous()
         return torch.randn(shape, device=self.loc.device, dtype=torch.float32)
 
-    def _meta(self, x, pe_dim, samples=1):
-        return SirenMeta(samples=samples, n_pix=x.shape[-2], fourier_dim=x.shape[-1], pe_dim=pe_dim,
-                         n_hidden=self.n_layers - 1, hidden=max(self.dims[1:-1]), out_dim=self.dims[-1], w0=self.w0,
-                         precision=self.precision,
-                         hidden_dims=tuple(self.dims[1:-1]) if len(set(self.dims[1:-1])) > 1 else None)
-
-    def _layer_slices(self):
-        cum = self.cum_param_sizes
-        return [(0 if i == 0 else int(cum[i - 1]), int(cum[i])) for i in range(self.n_layers)]
-
     # ---- reference API: helpers ----------------------------------------------------------------------
-    def group_to_layer(self, params, layer_idx):
-        lo, hi = self._layer_slices()[layer_idx]
-        return params[..., lo:hi]
-
     def layer_to_weight(self, in_dim, out_dim, layer_param):
         bias = layer_param[:, :out_dim]
         weights = layer_param[:, out_dim:].reshape(-1, in_dim, out_dim)

@@ -19,10 +19,10 @@ from torch import nn
 from torch.optim import Adam
 
 from . import ops
-from .ops import LevelSpec, SirenMeta
-from .upsample_fast import (hip_path_supported, tiled_2d_preferred, phase_form_preferred, phase_module,
-                            stitched2d_module, upsample_cifar_hip)
-from .utils import count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs, metric
+from . import test_step
+from .prior_model import InrGeometry
+from .ops import LevelSpec
+from .utils import count_net_params, hierarchy_row_maps, metric
 from .utils import map_hierarchical_model_to_int_weights  # noqa: F401  (module-level name, as upstream imports it)
 
 LN2 = np.log(2.)
@@ -98,7 +98,7 @@ class _Lvl:
                          enc_sample=self.sample, enc_mask=self.mask)
 
 
-class TestBNNmodel(nn.Module):
+class TestBNNmodel(nn.Module, InrGeometry):
     """RECOMBINER model for compression (test_model.py:33-856)."""
     __test__ = False
 
@@ -180,11 +180,14 @@ class TestBNNmodel(nn.Module):
         self.precision = 0
         self.stage1_bf16 = True      # 16-bit mode only: bf16-operand GEMMs for stage 1 of the upsampling net
         self.pe_bf16 = True          # 16-bit mode only: pe / dpe stored as bf16 (bit-identical, half the traffic)
+        self.stitched_pe = True      # as PriorBNNmodel.stitched_pe
         self.split_gemm = True       # 16-bit mode only: split-bf16 (hi/lo) operands for the A-transform fwd / dgrad GEMMs
         self.split_terms = 2         # as PriorBNNmodel.split_terms
         self.use_graph = True        # replay the fused training step as captured HIP graphs when possible
         self._specs = None
-        self._ws = None
+        self._ws = None              # persistent training workspace (test_step.py: the two captured graphs + what they reference)
+        self._weff_cache = {}        # phase-form conv weights: the mappings are frozen for this model's lifetime (test_model.py:117-126)
+        self._g_absmax = None        # max |g_samples| (the fast scorer's error bound uses it), set with g_samples
 
     # ---- reference-named views of the per-level state ------------------------------------------------------
     kl_beta = property(lambda s: s._l1.kl_beta)
@@ -236,22 +239,7 @@ class TestBNNmodel(nn.Module):
             eps.append(self._draw("l3", (N, S, D)).contiguous())
         return eps
 
-    def _meta(self, x, S):
-        return SirenMeta(samples=S, n_pix=x.shape[-2], fourier_dim=x.shape[-1], pe_dim=16,
-                         n_hidden=self.n_layers - 1, hidden=max(self.dims[1:-1]), out_dim=self.dims[-1], w0=self.w0,
-                         precision=self.precision,
-                         hidden_dims=tuple(self.dims[1:-1]) if len(set(self.dims[1:-1])) > 1 else None)
-
-    def _layer_slices(self):
-        cum = self.cum_param_sizes
-        return [(0 if i == 0 else int(cum[i - 1]), int(cum[i])) for i in range(self.n_layers)]
-
     # ---- reference API: helpers (test_model.py:260-281) ------------------------------------------------------------
-    def group_to_layer(self, param, layer_idx):
-        """the slice of a layer-vector row (.. x D_net) that belongs to layer `layer_idx`"""
-        lo, hi = self._layer_slices()[layer_idx]
-        return param[..., lo:hi]
-
     def layer_to_weight(self, in_dim, out_dim, layer_param):
         """layer vectors [N, L] or [N, S, L] -> (weights [.., in, out], bias [.., 1, out]): `[bias | W row-major]`"""
         if layer_param.ndim == 2:
@@ -261,39 +249,12 @@ class TestBNNmodel(nn.Module):
                     layer_param[:, :, :out_dim][:, :, None, :])
         raise ValueError("layer_to_weight: [N, L] or [N, S, L] expected")
 
-    def _pe_layout(self):
-        """as PriorBNNmodel._pe_layout: the patched presets in the 16-bit modes keep pe / dpe on the stitched grids"""
-        if self.precision != 0 and self.patch and getattr(self, "stitched_pe", True):
-            return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
-        return None
-
-    def _pe(self, lpe, stitched=False):
-        if self.precision != 0 and hip_path_supported(self.upsample_net, self.pixel_sizes, self.upsample_factors,
-                                                      self.patch, self.data_dim):
-            if not hasattr(self, "_weff_cache"):
-                self._weff_cache = {}        # the mappings are frozen for this model's lifetime (test_model.py:117-126)
-            return upsample_cifar_hip(self.upsample_net, lpe, self.stage1_bf16, self.pe_bf16, self._weff_cache)
-        net = self.upsample_net
-        if self.precision != 0 and tiled_2d_preferred(self.upsample_net, self.patch, self.data_dim):
-            net = stitched2d_module(self.upsample_net)
-        elif self.precision != 0 and phase_form_preferred(self.data_dim, self.patch):
-            net = phase_module(self.upsample_net) or self.upsample_net
-        return map_lpe_to_inr_inputs(net, lpe, self.latent_dim, self.pixel_sizes, self.upsample_factors,
-                                     self.patch, self.patch_nums, self.data_dim, stitched=stitched)
+    def _pe(self, lpe, stitched=False):          # InrGeometry._pe with this model's own, frozen upsampling net
+        return super()._pe(self.upsample_net, lpe, stitched, weff_cache=self._weff_cache)
 
     def _pe_from_sample(self, sample, S):
-        N, D = self._n, self._d_net
         lat = [self.pixel_sizes[i] // self.upsample_factors[i] for i in range(self.data_dim)]
-        lpe = sample[..., D:].permute(1, 0, 2).reshape(S, N, *lat, self.latent_dim)
-        return lpe
-
-    def _forward_parts(self, x, S, eps, differentiable):
-        specs = self._level_specs()
-        if differentiable:
-            sample = ops.sample_levels(specs, eps, S)
-        else:
-            sample = ops.reparam_fwd(specs, eps, S)                          # [N,S,Dtot]
-        return sample
+        return sample[..., self._d_net:].permute(1, 0, 2).reshape(S, self._n, *lat, self.latent_dim)
 
     # ---- A12 -------------------------------------------------------------------------------------------------
     def predict(self, x, random_seed=None, sample_size=1):
@@ -303,14 +264,14 @@ class TestBNNmodel(nn.Module):
         S, N, D = sample_size, self._n, self._d_net
         x = x.to(self.loc.device)
         eps = self._draw_all(S)
-        sample = self._forward_parts(x, S, eps, torch.is_grad_enabled())
+        sample = (ops.sample_levels if torch.is_grad_enabled() else ops.reparam_fwd)(self._level_specs(), eps, S)   # [N,S,Dtot]
         lpe = self._pe_from_sample(sample, S)
         pe = self._pe(lpe)                                                              # [N,S,P,16]
         h_w = sample[..., :D].reshape(N * S, D)
         parts = [h_w[:, lo:hi] @ self.linear_transform.A[i] for i, (lo, hi) in enumerate(self._layer_slices())]
         wvec = torch.cat(parts, -1)
         P = pe.shape[2]
-        y = ops.SirenFn.apply(x, pe.reshape(N * S, P, pe.shape[-1]).contiguous(), wvec, self._meta(x, S))
+        y = ops.SirenFn.apply(x, pe.reshape(N * S, P, pe.shape[-1]).contiguous(), wvec, self._meta(x, 16, S))
         y = y.reshape(N, S, P, -1)
         return y[:, 0] if S == 1 else y
 
@@ -383,7 +344,7 @@ class TestBNNmodel(nn.Module):
     def _gumbel(self, K):
         if self.g_samples is None:
             self.get_gumbel_sample()
-        if getattr(self, "_g_absmax", None) is None:
+        if self._g_absmax is None:                      # (g_samples assigned from outside)
             self._g_absmax = float(self.g_samples.abs().max())
         return self.g_samples[:K], self._g_absmax
 
@@ -486,131 +447,25 @@ class TestBNNmodel(nn.Module):
                 elbo.backward()
                 optimizer.step()
             return
-        lr = optimizer.param_groups[0]["lr"]
-        eps_adam = optimizer.param_groups[0].get("eps", 1e-8)
-        dev = self.loc.device
-        x = x.to(dev)
-        y = y.to(dev).contiguous()
-        S, N, D = sample_size, self._n, self._d_net
-        P, Cc = y.shape[1], y.shape[2]
-        specs = self._level_specs()
-        A = [a.detach() for a in self.linear_transform.A]
-        slices = self._layer_slices()
-        meta = self._meta(x, S)
-        # workspace that survives across calls (Adam state is re-zeroed = a fresh optimiser, the step counter
-        # restarts): its stable addresses let the two captured step graphs be reused by every fine-tune call
-        key = (x.data_ptr(), y.data_ptr(), tuple(x.shape), S, float(lr), float(eps_adam), self.precision,
-               self.loc.data_ptr(), self.log_scale.data_ptr(), bool(self.split_gemm), self.split_terms,
-               tuple(q.data_ptr() for q in A), tuple(q.data_ptr() for q in self.upsample_net.parameters()))
-        ws = self._ws
-        if ws is None or ws["key"] != key or ws["tab"].shape[0] < n_epochs:
-            # the Adam moments of all levels as views of one buffer: a fine-tune call (a few steps each, thousands of them
-            # per compression run) resets them with one launch
-            shapes = [lv.loc.shape for lv in self._levels for _ in range(4)]
-            state_flat, views = ops.zeroed_views(shapes, dev)
-            ws = dict(key=key, tab=ops.adam_table(lr, max(n_epochs, 2048)).to(dev), state_flat=state_flat,
-                      dyn=torch.zeros(2, device=dev), step_t=torch.zeros(1, device=dev, dtype=torch.long),
-                      states=[{k: next(views) for k in ("m_loc", "v_loc", "m_ls", "v_ls")} for lv in self._levels],
-                      graphs={}, warm=0,
-                      # bf16 copy of the coordinate grid: owned by the workspace that owns the graphs reading its address
-                      xf16=ops.xf_bf16(x, self.precision) if (self.precision in (1, 2) and dev.type == "cuda") else None)
-            self._ws = ws
-        else:
-            ws["state_flat"].zero_()
-        ws["step_t"].zero_()
-        tab, dyn, step_t, states = ws["tab"], ws["dyn"], ws["step_t"], ws["states"]
-        cfg = ops.adam_cfg(lr, 1, eps=eps_adam, dyn=dyn)
-        split = None
-        if self.split_gemm and self.precision != 0:
-            split = ws.get("split")
-            if split is None:                       # the mappings are fixed at test time: packed once per workspace
-                split = ops.ATransform(slices, dev, self.split_terms)
-                split.prepare(A)
-                ws["split"] = split
-
-        pe_lay = self._pe_layout()
-
-        def body(adjust):
-            ops.step_begin(tab, step_t, dyn)
-            eps = self._draw_all(S)
-            sample = ops.reparam_fwd(specs, eps, S)                                   # [N,S,Dtot]
-            lpe_t = self._pe_from_sample(sample, S).contiguous().requires_grad_(True)
-            with torch.enable_grad():
-                if pe_lay is not None:
-                    pe_c = self._pe(lpe_t, stitched=True)
-                else:
-                    pe = self._pe(lpe_t)
-                    pe_c = pe.reshape(N * S, P, pe.shape[-1]).contiguous()
-            h_w = sample[..., :D].reshape(N * S, D)
-            if split is not None:
-                wvec = split.forward(h_w, split.new_rows(N * S))
-            else:
-                wvec = torch.empty(N * S, D, device=dev, dtype=torch.float32)
-                for (lo, hi), a in zip(slices, A):
-                    torch.mm(h_w[:, lo:hi], a, out=wvec[:, lo:hi])
-            sse, dw, dpe = ops.siren_loss_bwd(x, pe_c.detach(), wvec, y, 1.0 / (S * P * Cc), meta, pe_layout=pe_lay,
-                                              xf16=ws["xf16"])
-            (d_lpe,) = torch.autograd.grad(pe_c, [lpe_t], dpe)                        # [S,N,*lat,C]
-            Dt = self._l1.D
-            if self.patch:        # levels 2 and 3 need the contiguous [N, S, D] gradient as well
-                dh = torch.empty(N * S, D, device=dev, dtype=torch.float32)
-                d_full = None
-            else:                 # the GEMMs write straight into the level-1 gradient buffer [N, S, D + Dlpe]
-                d_full = torch.empty(N, S, Dt, device=dev, dtype=torch.float32)
-                dh = d_full.view(N * S, Dt)[:, :D]
-            if split is not None:
-                split.dgrad(dw, dh)
-            else:
-                for (lo, hi), a in zip(slices, A):
-                    torch.mm(dw[:, lo:hi], a.t(), out=dh[:, lo:hi])
-            if d_full is None:
-                dh3 = dh.view(N, S, D)
-                d_full = torch.cat([dh3, d_lpe.reshape(S, N, -1).permute(1, 0, 2)], -1).contiguous()
-            else:
-                dh3 = None
-                d_full[:, :, D:].copy_(d_lpe.reshape(S, N, -1).permute(1, 0, 2))
-            grp = [self._group_kls(lv) for lv in self._levels] if adjust else None
-            for li, (lv, sp, e, stt) in enumerate(zip(self._levels, specs, eps, states)):
-                ops.posterior_bwd(sp, lv.p_loc, lv.p_log_scale, True, 1.0, d_full if li == 0 else dh3, e, S,
-                                  beta=lv.kl_beta, group_idx=lv.d_group_idx, n_groups=lv.n_groups, adam=cfg, state=stt)
-            if adjust:   # the old beta shaped this step's gradient; the new one acts from the next epoch on
-                for lv, gk in zip(self._levels, grp):
-                    ops.beta_update(gk, lv.kl_beta, lv.d_done, float(self.bit_per_group), float(self.kl_upper_buffer),
-                                    float(self.kl_lower_buffer), float(self.beta_step_size))
-            ops.step_end(step_t)
-
-        use_graph = self.use_graph and self.noise_source is None and not verbose and n_epochs >= 8 and dev.type == "cuda"
-        if use_graph:
+        # the step itself -- what it launches (TestStepPlan), the workspace `self._ws` with its two captured graphs, the parts of
+        # a step -- lives in test_step.py; a workspace whose key still holds is found again here, else a new one is built
+        step = test_step.TestTrainStep(self, x, y, n_epochs, optimizer.param_groups[0], sample_size, verbose)
+        step.prime()
+        graphed = step.plan.graphable
+        if graphed:
             # one noise stream per call (the reference reseeds with the epoch index before every step,
             # test_model.py:285,623 -- an un-capturable host action; either way every call sees the same stream)
             torch.manual_seed(0)
         for epoch in rng:
             adjust = (epoch % self.kl_adjust_gap == 0)
-            if not use_graph:
+            if not graphed:
                 torch.manual_seed(epoch)
-                body(adjust)
-                continue
-            g = ws["graphs"].get(adjust)
-            if g is None:
-                if ws["warm"] < 3:                     # eager warm-up steps (they are real steps)
-                    body(adjust)
-                    ws["warm"] += 1
-                    continue
-                try:
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):          # records; executes nothing
-                        body(adjust)
-                    ws["graphs"][adjust] = g
-                except Exception as exc:
-                    import warnings
-                    warnings.warn(f"HIP graph capture of the test-time step failed ({exc}); running eagerly")
-                    use_graph = False
-                    self.use_graph = False
-                    torch.cuda.synchronize()
-                    body(adjust)
-                    continue
-            g.replay()
+            # graph path: a warm-up step or the replay of the graph of this `adjust`; -> the exception of a failed capture
+            failure = step.graph_step(adjust) if graphed else step.body(adjust)
+            if failure is not None:
+                import warnings
+                warnings.warn(f"HIP graph capture of the test-time step failed ({failure}); running eagerly")
+                graphed = self.use_graph = False
 
     # ---- A20 -------------------------------------------------------------------------------------------------
     def _report(self, x, y):

@@ -323,9 +323,7 @@ class PriorTrainStep:
                 split.prepare(A)                  # the mappings change every step when they are trained
             wvec = split.forward(h_w, split.new_rows(N))
         else:
-            wvec = torch.empty(N, D, device=self.dev, dtype=torch.float32)
-            for (lo, hi), a in zip(slices, A):
-                torch.mm(h_w[:, lo:hi], a.detach(), out=wvec[:, lo:hi])
+            wvec = ops.a_transform_mm(h_w, A, slices, torch.empty(N, D, device=self.dev, dtype=torch.float32))
         return h_w, h16, eps, wvec, A16
 
     # ---- fused SIREN forward + MSE + backward -> (sse, dw, dpe, dw16)
@@ -361,11 +359,9 @@ class PriorTrainStep:
                 if p.training_mappings:
                     gA = [torch.mm(h16[:, lo:hi].t(), dw16[:, lo:hi]).float() for (lo, hi) in slices]
             else:
-                dh = torch.empty(N, D, device=self.dev, dtype=torch.float32)
-                for (lo, hi), a in zip(slices, self.A):
-                    torch.mm(dw[:, lo:hi], a.detach().t(), out=dh[:, lo:hi])
-                    if p.training_mappings:
-                        gA.append(torch.mm(h_w[:, lo:hi].t(), dw[:, lo:hi]))
+                dh = ops.a_transform_mm(dw, self.A, slices, torch.empty(N, D, device=self.dev, dtype=torch.float32), transpose=True)
+                if p.training_mappings:
+                    gA = [torch.mm(h_w[:, lo:hi].t(), dw[:, lo:hi]) for (lo, hi) in slices]
             if p.training_mappings and flat is not None:
                 gA = flat.pack(0, gA)
                 if p.capture_coll:  # bucket 0 (13.4 of the 14.4 MB) leaves from this stream (forked or not), inside the graph

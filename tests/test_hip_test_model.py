@@ -350,6 +350,73 @@ def test_test_time_training_captures_graphs_for_every_preset(name, precision):
         assert torch.isfinite(m.predict(X)).all()
 
 
+def _train12(m, X, Y):
+    """three warm-up steps, the captured plain step, and the captured step with the beta update at epoch 10"""
+    m.train(X, Y, 12, torch.optim.Adam(m.parameters(), lr=2e-4), False, sample_size=5)
+
+
+def _bf16_model(d, name):
+    cfg, n, m = build(d, name)
+    m.precision = 1
+    set_post(d, cfg, m)
+    return m, xdev(d, n), ydev(d)
+
+
+# what changes between two train() calls, one at a time (None: the storage of a level-2 parameter is re-allocated)
+KEY_CHANGES = {"cifar": [("pe_bf16", False), ("stage1_bf16", False), ("split_terms", 3), ("beta_step_size", 0.2)],
+               "patch1d": [("stitched_pe", False), ("h_loc", None)]}
+
+
+@pytest.mark.parametrize("name", sorted(KEY_CHANGES))
+def test_workspace_key_holds_what_the_captured_step_depends_on(name):
+    """an identical second call finds its workspace again; a switch, a beta constant or a storage that the captured step
+    depends on, changed before the next call, builds a new one (both graphs captured again) instead of replaying a stale graph"""
+    m, X, Y = _bf16_model(load(f"test_{name}.npz"), name)
+    _train12(m, X, Y)
+    ws = m._ws
+    assert ws is not None and set(ws["graphs"].keys()) == {True, False}
+    _train12(m, X, Y)
+    assert m._ws is ws
+    for attr, value in KEY_CHANGES[name]:
+        if value is None:
+            prm = getattr(m, attr)
+            prm.data = prm.data.clone()
+        else:
+            assert getattr(m, attr) != value
+            setattr(m, attr, value)
+        _train12(m, X, Y)
+        assert m._ws is not ws, attr
+        ws = m._ws                      # (the old one stays referenced up to here: `is not` cannot meet a recycled dict)
+        assert set(ws["graphs"].keys()) == {True, False} and m.use_graph, attr
+        for lv in m._levels:
+            assert torch.isfinite(lv.loc).all() and torch.isfinite(lv.log_scale).all() and torch.isfinite(lv.kl_beta).all(), attr
+
+
+def test_changed_beta_constant_acts_exactly():
+    """beta_step_size is a kernel argument of the captured adjusting step: changed between two calls it must act exactly as on
+    a model whose workspace was dropped by hand (three warm-up steps, new graphs), and differently from no change at all"""
+    d = load("test_cifar.npz")
+
+    def run(between):
+        m, X, Y = _bf16_model(d, "cifar")
+        _train12(m, X, Y)
+        between(m)
+        _train12(m, X, Y)
+        return [(lv.loc.detach().clone(), lv.log_scale.detach().clone(), lv.kl_beta.clone()) for lv in m._levels]
+
+    def changed(m):
+        m.beta_step_size = 0.2
+
+    def changed_and_dropped(m):
+        m.beta_step_size = 0.2
+        m._ws = None
+    a, b, c = run(changed), run(changed_and_dropped), run(lambda m: None)
+    for la, lb in zip(a, b):
+        for ta, tb in zip(la, lb):
+            assert torch.equal(ta, tb)
+    assert any(bool((la[2] != lc[2]).any()) for la, lc in zip(a, c))
+
+
 @pytest.mark.parametrize("width,precision", [(48, 1), (64, 2)])
 def test_wide_variant_test_time_training_and_bit_exact_decode(width, precision):
     """BASELINE's width variants on the test-time path (S = 5 samples through the wide SIREN kernel, group-ordered
