@@ -120,7 +120,9 @@ def test_deep_siren_against_fp32_restatement(prec, hidden, n_hidden):
     accumulation): depth compounds the operand rounding through sin(30 z).
     Measured on MI355X, worst over the cases, widths and depths (the emulation is within a few per cent of each): bf16 y 2.0e-2,
     sse 4.0e-4, dW 5.6e-3, dpe 2.6e-2, plain backward dW 1.6e-2, dpe 2.5e-2; f16 y 1.9e-3, sse 4.4e-5, dW 5.9e-4, dpe 2.9e-3,
-    plain backward dW 2.0e-3, dpe 3.2e-3."""
+    plain backward dW 2.0e-3, dpe 3.2e-3.  (The emulation here only scales the fp32 yardstick's limits with depth; the kernel
+    against an fp64 evaluator with the same rounding points, per layer, input half and row: test_hip_siren_operand_exact.py,
+    family "deep".)"""
     lim3 = np.array({1: (2.0e-2, 6e-4, 9e-3, 3.0e-2, 9e-3, 3.0e-2), 2: (2.7e-3, 6e-5, 1.4e-3, 3.6e-3, 1.4e-3, 3.6e-3)}[prec])
     for case in CASES:
         case = dict(case, hidden=hidden, n_hidden=n_hidden)

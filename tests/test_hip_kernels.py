@@ -111,7 +111,9 @@ def test_siren_fwd_bwd_loss(case):
 @pytest.mark.parametrize("case", [SIREN_CASES[0], SIREN_CASES[1], SIREN_CASES[2], SIREN_CASES[3], SIREN_CASES[4]])
 def test_siren_16bit_operands(case, prec):
     """bf16-operand / fp32-accumulate MFMA path against the fp32 oracle: bounded relative error
-    (operands carry 8 mantissa bits; accumulation, biases, loss and reductions are fp32)."""
+    (operands carry 8 mantissa bits; accumulation, biases, loss and reductions are fp32).  These limits carry the operands'
+    rounding noise; WHERE the kernels round, and that they round nowhere else, is held per block against an fp64 evaluator
+    with the same rounding points in test_hip_siren_operand_exact.py."""
     S, N, P, C = case["S"], case["N"], case["P"], case["C"]
     dims, D, xf, pe, wv, y = _siren_case(seed=1, **case)
     meta = SirenMeta(samples=S, n_pix=P, fourier_dim=case["F"], pe_dim=case["E"], n_hidden=case["n_hidden"], hidden=32,
@@ -139,7 +141,9 @@ def test_siren_16bit_operands_at_init_scale(prec, hidden):
     """the same comparison at the scale training actually runs at (SIREN initialisation, sqrt(6 / hidden) / 30), with limits
     set at 3x the error MEASURED on MI355X (tools/siren_err_probe.py, round 4: bf16 y 6.4e-3, sse 1.9e-4, dW 2.9e-3, dpe
     1.0e-2; f16 y 9.0e-4, sse 2.0e-5, dW 4.4e-4, dpe 1.2e-3 -- worst over the cases and widths 32 / 48 / 64): a kernel that
-    lost a factor of three in accuracy fails here, where the 3x-weight stress case above would still pass."""
+    lost a factor of three in accuracy fails here, where the 3x-weight stress case above would still pass.  (Accuracy of the
+    16-bit operand format as such; the kernels' own arithmetic -- every rounding point, per layer, per input half and per row --
+    is checked in test_hip_siren_operand_exact.py, whose evaluator rounds where the kernels round.)"""
     lim = {1: (2.0e-2, 6e-4, 9e-3, 3.0e-2), 2: (2.7e-3, 6e-5, 1.4e-3, 3.6e-3)}[prec]
     worst = np.zeros(4)
     for case in [SIREN_CASES[0], SIREN_CASES[3]] + ([SIREN_CASES[1], SIREN_CASES[2], SIREN_CASES[4]] if hidden == 32 else []):
@@ -255,7 +259,8 @@ WIDE_CASES = [
 @pytest.mark.parametrize("case", WIDE_CASES)
 def test_siren_wide_16bit_operands(case, prec):
     """the wide kernel against the fp32 torch restatement of the same MLP: forward, fused loss + backward, plain
-    backward; error bounds of the 16-bit operand types as for width 32; bitwise deterministic."""
+    backward; error bounds of the 16-bit operand types as for width 32; bitwise deterministic.  (Per layer, input half and row
+    against an evaluator with the kernel's rounding points: test_hip_siren_operand_exact.py, family "wide".)"""
     S, N, P, C, W = case["S"], case["N"], case["P"], case["C"], case["hidden"]
     dims, D, xf, pe, wv, y = _siren_case(seed=21, **case)
     meta = SirenMeta(samples=S, n_pix=P, fourier_dim=case["F"], pe_dim=case["E"], n_hidden=case["n_hidden"], hidden=W,
@@ -532,7 +537,9 @@ def test_siren_wave_family_against_the_workgroup_family(N, S, P, dpe):
     to 5e-4 of its largest entry (tile order, bias as two bf16 halves), input gradient to one bf16 ulp (1 / 128 of the largest
     entry), each also against the fp32 kernel at the 16-bit-operand tolerance; the wave family is bitwise reproducible, takes
     pixel-chunked launches and rows that are not on 16-byte boundaries, and leaves what it has no instance for (rows of
-    partial tiles, fp32 pe) to the workgroup family."""
+    partial tiles, fp32 pe) to the workgroup family.  (That the two differ by the bias form alone -- fp32 in the accumulator
+    against (hi, lo) halves through the matrix pipe -- is the statement of
+    test_hip_siren_operand_exact.py::test_wave_and_workgroup_family_against_the_same_evaluator.)"""
     lib = _lib.load()
     case = dict(F=16, E=16, n_hidden=3, C=3, P=P, N=N, S=S)
     dims, D, xf, pe, wv, y = _siren_case(seed=23, **case)
