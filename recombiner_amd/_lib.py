@@ -9,22 +9,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RCB_LIB: alternative build of the same ABI (same-box A/B timing of kernel changes); never a different backend
 LIB_PATH = os.environ.get("RCB_LIB") or os.path.join(_HERE, "lib", "librcb_hip.so")
 
-EXPORTS = ["rcb_version", "rcb_last_error_string", "rcb_struct_bytes", "rcb_siren_fwd", "rcb_siren_bwd", "rcb_siren_loss_bwd",
-           "rcb_reparam_fwd", "rcb_gauss_kl", "rcb_beta_update", "rcb_posterior_bwd", "rcb_adam_flat",
-           "rcb_col_moments", "rcb_rec_score_argmax", "rcb_rec_commit", "rcb_rec_workspace_bytes", "rcb_softplus_scale", "rcb_gauss_kl_colsum", "rcb_upconv_fwd",
-           "rcb_upconv_dgrad", "rcb_upconv_wgrad", "rcb_upconv_wgrad_workspace", "rcb_adam_multi", "rcb_step_begin",
-           "rcb_step_end", "rcb_upconv_weff_build", "rcb_upconv_weff_grad",
-           "rcb_upconv_dgrad_partial_rows", "rcb_debug_generic_kernels_only", "rcb_philox_normal",
-           "rcb_reparam_rng_fwd", "rcb_upconv_bwd_fused", "rcb_tile_gather", "rcb_tile_crop", "rcb_tile_fold",
-           "rcb_window_gather", "rcb_window_fold", "rcb_siren_reduce_chunks", "rcb_phaseconv_pack", "rcb_phaseconv_pack_uint4",
-           "rcb_phaseconv_fwd", "rcb_phaseconv_dgrad", "rcb_phaseconv_wgrad", "rcb_phaseconv_wgrad_workspace",
-           "rcb_phase_bigweight", "rcb_phase_bigweight_grad", "rcb_atrans_pack_elems", "rcb_atrans_pack", "rcb_atrans_plan",
-           "rcb_atrans_apply", "rcb_atrans_workspace_floats", "rcb_atrans_wgrad_narrow_workspace", "rcb_atrans_wgrad_narrow",
-           "rcb_stage1_1d_fwd", "rcb_stage1_1d_dgrad", "rcb_stage1_1d_wgrad", "rcb_stage1_1d_wgrad_workspace",
-           "rcb_reparam_hier_rng_fwd", "rcb_debug_siren_wave_tiles", "rcb_step_prepare", "rcb_step_tail",
-           "rcb_step_tail_eligible"]
-
-
 class RcbError(RuntimeError):
     pass
 
@@ -83,27 +67,91 @@ _lib = None
 ABI_VERSION = 407
 _MIRRORS = {0: SirenDesc, 1: Level, 2: LevelBwd, 3: AdamCfg, 4: AdamTensor, 5: RecDesc}
 
+# The prototype of every entry point of include/rcb.h, in header order: name -> (restype, [argtypes]).  load() applies it, so
+# ctypes converts Python numbers to the declared width and refuses an argument of the wrong class; the CPU tests hold the
+# table and the mirrors above to the header text (tests/test_host_cpu.py).  rcb_stream_t and every data pointer are c_void_p
+# (ptr() / addr() check what a tensor holds); a descriptor pointer takes byref(d), an array of the mirror, or None.
+_int, _i32, _i64, _u32, _u64, _f32, _f64, _p = C.c_int, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_double, C.c_void_p
+_siren, _level, _level_bwd = C.POINTER(SirenDesc), C.POINTER(Level), C.POINTER(LevelBwd)
+_adam_cfg, _adam_tensor, _rec = C.POINTER(AdamCfg), C.POINTER(AdamTensor), C.POINTER(RecDesc)
+PROTOTYPES = {
+    "rcb_version": (_int, []),
+    "rcb_last_error_string": (C.c_char_p, []),
+    "rcb_struct_bytes": (_i64, [_i32]),
+    "rcb_debug_siren_wave_tiles": (_int, [_i32]),
+    "rcb_siren_fwd": (_int, [_siren] + [_p] * 5),
+    "rcb_siren_bwd": (_int, [_siren] + [_p] * 7),
+    "rcb_siren_reduce_chunks": (_int, [_siren] + [_p] * 5),
+    "rcb_siren_loss_bwd": (_int, [_siren, _p, _p, _p, _p, _f32, _p, _p, _p, _p]),
+    "rcb_reparam_fwd": (_int, [_level, _i32, _i32, _i32, _i32, _p, _p]),
+    "rcb_reparam_hier_rng_fwd": (_int, [_level, _i32, _i32, _i32, _p, _p, _u64, _p, _p, _u64, _p]),
+    "rcb_philox_normal": (_int, [_p, _i64, _u64, _u32, _p, _i64, _u64, _p]),
+    "rcb_reparam_rng_fwd": (_int, [_p, _p, _i64, _u64, _u32, _p, _p, _p, _p, _p, _i32, _i64, _u64, _p]),
+    "rcb_gauss_kl": (_int, [_p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p, _p]),
+    "rcb_gauss_kl_colsum": (_int, [_p, _p, _i32, _p, _p, _i32, _i32, _p, _p]),
+    "rcb_beta_update": (_int, [_p, _p, _p, _i32, _i32, _f64, _f64, _f64, _f64, _p]),
+    "rcb_posterior_bwd": (_int, [_level_bwd, _adam_cfg, _p]),
+    "rcb_adam_flat": (_int, [_p, _p, _p, _p, _i64, _adam_cfg, _p]),
+    "rcb_adam_multi": (_int, [_adam_tensor, _i32, _adam_cfg, _p]),
+    "rcb_debug_generic_kernels_only": (_int, [_i32]),
+    "rcb_atrans_pack_elems": (_i64, [_i32, _p]),
+    "rcb_atrans_pack": (_int, [_p, _i32, _p, _p, _i32, _p]),
+    "rcb_atrans_plan": (_int, [_i64, _i32, _p, _i32, _p, _i32]),
+    "rcb_atrans_apply": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i32, _p, _p, _i32, _i32, _p, _p, _p, _p]),
+    "rcb_atrans_workspace_floats": (_i64, [_i64, _i32, _p, _p]),
+    "rcb_atrans_wgrad_narrow_workspace": (_i64, [_i32, _i32]),
+    "rcb_atrans_wgrad_narrow": (_int, [_p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _i32, _p, _p, _i32, _p]),
+    "rcb_step_begin": (_int, [_p, _i64, _p, _p, _p, _p]),
+    "rcb_step_end": (_int, [_p, _i32, _f64, _p, _p, _p, _i64, _p, _p, _p]),
+    "rcb_step_prepare": (_int, [_p, _i64, _p, _p, _p, _p, _i32, _p, _p, _i32] + [_p] * 6 + [_i32, _p, _p, _p, _p]),
+    "rcb_step_tail_eligible": (_int, [_level_bwd]),
+    "rcb_step_tail": (_int, [_level_bwd, _adam_cfg, _adam_tensor, _i32, _p, _i32, _f64, _p, _p, _i64, _p, _p, _p, _p]),
+    "rcb_col_moments": (_int, [_p, _p, _i32, _i32, _p, _p]),
+    "rcb_rec_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "rcb_rec_score_argmax": (_int, [_rec, _i32, _p, _i64, _p, _p, _p, _p, _p]),
+    "rcb_rec_commit": (_int, [_rec, _p, _p, _i32] + [_p] * 7),
+    "rcb_upconv_fwd": (_int, [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "rcb_upconv_dgrad_partial_rows": (_i32, [_i32]),
+    "rcb_upconv_dgrad": (_int, [_p, _i32, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p]),
+    "rcb_upconv_wgrad_workspace": (_i64, [_i32, _i32]),
+    "rcb_upconv_wgrad": (_int, [_p, _i32, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "rcb_upconv_bwd_fused": (_int, [_p] * 6 + [_i32, _i32, _i32, _p, _i64, _p, _p]),
+    "rcb_upconv_weff_build": (_int, [_p] * 6 + [_i32, _p, _p, _p, _p]),
+    "rcb_upconv_weff_grad": (_int, [_p, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p]),
+    "rcb_tile_gather": (_int, [_p, _p] + [_i32] * 10 + [_p]),
+    "rcb_tile_crop": (_int, [_p, _p] + [_i32] * 8 + [_p]),
+    "rcb_tile_fold": (_int, [_p, _p] + [_i32] * 8 + [_p]),
+    "rcb_phaseconv_pack_uint4": (_i64, [_i32, _i32, _i32]),
+    "rcb_phaseconv_pack": (_int, [_p, _i32, _i32, _p, _p, _p]),
+    "rcb_phaseconv_fwd": (_int, [_p] * 4 + [_i32] * 7 + [_p]),
+    "rcb_phaseconv_dgrad": (_int, [_p] * 4 + [_i32] * 6 + [_p]),
+    "rcb_phaseconv_wgrad_workspace": (_i64, [_i32, _i32]),
+    "rcb_phaseconv_wgrad": (_int, [_p] * 5 + [_i64] + [_i32] * 6 + [_p]),
+    "rcb_stage1_1d_fwd": (_int, [_p, _p, _p, _p, _i32, _i32, _p]),
+    "rcb_stage1_1d_dgrad": (_int, [_p, _p, _p, _i32, _i32, _p]),
+    "rcb_stage1_1d_wgrad_workspace": (_i64, []),
+    "rcb_stage1_1d_wgrad": (_int, [_p] * 5 + [_i64, _i32, _i32, _p]),
+    "rcb_window_gather": (_int, [_p, _p] + [_i32] * 6 + [_p]),
+    "rcb_window_fold": (_int, [_p, _p] + [_i32] * 6 + [_p]),
+    "rcb_phase_bigweight": (_int, [_p, _p, _i32, _i32, _p, _i32, _i32, _i32, _i32, _p]),
+    "rcb_phase_bigweight_grad": (_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _p]),
+    "rcb_softplus_scale": (_int, [_p, _p, _i64, _p]),
+}
+EXPORTS = list(PROTOTYPES)
+
 
 def load():
-    """dlopen the in-tree library (raises if it has not been built)."""
+    """dlopen the in-tree library (raises if it has not been built) and give every entry point its prototype."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RcbError(f"{LIB_PATH} not found: run `python -m recombiner_amd.build` (no CPU fallback exists)")
         lib = C.CDLL(LIB_PATH)
-        lib.rcb_last_error_string.restype = C.c_char_p
-        lib.rcb_upconv_wgrad_workspace.restype = C.c_int64
-        lib.rcb_rec_workspace_bytes.restype = C.c_int64
-        lib.rcb_phaseconv_pack_uint4.restype = C.c_int64
-        lib.rcb_phaseconv_wgrad_workspace.restype = C.c_int64
-        lib.rcb_stage1_1d_wgrad_workspace.restype = C.c_int64
-        lib.rcb_atrans_pack_elems.restype = C.c_int64
-        lib.rcb_atrans_wgrad_narrow_workspace.restype = C.c_int64
-        lib.rcb_atrans_workspace_floats.restype = C.c_int64
-        for name in EXPORTS:
+        for name, (restype, argtypes) in PROTOTYPES.items():
             if not hasattr(lib, name):
                 raise RcbError(f"{LIB_PATH} does not export {name}")
-        lib.rcb_struct_bytes.restype = C.c_int64
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if lib.rcb_version() != ABI_VERSION:
             raise RcbError(f"{LIB_PATH} is ABI version {lib.rcb_version()}, this binding was written against {ABI_VERSION}: "
                            "rebuild with `python -m recombiner_amd.build --force`")

@@ -19,6 +19,7 @@ from ._lib import AdamCfg, AdamTensor, Level, LevelBwd, RcbError, SirenDesc, add
 f32 = torch.float32
 f64 = torch.float64
 i32 = torch.int32
+bf16 = torch.bfloat16
 
 
 # ----------------------------------------------------------------------------------------------
@@ -185,7 +186,14 @@ def _siren_desc(meta: SirenMeta, wvec, xf, pe=None, dw_bf16=None, chunks=1, pe_l
     return d, G
 
 
-def _dev_ptr_strided(t):
+def _launch(entry, *args):
+    """enqueue one entry point of the library on the current stream (its last argument); a failure raises RcbError"""
+    check(getattr(_lib.load(), entry)(*args, stream_ptr()), entry)
+
+
+def _dev_ptr_strided(t, allow_none=False):
+    if t is None and allow_none:
+        return None
     if not t.is_cuda or t.dtype != f32:
         raise RcbError("expected an fp32 GPU tensor")
     return C.c_void_p(t.data_ptr())
@@ -202,31 +210,40 @@ def _check_pe(pe, G, meta, pe_layout=None):
 
 
 def siren_fwd(xf, pe, wvec, meta: SirenMeta, pixel_chunks=None, pe_layout=None):
-    lib = _lib.load()
     d, G = _siren_desc(meta, wvec, xf, pe, None, pixel_chunks or siren_pixel_chunks(wvec.shape[0], meta), pe_layout)
     _check_pe(pe, G, meta, pe_layout)
     y = torch.empty(G, meta.n_pix, meta.out_dim, device=wvec.device, dtype=f32)
-    check(lib.rcb_siren_fwd(C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec),
-                            ptr(y), stream_ptr()), "rcb_siren_fwd")
+    _launch("rcb_siren_fwd", C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec), ptr(y))
     return y
 
 
+def _chunk_partials(chunks, G, wvec, want_sse):
+    """few rows, pixel tiles split over several workgroups per row: (partial gradients [chunks, G, stride], partial sse [chunks, G])"""
+    if chunks == 1:
+        return None, None
+    part = torch.empty(chunks, G, wvec.stride(0), device=wvec.device, dtype=f32)
+    return part, (torch.empty(chunks, G, device=wvec.device, dtype=f32) if want_sse else None)
+
+
+def _reduce_chunks(d, part, sse_part, dw, sse):
+    """the partials summed in chunk order into dw / sse and into the 16-bit forms of the gradient that `d` names"""
+    _launch("rcb_siren_reduce_chunks", C.byref(d), ptr(part), ptr(sse_part, f32, True), _dev_ptr_strided(dw, True),
+            ptr(sse, f32, True))
+
+
 def siren_bwd(xf, pe, wvec, dy, meta: SirenMeta, want_dpe=True, pixel_chunks=None):
-    lib = _lib.load()
     chunks = pixel_chunks or siren_pixel_chunks(wvec.shape[0], meta)
     d, G = _siren_desc(meta, wvec, xf, pe, None, chunks)
     _check_pe(pe, G, meta)
     if tuple(dy.shape) != (G, meta.n_pix, meta.out_dim):
         raise RcbError("dy shape mismatch")
     dw = torch.empty(G, wvec.stride(0), device=wvec.device, dtype=f32)[:, :meta.d_net]
-    part = torch.empty(chunks, G, wvec.stride(0), device=wvec.device, dtype=f32) if chunks > 1 else None
+    part, _ = _chunk_partials(chunks, G, wvec, False)
     dpe = torch.empty_like(pe) if (want_dpe and meta.pe_dim) else None
-    check(lib.rcb_siren_bwd(C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec),
-                            ptr(dy.contiguous(), f32), _dev_ptr_strided(dw if part is None else part), ptr(dpe, None, True),
-                            stream_ptr()), "rcb_siren_bwd")
+    _launch("rcb_siren_bwd", C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec),
+            ptr(dy.contiguous(), f32), _dev_ptr_strided(dw if part is None else part), ptr(dpe, None, True))
     if part is not None:
-        check(lib.rcb_siren_reduce_chunks(C.byref(d), ptr(part), C.c_void_p(0), _dev_ptr_strided(dw), C.c_void_p(0),
-                                          stream_ptr()), "rcb_siren_reduce_chunks")
+        _reduce_chunks(d, part, None, dw, None)
     return dw, dpe
 
 
@@ -244,39 +261,19 @@ def siren_loss_bwd(xf, pe, wvec, target, dy_scale: float, meta: SirenMeta, want_
     A transform's batched weight-gradient GEMM, written by the kernel's epilogue).
     want_planes (16-bit modes): -> (sse, None, dpe, Planes): the gradient as its (hi, lo) bf16 planes INSTEAD of fp32
     (rcb_siren_desc.dw_bf16 + dw_lo): the operand form of ATransform.dgrad / .wgrad."""
-    lib = _lib.load()
     G = wvec.shape[0]
-    if want_planes:
-        if meta.precision == 0:
-            raise RcbError("gradient planes need a 16-bit precision mode")
-        planes = Planes(G, meta.d_net, wvec.device)
-        chunks = pixel_chunks or siren_pixel_chunks(G, meta)
-        d, G = _siren_desc(meta, wvec, xf, pe, None, chunks, pe_layout, xf16, dw_planes=planes if chunks == 1 else None)
-        _check_pe(pe, G, meta, pe_layout)
-        N = G // meta.samples
-        if tuple(target.shape) != (N, meta.n_pix, meta.out_dim):
-            raise RcbError(f"target must be [{N},{meta.n_pix},{meta.out_dim}], got {tuple(target.shape)}")
-        sse = torch.empty(G, device=wvec.device, dtype=f32)
-        dpe = torch.empty_like(pe) if (want_dpe and meta.pe_dim) else None
-        part = sse_part = None
-        if chunks > 1:
-            part = torch.empty(chunks, G, wvec.stride(0), device=wvec.device, dtype=f32)
-            sse_part = torch.empty(chunks, G, device=wvec.device, dtype=f32)
-        check(lib.rcb_siren_loss_bwd(C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec),
-                                     ptr(target, f32), C.c_float(dy_scale), ptr(sse if part is None else sse_part),
-                                     ptr(part, f32, True), ptr(dpe, None, True), stream_ptr()), "rcb_siren_loss_bwd")
-        if part is not None:
-            d2, _ = _siren_desc(meta, wvec, xf, pe, None, chunks, None, xf16, dw_planes=planes)
-            check(lib.rcb_siren_reduce_chunks(C.byref(d2), ptr(part), ptr(sse_part), C.c_void_p(0), ptr(sse), stream_ptr()),
-                  "rcb_siren_reduce_chunks")
-        return sse, None, dpe, planes
-    dw16 = None
-    if want_bf16:
-        if meta.precision == 0:
-            raise RcbError("the bf16 copy of the gradient needs a 16-bit precision mode")
-        dw16 = torch.empty(G, (meta.d_net + 7) // 8 * 8, device=wvec.device, dtype=bf16)[:, :meta.d_net]
+    if want_planes and meta.precision == 0:
+        raise RcbError("gradient planes need a 16-bit precision mode")
+    if want_planes and clock_probe is not None:
+        raise RcbError("siren_loss_bwd: clock_probe goes with the fp32 form of the gradient, not with want_planes")
+    want_bf16 = want_bf16 and not want_planes
+    if want_bf16 and meta.precision == 0:
+        raise RcbError("the bf16 copy of the gradient needs a 16-bit precision mode")
+    # where the gradient goes besides (planes: instead of) the fp32 dw; written by whichever launch forms the final sums
+    planes = Planes(G, meta.d_net, wvec.device) if want_planes else None
+    dw16 = torch.empty(G, (meta.d_net + 7) // 8 * 8, device=wvec.device, dtype=bf16)[:, :meta.d_net] if want_bf16 else None
     chunks = pixel_chunks or siren_pixel_chunks(G, meta)
-    d, G = _siren_desc(meta, wvec, xf, pe, None if chunks > 1 else dw16, chunks, pe_layout, xf16)
+    d, G = _siren_desc(meta, wvec, xf, pe, dw16 if chunks == 1 else None, chunks, pe_layout, xf16, planes if chunks == 1 else None)
     if clock_probe is not None:          # int64 [256, 4]: per-workgroup clock stamps (rcb_siren_desc.clock_probe; shader_clock_ghz)
         if clock_probe.dtype != torch.int64 or clock_probe.numel() < 1024 or not clock_probe.is_contiguous():
             raise RcbError("clock_probe: contiguous int64 [256, 4] expected")
@@ -286,20 +283,17 @@ def siren_loss_bwd(xf, pe, wvec, target, dy_scale: float, meta: SirenMeta, want_
     if tuple(target.shape) != (N, meta.n_pix, meta.out_dim):
         raise RcbError(f"target must be [{N},{meta.n_pix},{meta.out_dim}], got {tuple(target.shape)}")
     sse = torch.empty(G, device=wvec.device, dtype=f32)
-    dw = torch.empty(G, wvec.stride(0), device=wvec.device, dtype=f32)[:, :meta.d_net]
+    dw = None if want_planes else torch.empty(G, wvec.stride(0), device=wvec.device, dtype=f32)[:, :meta.d_net]
     dpe = torch.empty_like(pe) if (want_dpe and meta.pe_dim) else None
-    part = sse_part = None
-    if chunks > 1:          # few rows: pixel tiles split over several workgroups per row, partials summed in chunk order
-        part = torch.empty(chunks, G, wvec.stride(0), device=wvec.device, dtype=f32)
-        sse_part = torch.empty(chunks, G, device=wvec.device, dtype=f32)
-    check(lib.rcb_siren_loss_bwd(C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec),
-                                 ptr(target, f32), C.c_float(dy_scale), ptr(sse if part is None else sse_part),
-                                 _dev_ptr_strided(dw if part is None else part), ptr(dpe, None, True), stream_ptr()),
-          "rcb_siren_loss_bwd")
+    part, sse_part = _chunk_partials(chunks, G, wvec, True)
+    _launch("rcb_siren_loss_bwd", C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec), ptr(target, f32),
+            dy_scale, ptr(sse if part is None else sse_part), _dev_ptr_strided(dw if part is None else part, True),
+            ptr(dpe, None, True))
     if part is not None:
-        d2, _ = _siren_desc(meta, wvec, xf, pe, dw16, chunks, None, xf16)
-        check(lib.rcb_siren_reduce_chunks(C.byref(d2), ptr(part), ptr(sse_part), _dev_ptr_strided(dw), ptr(sse), stream_ptr()),
-              "rcb_siren_reduce_chunks")
+        d2, _ = _siren_desc(meta, wvec, xf, pe, dw16, chunks, None, xf16, planes)
+        _reduce_chunks(d2, part, sse_part, dw, sse)
+    if want_planes:
+        return sse, None, dpe, planes
     return (sse, dw, dpe, dw16) if want_bf16 else (sse, dw, dpe)
 
 
@@ -375,7 +369,6 @@ class LevelSpec:
 
 def reparam_fwd(levels: Sequence[LevelSpec], eps: Sequence[torch.Tensor], samples: int):
     """out[N, S, cols_out(level 0)] (rcb_reparam_fwd)."""
-    lib = _lib.load()
     n = levels[0].n_inr
     cols = levels[0].cols_out
     # gathered levels (test-time layout) of several INRs per launch: scratch for their packed (mu, sigma) records (rcb.h)
@@ -388,7 +381,7 @@ def reparam_fwd(levels: Sequence[LevelSpec], eps: Sequence[torch.Tensor], sample
         if tuple(e.shape) != (n, samples, lv.cols_out) or not e.is_contiguous():
             raise RcbError(f"eps must be contiguous [{n},{samples},{lv.cols_out}], got {tuple(e.shape)}")
     out = torch.empty(n, samples, cols, device=levels[0].loc.device, dtype=f32)
-    check(lib.rcb_reparam_fwd(arr, len(levels), n, samples, cols, ptr(out), stream_ptr()), "rcb_reparam_fwd")
+    _launch("rcb_reparam_fwd", arr, len(levels), n, samples, cols, ptr(out))
     return out
 
 
@@ -400,12 +393,16 @@ def hier_rng_eligible(levels: Sequence[LevelSpec]):
                and lv.cols_out == lv.cols == levels[0].cols for lv in levels[1:])
 
 
+def _seed_u64(seed):
+    """a seed as the uint64 the kernels take (ctypes does not range-check; negative seeds wrap as they always did)"""
+    return int(seed) & (2 ** 64 - 1)
+
+
 def reparam_hier_rng(levels: Sequence[LevelSpec], eps_out: Sequence[torch.Tensor], seed: int, rng_streams: Sequence[int], step,
                      group_offset=0):
     """-> out [N, 1, cols]: the multi-level training sample with every level's noise drawn in the kernel
     (rcb_reparam_hier_rng_fwd); eps_out[l] ([N, 1, cols], fp32) receives level l's noise for the posterior update.  `step` is the
     device-resident int64 step counter; level l draws from Philox stream rng_streams[l] at element index n * cols + d."""
-    lib = _lib.load()
     n, cols = levels[0].n_inr, levels[0].cols_out
     for e in eps_out:
         if tuple(e.shape) != (n, 1, cols) or e.dtype != f32 or not e.is_contiguous():
@@ -414,8 +411,8 @@ def reparam_hier_rng(levels: Sequence[LevelSpec], eps_out: Sequence[torch.Tensor
     outs = (C.c_void_p * len(levels))(*[e.data_ptr() for e in eps_out])
     streams = (C.c_uint32 * len(levels))(*[int(v) for v in rng_streams])
     out = torch.empty(n, 1, cols, device=levels[0].loc.device, dtype=f32)
-    check(lib.rcb_reparam_hier_rng_fwd(arr, len(levels), n, cols, outs, ptr(out), C.c_uint64(seed & (2 ** 64 - 1)), streams,
-                                       ptr(step, torch.int64), C.c_uint64(group_offset), stream_ptr()), "rcb_reparam_hier_rng_fwd")
+    _launch("rcb_reparam_hier_rng_fwd", arr, len(levels), n, cols, outs, ptr(out), _seed_u64(seed), streams, ptr(step, torch.int64),
+            group_offset)
     return out
 
 
@@ -498,38 +495,32 @@ def reparam_rng(lv: LevelSpec, seed: int, rng_stream: int, step, want_bf16=False
     (rcb_reparam_rng_fwd).  `step` is the device-resident int64 step counter.  want_bf16: third result, a bf16 copy of
     out as [n, cols] with a row stride that is a multiple of 8 (operand of the A transform's weight-gradient GEMM).
     buffers: write into the tensors of sample_buffers() instead of new ones."""
-    lib = _lib.load()
     if not rng_eligible(lv):
         raise RcbError("reparam_rng: plain levels only")
     n, cols = lv.rows, lv.cols
     out, eps, o16 = buffers if buffers is not None else sample_buffers(lv, want_bf16)
-    if isinstance(o16, Planes):            # the sample as (hi, lo) planes (sample_buffers(planes=True)): -> (None, eps, Planes)
-        check(lib.rcb_reparam_rng_fwd(ptr(lv.loc.detach(), f32), ptr(lv.log_scale.detach(), f32), C.c_int64(n * cols),
-                                      C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint32(rng_stream), ptr(step, torch.int64),
-                                      ptr(eps, f32, True), ptr(out, f32, True), C.c_void_p(o16.buf[0].data_ptr()),
-                                      C.c_void_p(o16.buf[1].data_ptr()), int(cols), C.c_int64(o16.ld), C.c_uint64(group_offset),
-                                      stream_ptr()), "rcb_reparam_rng_fwd")
+    planes = isinstance(o16, Planes)       # the sample as (hi, lo) planes (sample_buffers(planes=True)): -> (None, eps, Planes)
+    if planes:
+        hi, lo, ld = o16.buf[0].data_ptr(), o16.buf[1].data_ptr(), o16.ld
+    else:
+        if want_bf16 and o16 is None:
+            raise RcbError("reparam_rng: the buffers have no bf16 copy")
+        if not want_bf16:
+            o16 = None
+        hi, lo, ld = ptr(o16, bf16, True), None, 0 if o16 is None else o16.stride(0)
+    _launch("rcb_reparam_rng_fwd", ptr(lv.loc.detach(), f32), ptr(lv.log_scale.detach(), f32), n * cols, _seed_u64(seed),
+            rng_stream, ptr(step, torch.int64), ptr(eps, f32, True), ptr(out, f32, planes), hi, lo, cols, ld, group_offset)
+    if planes:
         return out, eps, o16
-    if want_bf16 and o16 is None:
-        raise RcbError("reparam_rng: the buffers have no bf16 copy")
-    if not want_bf16:
-        o16 = None
-    check(lib.rcb_reparam_rng_fwd(ptr(lv.loc.detach(), f32), ptr(lv.log_scale.detach(), f32), C.c_int64(n * cols),
-                                  C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint32(rng_stream), ptr(step, torch.int64),
-                                  ptr(eps, f32, True), ptr(out), ptr(o16, bf16, True), C.c_void_p(0), int(cols),
-                                  C.c_int64(0 if o16 is None else o16.stride(0)), C.c_uint64(group_offset), stream_ptr()),
-          "rcb_reparam_rng_fwd")
     return (out, eps, o16[:, :cols]) if want_bf16 else (out, eps)
 
 
 def philox_normal(n, seed: int, rng_stream: int, step, device="cuda", group_offset=0):
     """the noise stream of reparam_rng as a tensor (step: python int or device int64 tensor)"""
-    lib = _lib.load()
     out = torch.empty(n, device=device, dtype=f32)
     dev_step = step if torch.is_tensor(step) else None
-    check(lib.rcb_philox_normal(ptr(out), C.c_int64(n), C.c_uint64(seed & (2 ** 64 - 1)), C.c_uint32(rng_stream),
-                                ptr(dev_step, torch.int64, True), C.c_int64(0 if dev_step is not None else int(step)),
-                                C.c_uint64(group_offset), stream_ptr()), "rcb_philox_normal")
+    _launch("rcb_philox_normal", ptr(out), n, _seed_u64(seed), rng_stream, ptr(dev_step, torch.int64, True),
+            0 if dev_step is not None else int(step), group_offset)
     return out
 
 
@@ -579,7 +570,7 @@ def _level_bwd(lv: LevelSpec, p_loc, p_scale, p_is_log: bool, kl_scalar: float, 
         b.rng_group_offset = ns.group_offset
         if ns.redraw_eps and eps is not None:
             raise RcbError("posterior_bwd: redraw_eps takes eps = None")
-        b.rng_seed = ns.seed & (2 ** 64 - 1)
+        b.rng_seed = _seed_u64(ns.seed)
         b.rng_step_dev = addr(ns.step, torch.int64)
         b.rng_step_add = int(ns.step_add)
         b.rng_stream = int(ns.rng_stream)
@@ -593,11 +584,9 @@ def posterior_bwd(lv: LevelSpec, p_loc, p_scale, p_is_log: bool, kl_scalar: floa
                   want_grads=False, kl_accum=None, kl_scalar_dev=None, next_sample: Optional["NextSample"] = None):
     """Fused gradient gather + KL gradient (+ Adam).  Returns (g_loc, g_log_scale) when requested.
     next_sample (plain levels with Adam): also draw the next step's sample from the updated parameters."""
-    lib = _lib.load()
     b, g_loc, g_ls, _ws = _level_bwd(lv, p_loc, p_scale, p_is_log, kl_scalar, d_out, eps, samples, beta, group_idx, n_groups,
                                     adam, state, want_grads, kl_accum, kl_scalar_dev, next_sample)
-    check(lib.rcb_posterior_bwd(C.byref(b), C.byref(adam) if adam is not None else None, stream_ptr()),
-          "rcb_posterior_bwd")
+    _launch("rcb_posterior_bwd", C.byref(b), C.byref(adam) if adam is not None else None)
     return g_loc, g_ls
 
 
@@ -635,7 +624,6 @@ def sample_levels(levels: Sequence[LevelSpec], eps, samples):
 def gauss_kl(loc, log_scale, p_loc, p_scale, p_is_log=False, beta=None, group_idx=None, seg_start=None,
              seg_end=None, want_rows=True, want_groups=False):
     """-> (kl_row fp64 [rows] or None, kl_group fp64 [rows, G] or None)."""
-    lib = _lib.load()
     loc2 = loc.detach().reshape(loc.shape[0], -1)
     ls2 = log_scale.detach().reshape(loc.shape[0], -1)
     rows, cols = loc2.shape
@@ -645,10 +633,9 @@ def gauss_kl(loc, log_scale, p_loc, p_scale, p_is_log=False, beta=None, group_id
     pl, ps = p_loc.reshape(-1), p_scale.reshape(-1)
     if pl.numel() != cols or ps.numel() != cols:
         raise RcbError("prior shape mismatch")
-    check(lib.rcb_gauss_kl(ptr(loc2, f32), ptr(ls2, f32), ptr(pl, f32), ptr(ps, f32), int(bool(p_is_log)), rows,
-                           cols, ptr(beta, f32, True), ptr(group_idx, i32, True), n_groups,
-                           ptr(seg_start, i32, True), ptr(seg_end, i32, True), ptr(kl_row, f64, True),
-                           ptr(kl_group, f64, True), stream_ptr()), "rcb_gauss_kl")
+    _launch("rcb_gauss_kl", ptr(loc2, f32), ptr(ls2, f32), ptr(pl, f32), ptr(ps, f32), int(bool(p_is_log)), rows, cols,
+            ptr(beta, f32, True), ptr(group_idx, i32, True), n_groups, ptr(seg_start, i32, True), ptr(seg_end, i32, True),
+            ptr(kl_row, f64, True), ptr(kl_group, f64, True))
     return kl_row, kl_group
 
 
@@ -687,14 +674,12 @@ def gauss_kl_colsum_fx(loc, q_scale, p_loc, p_scale, q_is_log=False):
     """-> int64 [cols + 1]: sum over rows of the elementwise KL in units of 1 / COLSUM_FX nats (every element rounded to the
     integer grid on its own, exact integer accumulation: bitwise independent of the order of the workgroups and of how the
     rows are sharded; summed over ranks with an integer all-reduce) + the count of not-representable elements."""
-    lib = _lib.load()
     l2 = loc.detach().reshape(loc.shape[0], -1).contiguous()
     s2 = q_scale.detach().reshape(loc.shape[0], -1).contiguous()
     rows, cols = l2.shape
     out = torch.empty(cols + 1, device=loc.device, dtype=torch.int64)     # [cols] sums + the not-representable counter
-    check(lib.rcb_gauss_kl_colsum(ptr(l2, f32), ptr(s2, f32), int(bool(q_is_log)), ptr(p_loc.reshape(-1).contiguous(), f32),
-                                  ptr(p_scale.reshape(-1).contiguous(), f32), rows, cols, ptr(out), stream_ptr()),
-          "rcb_gauss_kl_colsum")
+    _launch("rcb_gauss_kl_colsum", ptr(l2, f32), ptr(s2, f32), int(bool(q_is_log)), ptr(p_loc.reshape(-1).contiguous(), f32),
+            ptr(p_scale.reshape(-1).contiguous(), f32), rows, cols, ptr(out))
     return out
 
 
@@ -711,11 +696,9 @@ def colsum_from_fx(fx):
 
 
 def beta_update(kl_group, beta, done_u8, bits=16.0, upper=0.0, lower=0.4, step=0.05):
-    lib = _lib.load()
     rows, G = beta.shape
-    check(lib.rcb_beta_update(ptr(kl_group, f64), ptr(beta, f32), ptr(done_u8, torch.uint8, True), rows, G,
-                              C.c_double(bits), C.c_double(upper), C.c_double(lower), C.c_double(step),
-                              stream_ptr()), "rcb_beta_update")
+    _launch("rcb_beta_update", ptr(kl_group, f64), ptr(beta, f32), ptr(done_u8, torch.uint8, True), rows, G,
+            bits, upper, lower, step)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -742,29 +725,32 @@ def zeroed_views(shapes, device):
 
 
 def adam_flat(p, g, m, v, cfg: AdamCfg):
-    lib = _lib.load()
     if not (p.is_contiguous() and g.is_contiguous()):
         raise RcbError("adam_flat needs contiguous tensors")
-    check(lib.rcb_adam_flat(ptr(p.detach(), f32), ptr(g, f32), ptr(m, f32), ptr(v, f32), C.c_int64(p.numel()),
-                            C.byref(cfg), stream_ptr()), "rcb_adam_flat")
+    _launch("rcb_adam_flat", ptr(p.detach(), f32), ptr(g, f32), ptr(m, f32), ptr(v, f32), p.numel(), C.byref(cfg))
+
+
+def _step_begin_args(table, step, dyn, kl_slots, who):
+    if table.dim() != 2 or table.shape[1] != 2 or (kl_slots is not None and kl_slots.numel() != 1024):
+        raise RcbError(f"{who}: table must be [n_steps, 2], kl_slots [1024]")
+    return ptr(table, f32), table.shape[0], ptr(step, torch.int64), ptr(dyn, f32), ptr(kl_slots, torch.int64, True)
+
+
+def _n_log(*logs):
+    """entries every given step log has room for (0 without logs)"""
+    return min((t.numel() for t in logs if t is not None), default=0)
 
 
 def step_begin(table, step, dyn, kl_slots=None):
     """dyn <- table[step] (per-step Adam scalars), kl_slots <- 0 (rcb_step_begin); everything stays on the device."""
-    lib = _lib.load()
-    if table.dim() != 2 or table.shape[1] != 2 or (kl_slots is not None and kl_slots.numel() != 1024):
-        raise RcbError("step_begin: table must be [n_steps, 2], kl_slots [1024]")
-    check(lib.rcb_step_begin(ptr(table, f32), C.c_int64(table.shape[0]), ptr(step, torch.int64), ptr(dyn, f32),
-                             ptr(kl_slots, torch.int64, True), stream_ptr()), "rcb_step_begin")
+    _launch("rcb_step_begin", *_step_begin_args(table, step, dyn, kl_slots, "step_begin"))
 
 
 def step_end(step, sse=None, mse_scale=1.0, kl_slots=None, mse_log=None, kl_log=None, aux_counter=None):
     """mse_log[step] = mse_scale * sum(sse), kl_log[step] = sum(kl_slots), step += 1, aux_counter += 1 (rcb_step_end)."""
-    lib = _lib.load()
-    n_log = min(t.numel() for t in (mse_log, kl_log) if t is not None) if (mse_log is not None or kl_log is not None) else 0
-    check(lib.rcb_step_end(ptr(sse, f32, True), 0 if sse is None else sse.numel(), C.c_double(mse_scale),
-                           ptr(kl_slots, torch.int64, True), ptr(mse_log, f64, True), ptr(kl_log, f64, True), C.c_int64(n_log),
-                           ptr(step, torch.int64), ptr(aux_counter, torch.int64, True), stream_ptr()), "rcb_step_end")
+    _launch("rcb_step_end", ptr(sse, f32, True), 0 if sse is None else sse.numel(), mse_scale, ptr(kl_slots, torch.int64, True),
+            ptr(mse_log, f64, True), ptr(kl_log, f64, True), _n_log(mse_log, kl_log), ptr(step, torch.int64),
+            ptr(aux_counter, torch.int64, True))
 
 
 ADAM_MAX_TENSORS = 16
@@ -782,11 +768,10 @@ def _adam_tensors(chunk, what):
 
 def adam_multi(params, grads, ms, vs, cfg: AdamCfg):
     """Adam step over a list of fp32 tensors in one launch (rcb_adam_multi); lists longer than 16 are chunked."""
-    lib = _lib.load()
     items = list(zip(params, grads, ms, vs))
     for k in range(0, len(items), ADAM_MAX_TENSORS):
         chunk = items[k:k + ADAM_MAX_TENSORS]
-        check(lib.rcb_adam_multi(_adam_tensors(chunk, "adam_multi"), len(chunk), C.byref(cfg), stream_ptr()), "rcb_adam_multi")
+        _launch("rcb_adam_multi", _adam_tensors(chunk, "adam_multi"), len(chunk), C.byref(cfg))
 
 
 def step_fused_enabled():
@@ -799,24 +784,11 @@ def step_fused_enabled():
 def step_prepare(table, step, dyn, kl_slots, atrans, A, W1, b1, W2, W3, bf16_out):
     """step_begin(table, step, dyn, kl_slots) + atrans.prepare(A) + upconv_weff_build(W1, b1, W2, W3, bf16_out) in ONE launch
     (rcb_step_prepare): every output bit-identical to theirs.  -> (Weff1, b1rep, Weff2, Weff3, pack) of upconv_weff_build."""
-    lib = _lib.load()
-    if table.dim() != 2 or table.shape[1] != 2 or (kl_slots is not None and kl_slots.numel() != 1024):
-        raise RcbError("step_prepare: table must be [n_steps, 2], kl_slots [1024]")
+    begin = _step_begin_args(table, step, dyn, kl_slots, "step_prepare")
     arr = atrans.mats_arg(A)
-    if (tuple(W1.shape), tuple(W2.shape), tuple(W3.shape)) != ((64, 128, 5, 5), (64, 64, 3, 3), (16, 64, 3, 3)):
-        raise RcbError("step_prepare: conv weight shapes of the CIFAR upsampling net expected")
-    dev, dt = W1.device, (bf16 if bf16_out else f32)
-    weff1 = torch.empty(512, 4096, device=dev, dtype=dt)
-    b1rep = torch.empty(4096, device=dev, dtype=dt)
-    weff2 = torch.empty(2, 2, 64, 2, 2, 64, device=dev, dtype=f32)
-    weff3 = torch.empty(2, 2, 64, 2, 2, 16, device=dev, dtype=f32)
-    pack = torch.empty(UPCONV_PACK_UINT4 * 16, device=dev, dtype=torch.uint8)
-    check(lib.rcb_step_prepare(ptr(table, f32), C.c_int64(table.shape[0]), ptr(step, torch.int64), ptr(dyn, f32),
-                               ptr(kl_slots, torch.int64, True), arr, len(atrans.sizes), atrans._sizes_c, ptr(atrans.packed),
-                               int(atrans.terms == 3), ptr(W1.detach(), f32), ptr(b1.detach(), f32), ptr(W2.detach(), f32),
-                               ptr(W3.detach(), f32), ptr(weff1), ptr(b1rep), int(bool(bf16_out)), ptr(weff2), ptr(weff3),
-                               ptr(pack), stream_ptr()), "rcb_step_prepare")
-    return weff1, b1rep, weff2, weff3, pack
+    out, build = _weff_build_args(W1, b1, W2, W3, bf16_out, "step_prepare")
+    _launch("rcb_step_prepare", *begin, arr, len(atrans.sizes), atrans._sizes_c, ptr(atrans.packed), int(atrans.terms == 3), *build)
+    return out
 
 
 STEP_TAIL_TICKETS = 65
@@ -837,11 +809,9 @@ def step_tail(level_args, level_kwargs, params, grads, ms, vs, cfg: AdamCfg, tic
     if tickets.dtype != torch.int32 or tickets.numel() != STEP_TAIL_TICKETS:
         raise RcbError(f"step_tail: tickets must be {STEP_TAIL_TICKETS} int32")
     arr = _adam_tensors(list(zip(params, grads, ms, vs)), "step_tail")
-    n_log = min(t.numel() for t in (mse_log, kl_log) if t is not None) if (mse_log is not None or kl_log is not None) else 0
-    check(lib.rcb_step_tail(C.byref(b), C.byref(cfg), arr, len(params), ptr(sse, f32, True), 0 if sse is None else sse.numel(),
-                            C.c_double(mse_scale), ptr(mse_log, f64, True), ptr(kl_log, f64, True), C.c_int64(n_log),
-                            ptr(step, torch.int64), ptr(aux_counter, torch.int64, True), ptr(tickets, torch.int32), stream_ptr()),
-          "rcb_step_tail")
+    _launch("rcb_step_tail", C.byref(b), C.byref(cfg), arr, len(params), ptr(sse, f32, True), 0 if sse is None else sse.numel(),
+            mse_scale, ptr(mse_log, f64, True), ptr(kl_log, f64, True), _n_log(mse_log, kl_log), ptr(step, torch.int64),
+            ptr(aux_counter, torch.int64, True), ptr(tickets, torch.int32))
     return True
 
 
@@ -849,12 +819,11 @@ def col_moments_fx(loc, log_scale):
     """-> int64 [6 * cols + 1]: exact fixed-point sums over the rows of loc (rcb_col_moments): as [3, 2, cols] the (hi, lo)
     parts of sum x, sum x^2, sum sigma^2, then the count of terms that were NaN / Inf / out of range.  Integer sums: add them
     over ranks with an integer all-reduce, then moments_from_fx."""
-    lib = _lib.load()
     l2 = loc.detach().reshape(loc.shape[0], -1)
     s2 = log_scale.detach().reshape(loc.shape[0], -1)
     rows, cols = l2.shape
     out = torch.empty(6 * cols + 1, device=loc.device, dtype=torch.int64)
-    check(lib.rcb_col_moments(ptr(l2, f32), ptr(s2, f32), rows, cols, ptr(out), stream_ptr()), "rcb_col_moments")
+    _launch("rcb_col_moments", ptr(l2, f32), ptr(s2, f32), rows, cols, ptr(out))
     return out
 
 
@@ -883,10 +852,8 @@ def shader_clock_ghz(probe):
 
 
 def softplus_scale(log_scale):
-    lib = _lib.load()
     out = torch.empty_like(log_scale)
-    check(lib.rcb_softplus_scale(ptr(log_scale.detach(), f32), ptr(out), C.c_int64(out.numel()), stream_ptr()),
-          "rcb_softplus_scale")
+    _launch("rcb_softplus_scale", ptr(log_scale.detach(), f32), ptr(out), out.numel())
     return out
 
 
@@ -964,9 +931,10 @@ class RecJobs:
         return cls(dev(row), dev(start), dev(glen), grp), order
 
 
-def _rec_desc(loc, scale, p_loc, p_scale, tables: RecTables, gumbel, gumbel_absmax, jobs: RecJobs):
+def _rec_desc(loc, scale, p_loc, p_scale, tables: RecTables, gumbel, gumbel_absmax, jobs: RecJobs, rows=1 << 30):
+    """rows: of the parameter matrix when loc is None (rcb_rec_commit needs neither the posterior nor the Gumbel noise)"""
     mg, ptrs, amax = tables.device_arrays()
-    rows, cols = (loc.shape if loc is not None else (int(1 << 30), p_loc.shape[0]))
+    rows, cols = loc.shape if loc is not None else (rows, p_loc.numel())
     d = _lib.RecDesc(addr(None if loc is None else loc.detach(), f32), addr(scale, f32), addr(p_loc, f32), addr(p_scale, f32),
                      int(rows), int(cols), addr(ptrs, torch.int64), addr(amax, f64), int(mg),
                      addr(gumbel, f64), float(gumbel_absmax), int(tables.K), addr(jobs.row, i32), addr(jobs.start, i32),
@@ -1000,8 +968,7 @@ def rec_score(loc, scale, p_loc, p_scale, tables: RecTables, gumbel, jobs: RecJo
     best = torch.empty(B, 2, device=dev, dtype=f64)
     unc = torch.empty(B, device=dev, dtype=torch.uint8)
     logw0 = torch.empty(K, device=dev, dtype=f64) if want_logw0 else None
-    check(lib.rcb_rec_score_argmax(C.byref(d), int(mode), ptr(ws), C.c_int64(n_ws), ptr(idx), ptr(best), ptr(unc),
-                                   ptr(logw0, f64, True), stream_ptr()), "rcb_rec_score_argmax")
+    _launch("rcb_rec_score_argmax", C.byref(d), int(mode), ptr(ws), n_ws, ptr(idx), ptr(best), ptr(unc), ptr(logw0, f64, True))
     return idx, best, unc, logw0
 
 
@@ -1009,20 +976,16 @@ def rec_commit(p_loc, p_scale, tables: RecTables, jobs: RecJobs, idx, n_groups=0
                enc_mask=None, done=None, beta=None, idx_groupwise=None):
     """z = p_loc + p_scale * xi[idx] per job (fp64 mul, add) and the state update of compress_group (rcb_rec_commit).
     enc_sample / enc_mask: fp32 [rows, cols]; done uint8 / beta fp32 / idx_groupwise int32: [rows, n_groups]."""
-    lib = _lib.load()
     rows = enc_sample.shape[0] if enc_sample is not None else (done.shape[0] if done is not None else 1 << 30)
-    mg, ptrs, amax = tables.device_arrays()
-    d = _lib.RecDesc(None, None, addr(p_loc, f32), addr(p_scale, f32), int(rows), int(p_loc.numel()), addr(ptrs, torch.int64),
-                     addr(amax, f64), int(mg), None, 0.0, int(tables.K), addr(jobs.row, i32), addr(jobs.start, i32),
-                     addr(jobs.glen, i32), jobs.n)
-    z = torch.zeros(jobs.n, mg, device=p_loc.device, dtype=f64) if want_z else None
+    d, _keep = _rec_desc(None, None, p_loc, p_scale, tables, None, 0.0, jobs, rows)
+    z = torch.zeros(jobs.n, d.max_glen, device=p_loc.device, dtype=f64) if want_z else None
     for t_, shape in ((enc_sample, (rows, p_loc.numel())), (enc_mask, (rows, p_loc.numel())), (done, (rows, n_groups)),
                       (beta, (rows, n_groups)), (idx_groupwise, (rows, n_groups))):
         if t_ is not None and tuple(t_.shape) != tuple(shape):
             raise RcbError(f"rec_commit: state tensor of shape {tuple(t_.shape)}, expected {tuple(shape)}")
-    check(lib.rcb_rec_commit(C.byref(d), ptr(idx, i32), ptr(jobs.group, i32, True), int(n_groups), ptr(z, f64, True),
-                             ptr(enc_sample, f32, True), ptr(enc_mask, f32, True), ptr(done, torch.uint8, True),
-                             ptr(beta, f32, True), ptr(idx_groupwise, i32, True), stream_ptr()), "rcb_rec_commit")
+    _launch("rcb_rec_commit", C.byref(d), ptr(idx, i32), ptr(jobs.group, i32, True), int(n_groups), ptr(z, f64, True),
+            ptr(enc_sample, f32, True), ptr(enc_mask, f32, True), ptr(done, torch.uint8, True), ptr(beta, f32, True),
+            ptr(idx_groupwise, i32, True))
     return z
 
 
@@ -1055,9 +1018,6 @@ def rec_score_argmax(loc, scale, p_loc, p_scale, tables, gumbel, job_row, job_st
 # ----------------------------------------------------------------------------------------------
 # N1: phase-form upsampling stages (rcb_upconv_*)
 # ----------------------------------------------------------------------------------------------
-bf16 = torch.bfloat16
-
-
 def _xmode(x, preact):
     """0: bf16 activation, 1: fp32 pre-activation, 2: bf16 pre-activation"""
     if x.dtype == f32:
@@ -1068,12 +1028,11 @@ def _xmode(x, preact):
 def upconv_fwd(x, weff, bias, grid, cout, out_f32, preact=False, linear_bf16=False, pack=None):
     """x [B, g, g, 64] (fp32/bf16 pre-activation or bf16 activation) -> y [B, 2g, 2g, cout]: bf16 with LeakyReLU,
     fp32 linear (out_f32) or bf16 linear (linear_bf16)."""
-    lib = _lib.load()
     B = x.shape[0]
     y = torch.empty(B, 2 * grid, 2 * grid, cout, device=x.device, dtype=f32 if out_f32 else bf16)
     omode = 1 if out_f32 else (2 if linear_bf16 else 0)
-    check(lib.rcb_upconv_fwd(ptr(x), _xmode(x, preact), ptr(weff, f32), ptr(bias, f32), ptr(y), omode, B, grid,
-                             cout, ptr(pack, None, True), stream_ptr()), "rcb_upconv_fwd")
+    _launch("rcb_upconv_fwd", ptr(x), _xmode(x, preact), ptr(weff, f32), ptr(bias, f32), ptr(y), omode, B, grid, cout,
+            ptr(pack, None, True))
     return y
 
 
@@ -1085,21 +1044,25 @@ def upconv_dgrad(dy, weff, x, grid, cout, preact=False, want_dbias=False, pack=N
     part = None
     if want_dbias:
         part = torch.empty(int(lib.rcb_upconv_dgrad_partial_rows(B)), 64, device=x.device, dtype=f32)
-    check(lib.rcb_upconv_dgrad(ptr(dy), int(dy.dtype == f32), ptr(weff, f32), ptr(x), _xmode(x, preact), ptr(dx),
-                               ptr(part, f32, True), B, grid, cout, ptr(pack, None, True), stream_ptr()), "rcb_upconv_dgrad")
+    _launch("rcb_upconv_dgrad", ptr(dy), int(dy.dtype == f32), ptr(weff, f32), ptr(x), _xmode(x, preact), ptr(dx),
+            ptr(part, f32, True), B, grid, cout, ptr(pack, None, True))
     return (dx, part) if want_dbias else dx
+
+
+def _wgrad_buffers(lib, B, cout, device):
+    """-> (dWeff [2,2,64,2,2,cout] and dbias [cout] as views of one buffer, slab workspace, its size in floats)"""
+    buf = torch.empty(2 * 2 * 64 * 2 * 2 * cout + cout, device=device, dtype=f32)
+    n_ws = int(lib.rcb_upconv_wgrad_workspace(B, cout))
+    return buf[:-cout].view(2, 2, 64, 2, 2, cout), buf[-cout:], torch.empty(n_ws, device=device, dtype=f32), n_ws
 
 
 def upconv_wgrad(x, dy, grid, cout, preact=False):
     """-> (dWeff [2,2,64,2,2,cout], dbias [cout]) in one pass over x and dy (deterministic: no atomics)."""
     lib = _lib.load()
     B = x.shape[0]
-    buf = torch.empty(2 * 2 * 64 * 2 * 2 * cout + cout, device=x.device, dtype=f32)
-    dw, db = buf[:-cout].view(2, 2, 64, 2, 2, cout), buf[-cout:]
-    n_ws = int(lib.rcb_upconv_wgrad_workspace(B, cout))
-    ws = torch.empty(n_ws, device=x.device, dtype=f32)
-    check(lib.rcb_upconv_wgrad(ptr(x), _xmode(x, preact), ptr(dy), int(dy.dtype == f32), ptr(dw), ptr(db), B, grid,
-                               cout, ptr(ws), C.c_int64(n_ws), stream_ptr()), "rcb_upconv_wgrad")
+    dw, db, ws, n_ws = _wgrad_buffers(lib, B, cout, x.device)
+    _launch("rcb_upconv_wgrad", ptr(x), _xmode(x, preact), ptr(dy), int(dy.dtype == f32), ptr(dw), ptr(db), B, grid, cout,
+            ptr(ws), n_ws)
     return dw, db
 
 
@@ -1110,12 +1073,9 @@ def upconv_bwd_fused(dy, weff, x, grid, cout, pack=None):
         raise RcbError("upconv_bwd_fused: bf16 tensors expected")
     B = x.shape[0]
     dx = torch.empty_like(x)
-    buf = torch.empty(2 * 2 * 64 * 2 * 2 * cout + cout, device=x.device, dtype=f32)
-    dw, db = buf[:-cout].view(2, 2, 64, 2, 2, cout), buf[-cout:]
-    n_ws = int(lib.rcb_upconv_wgrad_workspace(B, cout))
-    ws = torch.empty(n_ws, device=x.device, dtype=f32)
-    check(lib.rcb_upconv_bwd_fused(ptr(dy), ptr(weff, f32), ptr(x), ptr(dx), ptr(dw), ptr(db), B, grid, cout, ptr(ws),
-                                   C.c_int64(n_ws), ptr(pack, None, True), stream_ptr()), "rcb_upconv_bwd_fused")
+    dw, db, ws, n_ws = _wgrad_buffers(lib, B, cout, x.device)
+    _launch("rcb_upconv_bwd_fused", ptr(dy), ptr(weff, f32), ptr(x), ptr(dx), ptr(dw), ptr(db), B, grid, cout, ptr(ws), n_ws,
+            ptr(pack, None, True))
     return dx, dw, db
 
 
@@ -1137,31 +1097,27 @@ def tile_gather(img, Ty, Tx, T, step, off, ring):
     """img [n,H,W,C] -> tiles [n*Ty*Tx, T, T, C] (rcb_tile_gather)"""
     n, H, W, Cc = _tile_img(img)
     tiles = torch.empty(n * Ty * Tx, T, T, Cc, device=img.device, dtype=bf16)
-    check(_lib.load().rcb_tile_gather(ptr(img), ptr(tiles), n, H, W, Cc, Ty, Tx, T, step, off, ring, stream_ptr()), "rcb_tile_gather")
+    _launch("rcb_tile_gather", ptr(img), ptr(tiles), n, H, W, Cc, Ty, Tx, T, step, off, ring)
     return tiles
 
 
-def _tile_out(tiles, n, H, W, Ty, Tx):
+def _tile_to_img(entry, tiles, n, H, W, Ty, Tx, off):
     if tiles.dtype != bf16 or not tiles.is_cuda or tiles.dim() != 4 or not tiles.is_contiguous() or tiles.shape[0] != n * Ty * Tx \
             or tiles.shape[1] != tiles.shape[2] or tiles.shape[-1] % 8:
         raise RcbError("tiles: contiguous bf16 GPU tiles [n*Ty*Tx, T, T, C] expected")
-    return torch.empty(n, H, W, tiles.shape[-1], device=tiles.device, dtype=bf16)
+    img = torch.empty(n, H, W, tiles.shape[-1], device=tiles.device, dtype=bf16)
+    _launch(entry, ptr(tiles), ptr(img), n, H, W, tiles.shape[-1], Ty, Tx, tiles.shape[1], off)
+    return img
 
 
 def tile_crop(tiles, n, H, W, Ty, Tx, off):
     """tiles [n*Ty*Tx, T, T, C] -> img [n,H,W,C] from the inner T-2 rows / columns of every tile (rcb_tile_crop)"""
-    img = _tile_out(tiles, n, H, W, Ty, Tx)
-    check(_lib.load().rcb_tile_crop(ptr(tiles), ptr(img), n, H, W, tiles.shape[-1], Ty, Tx, tiles.shape[1], off, stream_ptr()),
-          "rcb_tile_crop")
-    return img
+    return _tile_to_img("rcb_tile_crop", tiles, n, H, W, Ty, Tx, off)
 
 
 def tile_fold(tiles, n, H, W, Ty, Tx, off):
     """tiles [n*Ty*Tx, T, T, C] -> img [n,H,W,C], overlapping tile borders summed (rcb_tile_fold)"""
-    img = _tile_out(tiles, n, H, W, Ty, Tx)
-    check(_lib.load().rcb_tile_fold(ptr(tiles), ptr(img), n, H, W, tiles.shape[-1], Ty, Tx, tiles.shape[1], off, stream_ptr()),
-          "rcb_tile_fold")
-    return img
+    return _tile_to_img("rcb_tile_fold", tiles, n, H, W, Ty, Tx, off)
 
 
 def _win_geo(shape):
@@ -1178,8 +1134,7 @@ def window_gather(x):
         raise RcbError("window_gather: contiguous bf16 GPU tensor expected")
     nd, g = _win_geo(x.shape)
     cols = torch.empty(x.shape[0] * g[0] * g[1] * g[2], 3 ** nd * x.shape[-1], device=x.device, dtype=bf16)
-    check(_lib.load().rcb_window_gather(ptr(x), ptr(cols), x.shape[0], g[0], g[1], g[2], x.shape[-1], nd, stream_ptr()),
-          "rcb_window_gather")
+    _launch("rcb_window_gather", ptr(x), ptr(cols), x.shape[0], g[0], g[1], g[2], x.shape[-1], nd)
     return cols
 
 
@@ -1190,8 +1145,7 @@ def window_fold(dcols, shape):
             tuple(dcols.shape) != (shape[0] * g[0] * g[1] * g[2], 3 ** nd * shape[-1]):
         raise RcbError("window_fold: contiguous bf16 GPU matrix [B*prod(g), 3^d*C] expected")
     dx = torch.empty(tuple(shape), device=dcols.device, dtype=bf16)
-    check(_lib.load().rcb_window_fold(ptr(dcols), ptr(dx), shape[0], g[0], g[1], g[2], shape[-1], nd, stream_ptr()),
-          "rcb_window_fold")
+    _launch("rcb_window_fold", ptr(dcols), ptr(dx), shape[0], g[0], g[1], g[2], shape[-1], nd)
     return dx
 
 
@@ -1204,8 +1158,7 @@ def phase_bigweight(W, factors, k, pad, dtype=bf16):
     wt = W.permute(*range(2, 2 + nd), 1, 0).contiguous()                       # [k^d, Cin, Cout]
     f = (C.c_int32 * 3)(*[int(v) for v in factors], *([0] * (3 - nd)))
     big = torch.empty(3 ** nd * cin, int(np.prod(factors)) * cout, device=W.device, dtype=dtype)
-    check(_lib.load().rcb_phase_bigweight(ptr(wt), ptr(big, None, True), int(dtype == bf16), nd, f, int(k), int(pad), cin, cout,
-                                          stream_ptr()), "rcb_phase_bigweight")
+    _launch("rcb_phase_bigweight", ptr(wt), ptr(big, None, True), int(dtype == bf16), nd, f, int(k), int(pad), cin, cout)
     return big
 
 
@@ -1217,8 +1170,8 @@ def phase_bigweight_grad(dbig, w_shape, factors, k, pad):
         raise RcbError("phase_bigweight_grad: contiguous [3^d * Cin, prod(f) * Cout] GPU matrix expected")
     f = (C.c_int32 * 3)(*[int(v) for v in factors], *([0] * (3 - nd)))
     dwt = torch.empty(*([int(k)] * nd), cin, cout, device=dbig.device, dtype=f32)
-    check(_lib.load().rcb_phase_bigweight_grad(ptr(dbig, None, True), int(dbig.dtype == bf16), ptr(dwt), nd, f, int(k), int(pad),
-                                               cin, cout, stream_ptr()), "rcb_phase_bigweight_grad")
+    _launch("rcb_phase_bigweight_grad", ptr(dbig, None, True), int(dbig.dtype == bf16), ptr(dwt), nd, f, int(k), int(pad),
+            cin, cout)
     return dwt.permute(nd + 1, nd, *range(nd)).contiguous()
 
 
@@ -1237,8 +1190,8 @@ def stage1_1d_fwd(x, wbig, bias):
     if tuple(wbig.shape) != (384, 256) or wbig.dtype != bf16 or not wbig.is_contiguous() or bias.numel() != 64:
         raise RcbError("stage1_1d_fwd: wbig bf16 [384, 256] and bias [64] expected")
     x1 = torch.empty(x.shape[0], 4 * x.shape[1], 64, device=x.device, dtype=bf16)
-    check(_lib.load().rcb_stage1_1d_fwd(ptr(x, f32), ptr(wbig), ptr(bias.detach().float().contiguous(), f32), ptr(x1), x.shape[0], x.shape[1],
-                                        stream_ptr()), "rcb_stage1_1d_fwd")
+    _launch("rcb_stage1_1d_fwd", ptr(x, f32), ptr(wbig), ptr(bias.detach().float().contiguous(), f32), ptr(x1),
+            x.shape[0], x.shape[1])
     return x1
 
 
@@ -1264,8 +1217,7 @@ def stage1_1d_dgrad(dz, wbig):
     if dz.dim() != 3 or dz.shape[-1] != 64 or dz.shape[1] % 4 or dz.dtype != bf16 or not dz.is_cuda or not dz.is_contiguous():
         raise RcbError("stage1_1d_dgrad: contiguous bf16 GPU tensor [B, 4 g, 64] expected")
     dx = torch.empty(dz.shape[0], dz.shape[1] // 4, 128, device=dz.device, dtype=f32)
-    check(_lib.load().rcb_stage1_1d_dgrad(ptr(dz), ptr(wbig), ptr(dx, f32), dz.shape[0], dz.shape[1] // 4, stream_ptr()),
-          "rcb_stage1_1d_dgrad")
+    _launch("rcb_stage1_1d_dgrad", ptr(dz), ptr(wbig), ptr(dx, f32), dz.shape[0], dz.shape[1] // 4)
     return dx
 
 
@@ -1279,8 +1231,7 @@ def stage1_1d_wgrad(x, dz):
     ws = _scratch("stage1_1d_wgrad", n_ws, x.device)
     dwbig = torch.empty(384, 256, device=x.device, dtype=f32)
     db = torch.empty(64, device=x.device, dtype=f32)
-    check(lib.rcb_stage1_1d_wgrad(ptr(x, f32), ptr(dz), ptr(dwbig, f32), ptr(db, f32), ptr(ws, f32), C.c_int64(n_ws), x.shape[0],
-                                  x.shape[1], stream_ptr()), "rcb_stage1_1d_wgrad")
+    _launch("rcb_stage1_1d_wgrad", ptr(x, f32), ptr(dz), ptr(dwbig, f32), ptr(db, f32), ptr(ws, f32), n_ws, x.shape[0], x.shape[1])
     return dwbig, db
 
 
@@ -1304,8 +1255,7 @@ def phaseconv_pack(W, want_fwd=True, want_dgrad=True):
     for which, want in ((0, want_fwd), (1, want_dgrad)):
         n = int(lib.rcb_phaseconv_pack_uint4(nd, cout, which))
         out.append(torch.empty(n * 16, device=W.device, dtype=torch.uint8) if want else None)
-    check(lib.rcb_phaseconv_pack(ptr(W.detach().contiguous(), f32), nd, cout, ptr(out[0], None, True), ptr(out[1], None, True),
-                                 stream_ptr()), "rcb_phaseconv_pack")
+    _launch("rcb_phaseconv_pack", ptr(W.detach().contiguous(), f32), nd, cout, ptr(out[0], None, True), ptr(out[1], None, True))
     return out[0], out[1]
 
 
@@ -1315,8 +1265,8 @@ def phaseconv_fwd(x, frags, bias, cout, leaky_out):
         raise RcbError("phaseconv_fwd: contiguous bf16 input expected")
     nd, g = _pc_geo(x.shape)
     y = torch.empty([x.shape[0]] + [2 * v for v in x.shape[1:-1]] + [cout], device=x.device, dtype=bf16)
-    check(_lib.load().rcb_phaseconv_fwd(ptr(x), ptr(frags), ptr(bias.detach().contiguous(), f32), ptr(y), x.shape[0], g[0], g[1], g[2],
-                                        nd, cout, int(bool(leaky_out)), stream_ptr()), "rcb_phaseconv_fwd")
+    _launch("rcb_phaseconv_fwd", ptr(x), ptr(frags), ptr(bias.detach().contiguous(), f32), ptr(y), x.shape[0], g[0], g[1], g[2], nd,
+            cout, int(bool(leaky_out)))
     return y
 
 
@@ -1328,8 +1278,7 @@ def phaseconv_dgrad(dy, frags, x_act):
     if list(dy.shape[1:-1]) != [2 * v for v in x_act.shape[1:-1]] or dy.shape[0] != x_act.shape[0]:
         raise RcbError("phaseconv_dgrad: dy grid must be twice the input grid")
     dx = torch.empty_like(x_act)
-    check(_lib.load().rcb_phaseconv_dgrad(ptr(dy), ptr(frags), ptr(x_act), ptr(dx), x_act.shape[0], g[0], g[1], g[2], nd, dy.shape[-1],
-                                          stream_ptr()), "rcb_phaseconv_dgrad")
+    _launch("rcb_phaseconv_dgrad", ptr(dy), ptr(frags), ptr(x_act), ptr(dx), x_act.shape[0], g[0], g[1], g[2], nd, dy.shape[-1])
     return dx
 
 
@@ -1346,37 +1295,38 @@ def phaseconv_wgrad(x_act, dy):
     ws = _scratch("phaseconv_wgrad_%d_%d" % (nd, cout), n_ws, dy.device)
     dW = torch.empty([cout, 64] + [3] * nd, device=dy.device, dtype=f32)
     db = torch.empty(cout, device=dy.device, dtype=f32)
-    check(lib.rcb_phaseconv_wgrad(ptr(x_act), ptr(dy), ptr(dW), ptr(db), ptr(ws), C.c_int64(n_ws), x_act.shape[0], g[0], g[1], g[2],
-                                  nd, cout, stream_ptr()), "rcb_phaseconv_wgrad")
+    _launch("rcb_phaseconv_wgrad", ptr(x_act), ptr(dy), ptr(dW), ptr(db), ptr(ws), n_ws, x_act.shape[0], g[0], g[1], g[2], nd, cout)
     return dW, db
 
 
 UPCONV_PACK_UINT4 = 22528
 
 
-def upconv_weff_build(W1, b1, W2, W3, bf16_out):
-    """conv weights of the CIFAR-geometry upsampling net -> (Weff1 [512,4096], b1rep [4096], Weff2, Weff3, pack) where
-    pack holds the stage-2/3 effective weights as pre-ordered bf16 MFMA fragments for upconv_fwd / upconv_dgrad."""
-    lib = _lib.load()
-    dev = W1.device
+def _weff_build_args(W1, b1, W2, W3, bf16_out, who):
+    """-> ((Weff1, b1rep, Weff2, Weff3, pack) to be written, the arguments of rcb_upconv_weff_build up to the stream)"""
     if (tuple(W1.shape), tuple(W2.shape), tuple(W3.shape)) != ((64, 128, 5, 5), (64, 64, 3, 3), (16, 64, 3, 3)):
-        raise RcbError("upconv_weff_build: conv weight shapes of the CIFAR upsampling net expected")
-    dt = bf16 if bf16_out else f32
+        raise RcbError(f"{who}: conv weight shapes of the CIFAR upsampling net expected")
+    dev, dt = W1.device, (bf16 if bf16_out else f32)
     weff1 = torch.empty(512, 4096, device=dev, dtype=dt)
     b1rep = torch.empty(4096, device=dev, dtype=dt)
     weff2 = torch.empty(2, 2, 64, 2, 2, 64, device=dev, dtype=f32)
     weff3 = torch.empty(2, 2, 64, 2, 2, 16, device=dev, dtype=f32)
     pack = torch.empty(UPCONV_PACK_UINT4 * 16, device=dev, dtype=torch.uint8)      # bf16 MFMA fragments (include/rcb.h)
-    check(lib.rcb_upconv_weff_build(ptr(W1.detach(), f32), ptr(b1.detach(), f32), ptr(W2.detach(), f32),
-                                    ptr(W3.detach(), f32), ptr(weff1), ptr(b1rep), int(bool(bf16_out)), ptr(weff2),
-                                    ptr(weff3), ptr(pack), stream_ptr()), "rcb_upconv_weff_build")
-    return weff1, b1rep, weff2, weff3, pack
+    return (weff1, b1rep, weff2, weff3, pack), (*(ptr(w.detach(), f32) for w in (W1, b1, W2, W3)), ptr(weff1), ptr(b1rep),
+                                                int(bool(bf16_out)), ptr(weff2), ptr(weff3), ptr(pack))
+
+
+def upconv_weff_build(W1, b1, W2, W3, bf16_out):
+    """conv weights of the CIFAR-geometry upsampling net -> (Weff1 [512,4096], b1rep [4096], Weff2, Weff3, pack) where
+    pack holds the stage-2/3 effective weights as pre-ordered bf16 MFMA fragments for upconv_fwd / upconv_dgrad."""
+    out, build = _weff_build_args(W1, b1, W2, W3, bf16_out, "upconv_weff_build")
+    _launch("rcb_upconv_weff_build", *build)
+    return out
 
 
 def upconv_weff_grad(dweff1, dweff2, dweff3, db1_partial=None):
     """gradients of the effective weights -> (dW1 [64,128,5,5], dW2 [64,64,3,3], dW3 [16,64,3,3]) and, given the
     per-workgroup partials of upconv_dgrad(want_dbias=True), the stage-1 bias gradient db1 [64]."""
-    lib = _lib.load()
     dev = dweff1.device
     if dweff1.numel() != 512 * 4096 or dweff2.numel() != 65536 or dweff3.numel() != 16384:
         raise RcbError("upconv_weff_grad: shape mismatch")
@@ -1384,10 +1334,8 @@ def upconv_weff_grad(dweff1, dweff2, dweff3, db1_partial=None):
     dW2 = torch.empty(64, 64, 3, 3, device=dev, dtype=f32)
     dW3 = torch.empty(16, 64, 3, 3, device=dev, dtype=f32)
     db1 = torch.empty(64, device=dev, dtype=f32) if db1_partial is not None else None
-    check(lib.rcb_upconv_weff_grad(ptr(dweff1), int(dweff1.dtype == bf16), ptr(dweff2, f32), ptr(dweff3, f32), ptr(dW1),
-                                   ptr(dW2), ptr(dW3), ptr(db1_partial, f32, True),
-                                   0 if db1_partial is None else db1_partial.shape[0], ptr(db1, f32, True), stream_ptr()),
-          "rcb_upconv_weff_grad")
+    _launch("rcb_upconv_weff_grad", ptr(dweff1), int(dweff1.dtype == bf16), ptr(dweff2, f32), ptr(dweff3, f32), ptr(dW1), ptr(dW2),
+            ptr(dW3), ptr(db1_partial, f32, True), 0 if db1_partial is None else db1_partial.shape[0], ptr(db1, f32, True))
     return (dW1, dW2, dW3) if db1_partial is None else (dW1, dW2, dW3, db1)
 
 
@@ -1438,23 +1386,22 @@ class ATransform:
 
     def prepare(self, A):
         arr = self.mats_arg(A)
-        check(_lib.load().rcb_atrans_pack(arr, len(self.sizes), self._sizes_c, ptr(self.packed), int(self.terms == 3), stream_ptr()),
-              "rcb_atrans_pack")
+        _launch("rcb_atrans_pack", arr, len(self.sizes), self._sizes_c, ptr(self.packed), int(self.terms == 3))
 
     def _plan(self, rows):
         pl = self._plans.get(rows)
         if pl is None:
             lib = _lib.load()
-            need = lib.rcb_atrans_plan(C.c_int64(rows), len(self.sizes), self._sizes_c, int(self.n_cu), None, 0)   # size query
+            need = lib.rcb_atrans_plan(rows, len(self.sizes), self._sizes_c, int(self.n_cu), None, 0)   # size query
             if need <= 0:
                 check(need or -1, "rcb_atrans_plan")
             buf = (C.c_int32 * need)()
-            n = lib.rcb_atrans_plan(C.c_int64(rows), len(self.sizes), self._sizes_c, int(self.n_cu), buf, need)
+            n = lib.rcb_atrans_plan(rows, len(self.sizes), self._sizes_c, int(self.n_cu), buf, need)
             if n != need:
                 check(n if n < 0 else -1, "rcb_atrans_plan")
             host = torch.frombuffer(buf, dtype=torch.int32, count=n).clone()
             head = (C.c_int32 * 12)(*[int(v) for v in host[:12]])
-            nws = int(lib.rcb_atrans_workspace_floats(C.c_int64(rows), len(self.sizes), self._sizes_c, head))
+            nws = int(lib.rcb_atrans_workspace_floats(rows, len(self.sizes), self._sizes_c, head))
             pl = (host.to(self.device), head, nws)
             self._plans[rows] = pl
         return pl
@@ -1473,12 +1420,11 @@ class ATransform:
         plan, head, nws = self._plan(rows)
         ws = torch.empty(nws, device=self.device, dtype=f32) if nws else None      # (few rows: slabs of the K-split launch)
         if planes:
-            xa = (C.c_void_p(0), C.c_int64(0), C.c_void_p(x.buf[0].data_ptr()), C.c_void_p(x.buf[1].data_ptr()), C.c_int64(x.ld))
+            xa = (None, 0, x.buf[0].data_ptr(), x.buf[1].data_ptr(), x.ld)
         else:
-            xa = (C.c_void_p(x.data_ptr()), C.c_int64(x.stride(0)), C.c_void_p(0), C.c_void_p(0), C.c_int64(0))
-        check(_lib.load().rcb_atrans_apply(*xa, C.c_void_p(out.data_ptr()), C.c_int64(out.stride(0)), C.c_int64(rows),
-                                          len(self.sizes), self._sizes_c, ptr(self.packed), int(transpose), int(terms),
-                                          ptr(plan), head, ptr(ws, f32, True), stream_ptr()), "rcb_atrans_apply")
+            xa = (x.data_ptr(), x.stride(0), None, None, 0)
+        _launch("rcb_atrans_apply", *xa, out.data_ptr(), out.stride(0), rows, len(self.sizes), self._sizes_c, ptr(self.packed),
+                int(transpose), int(terms), ptr(plan), head, ptr(ws, f32, True))
         return out
 
     def forward(self, h_w, out):
@@ -1538,11 +1484,9 @@ class ATransform:
                 g = torch.empty(n, n, device=self.device, dtype=f32)
                 def operand(t, is_planes):
                     if is_planes:
-                        return (C.c_void_p(0), C.c_void_p(t.buf[0, :, lo:hi].data_ptr()), C.c_void_p(t.buf[1, :, lo:hi].data_ptr()),
-                                C.c_int64(t.ld))
-                    return (C.c_void_p(t[:, lo:hi].data_ptr()), C.c_void_p(0), C.c_void_p(0), C.c_int64(t.stride(0)))
-                check(lib.rcb_atrans_wgrad_narrow(*operand(h_w, hp), *operand(dw, dp), C.c_int64(rows), n, ptr(g), ptr(ws), slabs,
-                                                  stream_ptr()), "rcb_atrans_wgrad_narrow")
+                        return None, t.buf[0, :, lo:hi].data_ptr(), t.buf[1, :, lo:hi].data_ptr(), t.ld
+                    return t[:, lo:hi].data_ptr(), None, None, t.stride(0)
+                _launch("rcb_atrans_wgrad_narrow", *operand(h_w, hp), *operand(dw, dp), rows, n, ptr(g), ptr(ws), slabs)
                 out[i] = g
             else:
                 hf = h_w.float() if hp else h_w

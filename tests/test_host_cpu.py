@@ -34,6 +34,194 @@ def test_descriptor_mirrors_have_the_library_sizes():
     assert lib.rcb_struct_bytes(99) == -1
 
 
+# ---------------------------------------------------------------------------------------------------
+# the binding against the text of include/rcb.h: prototypes (_lib.PROTOTYPES) and structure fields (_lib._MIRRORS)
+# ---------------------------------------------------------------------------------------------------
+_C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+              "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double, "rcb_stream_t": ctypes.c_void_p}
+_C_STRUCTS = {"rcb_siren_desc": _lib.SirenDesc, "rcb_level": _lib.Level, "rcb_level_bwd": _lib.LevelBwd,
+              "rcb_adam_cfg": _lib.AdamCfg, "rcb_adam_tensor": _lib.AdamTensor, "rcb_rec_desc": _lib.RecDesc}
+
+
+def _header():
+    return open(os.path.join(ROOT, "include", "rcb.h")).read()
+
+
+def _code_of(hdr):
+    """the header without comments and preprocessor lines"""
+    return re.sub(r"(?m)^\s*#.*$", "", re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S))
+
+
+def _ctype_of(ctype, in_struct):
+    """the ctypes type the binding must use for a C type as the header spells it: every data pointer is c_void_p; a pointer
+    to a descriptor as a PARAMETER is POINTER(mirror), const char* is c_char_p"""
+    t = re.sub(r"\bconst\b", " ", ctype).replace("*", " * ").split()
+    if "*" in t:
+        if not in_struct and t == [t[0], "*"] and t[0] in _C_STRUCTS:
+            return ctypes.POINTER(_C_STRUCTS[t[0]])
+        return ctypes.c_char_p if t == ["char", "*"] else ctypes.c_void_p
+    assert len(t) == 1 and t[0] in _C_SCALARS, f"C type {ctype!r} has no entry in the test's map"
+    return _C_SCALARS[t[0]]
+
+
+def _parse_prototypes(hdr):
+    """[(name, return C type, [parameter C types])] of every rcb_*(...) declaration, in header order"""
+    code = re.sub(r"typedef\b[^;{]*(\{.*?\})?[^;{]*;", "", _code_of(hdr), flags=re.S)           # structures, rcb_stream_t
+    code = re.sub(r'extern\s+"C"\s*\{|\}', "", code)
+    out = []
+    for decl in (d.strip() for d in code.split(";")):
+        if not decl:
+            continue
+        m = re.fullmatch(r"(.+?)\b(rcb_[a-z0-9_]+)\s*\((.*)\)", decl, flags=re.S)
+        assert m, f"cannot parse the declaration {decl!r}"
+        params = [] if m.group(3).strip() == "void" else [p.strip() for p in m.group(3).split(",")]
+        for p_ in params:
+            assert re.fullmatch(r".*[\s*]\w+", p_, flags=re.S), f"{m.group(2)}: parameter {p_!r} has no name"
+        out.append((m.group(2), m.group(1).strip(), [re.sub(r"\w+$", "", p_).strip() for p_ in params]))
+    return out
+
+
+def _parse_structs(hdr):
+    """{structure name: [(field, C type, array length or None)]} of the typedef struct { ... } bodies; `int32_t rows, cols;`
+    declares two fields, `int32_t v[3];` an array"""
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(rcb_\w+)\s*;", _code_of(hdr), flags=re.S):
+        fields = []
+        for decl in (d.strip() for d in body.split(";")):
+            if not decl:
+                continue
+            m = re.fullmatch(r"(.*?[\s*])(\w+(?:\[\d+\])?(?:\s*,\s*\w+(?:\[\d+\])?)*)", decl, flags=re.S)
+            assert m, f"{name}: cannot parse the member declaration {decl!r}"
+            for item in m.group(2).split(","):
+                f = re.fullmatch(r"\s*(\w+)(?:\[(\d+)\])?\s*", item)
+                fields.append((f.group(1), m.group(1).strip(), int(f.group(2)) if f.group(2) else None))
+        out[name] = fields
+    return out
+
+
+def _prototype_mismatches(hdr, table):
+    """what differs between the header's declarations and a name -> (restype, [argtypes]) table, each entry naming its function"""
+    bad, declared = [], _parse_prototypes(hdr)
+    names = [d[0] for d in declared]
+    bad += [f"{n}: declared {names.count(n)} times" for n in sorted(set(names)) if names.count(n) > 1]
+    bad += [f"{n}: declared in the header, not in the table" for n in names if n not in table]
+    bad += [f"{n}: in the table, not declared in the header" for n in table if n not in names]
+    if not bad and list(table) != names:
+        bad.append("the table is not in header order: first difference at "
+                   + next(a for a, b in zip(table, names) if a != b))
+    for name, ret, params in declared:
+        if name not in table:
+            continue
+        restype, argtypes = table[name]
+        if restype is not _ctype_of(ret, False):
+            bad.append(f"{name}: returns {ret}, the table says {restype.__name__}")
+        if len(argtypes) != len(params):
+            bad.append(f"{name}: {len(params)} parameters declared, {len(argtypes)} in the table")
+            continue
+        bad += [f"{name}: parameter {i} is {c}, the table says {a.__name__}"
+                for i, (c, a) in enumerate(zip(params, argtypes)) if a is not _ctype_of(c, False)]
+    return bad
+
+
+def _struct_mismatches(hdr, mirrors):
+    """what differs between the header's structures and {structure name: ctypes mirror}, each entry naming structure and field"""
+    bad, structs = [], _parse_structs(hdr)
+    if sorted(structs) != sorted(mirrors):
+        bad.append(f"structures declared {sorted(structs)}, mirrored {sorted(mirrors)}")
+    for name in sorted(set(structs) & set(mirrors)):
+        want = [(f, _ctype_of(c, True), n) for f, c, n in structs[name]]
+        have = [(f, getattr(t, "_type_", t), t._length_) if issubclass(t, ctypes.Array) else (f, t, None)
+                for f, t in mirrors[name]._fields_]
+        if [w[0] for w in want] != [h[0] for h in have]:
+            k = next((i for i, (w, h) in enumerate(zip(want, have)) if w[0] != h[0]), min(len(want), len(have)))
+            bad.append(f"{name}: field {k} is {want[k][0] if k < len(want) else None} in the header, "
+                       f"{have[k][0] if k < len(have) else None} in the mirror ({len(want)} / {len(have)} fields)")
+            continue
+        bad += [f"{name}.{w[0]}: {w[1].__name__}{[w[2]] if w[2] else ''} in the header, {h[1].__name__}{[h[2]] if h[2] else ''} "
+                "in the mirror" for w, h in zip(want, have) if w[1:] != h[1:]]
+    return bad
+
+
+def test_prototype_table_matches_the_header():
+    """every rcb_*(...) declaration of include/rcb.h -- as many as the export test finds names -- has its return type and its
+    parameter types, one by one and in header order, in _lib.PROTOTYPES, and the table has nothing else"""
+    hdr = _header()
+    declared = _parse_prototypes(hdr)
+    assert len(declared) == len(set(re.findall(r"\b(rcb_[a-z0-9_]+)\s*\(", hdr))) == len(_lib.PROTOTYPES) >= 61
+    assert _lib.EXPORTS == [d[0] for d in declared]
+    assert _prototype_mismatches(hdr, _lib.PROTOTYPES) == []
+
+
+def test_descriptor_mirrors_match_the_header_fields():
+    """every ctypes mirror has the fields of its structure in include/rcb.h: names, order and types, comma declarators and
+    arrays included; _lib._MIRRORS numbers them as the header's RCB_STRUCT_* selectors do"""
+    hdr = _header()
+    parsed = _parse_structs(hdr)
+    assert len(parsed["rcb_level"]) == 13 and ("pe_patch_nums", "int32_t", 3) in parsed["rcb_siren_desc"]
+    assert _struct_mismatches(hdr, _C_STRUCTS) == []
+    selectors = {"rcb_" + n.lower(): int(v) for n, v in re.findall(r"#define RCB_STRUCT_(\w+) (\d+)", hdr)}
+    assert {n: _lib._MIRRORS[v] for n, v in selectors.items()} == _C_STRUCTS
+
+
+def _edited(hdr, old, new):
+    assert hdr.count(old) == 1, old
+    return hdr.replace(old, new)
+
+
+def test_header_checks_report_drift():
+    """the two comparisons fail, naming the function or the field, on copies of the header with one edit each"""
+    hdr = _header()
+
+    def protos(old, new):
+        return _prototype_mismatches(_edited(hdr, old, new), _lib.PROTOTYPES)
+
+    def structs(old, new):
+        return _struct_mismatches(_edited(hdr, old, new), _C_STRUCTS)
+
+    bad = protos("rcb_struct_bytes(int32_t which)", "rcb_struct_bytes(int64_t which)")            # a parameter widened
+    assert len(bad) == 1 and bad[0].startswith("rcb_struct_bytes: parameter 0 is int64_t")
+    bad = protos("float* scale, int64_t n, rcb_stream_t stream)", "float* scale, rcb_stream_t stream)")     # a parameter removed
+    assert len(bad) == 1 and bad[0].startswith("rcb_softplus_scale: 3 parameters declared, 4 in the table")
+    bad = protos("int rcb_version(void);", "int rcb_version(void);\nint rcb_new_entry(const float* x,\n  int32_t n);")
+    assert bad == ["rcb_new_entry: declared in the header, not in the table"]                    # a declaration added
+    bad = protos("int64_t rcb_stage1_1d_wgrad_workspace(void)", "int rcb_stage1_1d_wgrad_workspace(void)")
+    assert len(bad) == 1 and bad[0].startswith("rcb_stage1_1d_wgrad_workspace: returns int,")    # a return type narrowed
+    swapped = _edited(_edited(_edited(hdr, "float* g_loc;", "float* @;"), "float* g_log_scale;", "float* g_loc;"),
+                      "float* @;", "float* g_log_scale;")                                        # two same-size fields swapped
+    bad = _struct_mismatches(swapped, _C_STRUCTS)
+    assert len(bad) == 1 and bad[0].startswith("rcb_level_bwd: field 20 is g_log_scale in the header, g_loc in the mirror")
+    bad = structs("int32_t max_glen;", "uint32_t max_glen;")                                     # a field's signedness changed
+    assert bad == ["rcb_rec_desc.max_glen: c_uint in the header, c_int in the mirror"]
+    bad = structs("int32_t rows, cols, cols_out;", "int32_t rows, cols;  int64_t cols_out;")     # an int32 pair's neighbour widened
+    assert len(bad) == 1 and bad[0].startswith("rcb_level.cols_out: c_long in the header")
+    bad = structs("int32_t pe_patch_nums[3];", "int32_t pe_patch_nums[4];")                      # an array grown
+    assert len(bad) == 1 and bad[0].startswith("rcb_siren_desc.pe_patch_nums:")
+    table = dict(_lib.PROTOTYPES, rcb_not_in_header=(ctypes.c_int, []))
+    assert _prototype_mismatches(hdr, table) == ["rcb_not_in_header: in the table, not declared in the header"]
+
+
+def test_argument_classes_are_checked_at_the_call():
+    """with the prototypes applied ctypes refuses, before the library is entered, an argument of the wrong class: a float or
+    a pointer object for an integer parameter, another structure (or a plain integer) for a descriptor pointer, and too few
+    arguments.  It does NOT refuse extra trailing arguments, nor an integer outside the parameter's range (the value is
+    truncated to the declared width without a word): the wrappers in ops.py stay responsible for counts and ranges."""
+    lib = _lib.load()
+    for wrong in (1.0, ctypes.c_void_p(1)):
+        with pytest.raises(ctypes.ArgumentError):
+            lib.rcb_struct_bytes(wrong)
+        with pytest.raises(ctypes.ArgumentError):
+            lib.rcb_rec_workspace_bytes(4, wrong, 64)
+    for wrong in (ctypes.byref(_lib.Level()), _lib.AdamCfg(), 4096):
+        with pytest.raises(ctypes.ArgumentError):
+            lib.rcb_step_tail_eligible(wrong)
+    with pytest.raises(TypeError):
+        lib.rcb_struct_bytes()
+    with pytest.raises(TypeError):
+        lib.rcb_rec_workspace_bytes(4, 3)
+    assert lib.rcb_struct_bytes(99) == -1 and lib.rcb_struct_bytes(0) == ctypes.sizeof(_lib.SirenDesc)
+    assert lib.rcb_rec_workspace_bytes(4, 3, 64) > 0 and isinstance(lib.rcb_last_error_string(), bytes)
+
+
 def test_product_refuses_cpu_tensors():
     with pytest.raises(_lib.RcbError):
         ops.softplus_scale(torch.zeros(4))
