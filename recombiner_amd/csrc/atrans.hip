@@ -10,10 +10,15 @@
 // contraction index contiguous (forward: A^T, data gradient: A), zero-padded to multiples of 32.
 //
 // Decomposition (forward / data gradient).  The output of layer l is [rows, L_l]; rows are cut into 256-row tiles, the
-// columns of all layers, flattened into 32-column blocks, into R contiguous runs per row tile of (nearly) equal cost, so
-// that rows/256 * R workgroups fill the chip once (4096 rows: 16 * 16 = 256 workgroups of 6-7 blocks) -- the 33 blocks
-// of a 1056-wide layer divide by nothing useful, and a tile grid per layer leaves 1/8 of a wave of tiles over.  A run is
-// cut at layer boundaries into segments of <= 7 blocks (host side: rcb_atrans_plan).  Per segment a 512-thread workgroup
+// columns of all layers, flattened into 32-column blocks, into at most R contiguous runs per row tile, so that at most
+// rows/256 * R workgroups fill the chip once -- the 33 blocks of a 1056-wide layer divide by nothing useful, and a tile
+// grid per layer leaves 1/8 of a wave of tiles over.  A run is cut at layer boundaries into segments of <= 7 blocks, and
+// every segment walks its layer's whole contraction, whatever its width: the host planner (rcb_atrans_plan) prices a
+// segment chunks * (PLAN_F + blocks) + PLAN_E and keeps the most expensive run as cheap as it can, so a run holds
+// pieces of two layers only where nothing else fits (4096 rows of the headline's [1056, 1056, 1056, 99] on 256 CUs:
+// 16 * 16 = 256 workgroups, per wide layer one-segment runs of 7, 7, 7, 6, 6 blocks, the 99-wide layer a run of its own;
+// the greedy equal-cost runs before that were 15 per row tile = 240 workgroups, two of them over a layer boundary with
+// 66 chunk iterations instead of 33).  Per segment a 512-thread workgroup
 // walks the contraction in 32-deep chunks through a ring of three LDS stages filled by LDS-DMA (global_load_lds_dwordx4:
 // no staging registers, no ds_write): the x rows as they are (fp32, 128-byte rows; every wave fetches the 32 rows it
 // multiplies), the mapping rows as bf16 (64-byte rows); the 16-byte chunk index is XORed with row bits ON THE SOURCE
@@ -44,7 +49,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define ATRANS_DIAG 0
 #endif
 #ifndef ATRANS_STAMPS
-#define ATRANS_STAMPS 0      // diagnostic build: s_memtime stamps of workgroup 0 (rcb_debug_atrans_stamps)
+// diagnostic build: s_memtime stamps of workgroup 0's chunk loop (rcb_debug_atrans_stamps) and the begin / end of EVERY
+// workgroup of the last launch (rcb_debug_atrans_wg_stamps; tools/atrans_wg_stamps.py)
+#define ATRANS_STAMPS 0
 #endif
 #ifndef ATRANS_SPREAD_PIN
 #define ATRANS_SPREAD_PIN 1
@@ -74,6 +81,8 @@ template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 #if ATRANS_STAMPS
 __device__ unsigned long long g_stamps[8][40][6];
+constexpr int WG_STAMPS = 8192;
+__device__ unsigned long long g_wg_stamps[WG_STAMPS][4];      // per logical workgroup: s_memrealtime begin, end; s_memtime begin, end
 #define STAMP(it, pt)                                                                 \
   do {                                                                               \
     if (blockIdx.x == 0 && (it) < 40) {                                              \
@@ -352,9 +361,6 @@ __device__ __forceinline__ void run_segment(const AtArgs& a, const int4 sg, cons
     // ring of three stages: chunk kc + 2 is requested during iteration kc, behind its barrier (every wave has then
     // finished reading the stage it overwrites, chunk kc - 1); a wave waits for ITS DMAs of chunk kc (all but the NDMA
     // youngest) before that barrier, so behind it the whole stage has landed.
-    // ring of three stages: chunk kc + 2 is requested during iteration kc, behind its barrier (every wave has then
-    // finished reading the stage it overwrites, chunk kc - 1); a wave waits for ITS DMAs of chunk kc (all but the NDMA
-    // youngest) before that barrier, so behind it the whole stage has landed.
     issue(0);
     if (nk > 1) {
       issue(1);
@@ -454,6 +460,9 @@ __global__ void __launch_bounds__(NT, 2) atrans_kernel(AtArgs a) {
   // workgroups that share a row tile (consecutive logical ids) onto one XCD: blocks b, b + 8, ... share an XCD
   int id = blockIdx.x;
   if ((a.n_wg & 7) == 0) id = (id & 7) * (a.n_wg >> 3) + (id >> 3);
+#if ATRANS_STAMPS
+  const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime(), ct0 = __builtin_amdgcn_s_memtime();
+#endif
   const int s0 = a.seg_begin[id], s1 = a.seg_begin[id + 1];
   for (int s = s0; s < s1; ++s) {
     const int4 sg = a.segs[2 * s], sk = a.segs[2 * s + 1];
@@ -464,6 +473,16 @@ __global__ void __launch_bounds__(NT, 2) atrans_kernel(AtArgs a) {
       dispatch_segment<TERMS, false, PLANES>(a, sg, sk, lds);
     }
   }
+#if ATRANS_STAMPS
+  wait_vm<0>();                    // the output stores of every wave belong to the workgroup's time
+  __syncthreads();
+  if (threadIdx.x == 0 && id < WG_STAMPS) {
+    g_wg_stamps[id][0] = rt0;
+    g_wg_stamps[id][1] = __builtin_amdgcn_s_memrealtime();
+    g_wg_stamps[id][2] = ct0;
+    g_wg_stamps[id][3] = __builtin_amdgcn_s_memtime();
+  }
+#endif
 }
 
 // ---- K-split launches: sum of the slabs in slab order (fixed: bitwise reproducible) ---------------------------------------
@@ -492,13 +511,51 @@ __global__ void __launch_bounds__(256) atrans_slab_sum_kernel(SlabArgs a) {
 __global__ void __launch_bounds__(256) atrans_pack_kernel(PackArgs a) { atrans_pack_body(a, (int)blockIdx.x); }
 
 
-struct Blk {
-  int layer, cb, w, maxseg;      // column block cb of the layer; w = contraction chunks (cost of one block); longest segment
-};
+// What a segment costs its workgroup, in units of one column block's share of a chunk iteration: an iteration over w
+// blocks takes a + b w (staging the 256 x 32 x tile, reading and splitting its fragments and the barrier do not depend
+// on w), the prologue + epilogue of a segment (pipeline fill, output stores) a constant.  Least-squares fit of
+// profiles/r09_atrans_wg_stamps_parent.txt: a / b = 2.7, prologue + epilogue = 28 b.
+// A ragged layer (size not a multiple of 8) stages x through registers, synchronously: 16.5-20 us for a segment of two
+// blocks over four chunks (profiles/r09_atrans_wg_stamps_branch.txt, runs "3:2") = 3-4 us per chunk = 20 blocks' worth.
+constexpr int PLAN_F = 3, PLAN_E = 28, PLAN_F_RAGGED = 20;
 
-// cost of blocks [b0, b1) as one run: cut at layer boundaries, pieces of more than maxseg blocks in near-equal parts
-long long run_cost(const std::vector<Blk>& blks, int b0, int b1, std::vector<int4>* segs, int row0) {
-  long long cost = 0;
+struct Blk {
+  int layer, cb, w, maxseg, wgs, nc, f;   // column block cb of the layer; w = chunk iterations of a workgroup on it; longest
+};    // segment; workgroups per segment (the layer's K slices); chunks of the contraction; fixed part of a chunk iteration
+
+// a layer's piece of n blocks inside a run: ceil(n / maxseg) near-equal segments.  Their cost to ONE workgroup: the sum
+// (it walks them one after the other), K-split launches: the largest (a workgroup per segment and slice)
+struct Piece {
+  long long cost;
+  int segs, wgs;
+};
+Piece piece_cost(const Blk& b, int n, bool ksplit) {
+  const int parts = (n + b.maxseg - 1) / b.maxseg;
+  if (ksplit) return Piece{(long long)b.w * (b.f + (n + parts - 1) / parts) + PLAN_E, parts, parts * b.wgs};
+  return Piece{(long long)b.w * ((long long)b.f * parts + n) + (long long)PLAN_E * parts, parts, 1};
+}
+
+// the runs [b, e) for b = e - 1 down to 0: fn(b, cost, segments, workgroups) until it returns false
+template <class Fn>
+void runs_ending_at(const std::vector<Blk>& blks, int e, bool ksplit, Fn fn) {
+  long long tail = 0;            // the complete pieces behind the first one
+  int tail_segs = 0, tail_wgs = 0, n = 0;
+  for (int b = e - 1; b >= 0; --b) {
+    if (n && blks[b].layer != blks[b + 1].layer) {
+      const Piece p = piece_cost(blks[b + 1], n, ksplit);
+      tail = ksplit ? std::max(tail, p.cost) : tail + p.cost;
+      tail_segs += p.segs;
+      tail_wgs += p.wgs;
+      n = 0;
+    }
+    ++n;
+    const Piece p = piece_cost(blks[b], n, ksplit);
+    if (!fn(b, ksplit ? std::max(tail, p.cost) : tail + p.cost, tail_segs + p.segs, ksplit ? tail_wgs + p.wgs : 1)) break;
+  }
+}
+
+// the segments of blocks [b0, b1) as one run
+void run_segments(const std::vector<Blk>& blks, int b0, int b1, std::vector<int4>& segs, int row0) {
   int i = b0;
   while (i < b1) {
     int j = i;
@@ -507,13 +564,132 @@ long long run_cost(const std::vector<Blk>& blks, int b0, int b1, std::vector<int
     int done = 0;
     for (int p = 0; p < parts; ++p) {
       const int m = (n - done + (parts - p) - 1) / (parts - p);
-      cost += (long long)m * blks[i].w + 6;        // + 6: prologue / epilogue of a segment, in block-chunk units
-      if (segs) segs->push_back(make_int4(blks[i].layer, row0, blks[i + done].cb, m));
+      segs.push_back(make_int4(blks[i].layer, row0, blks[i + done].cb, m));
       done += m;
     }
     i = j;
   }
-  return cost;
+}
+
+// K-split launches: S and R = ceil(blocks / MAXSEG) are sized so that equal-cost runs of whole segments fill the chip once.
+// The workgroups such runs take per row tile -- a block costs its layer's chunks, a segment 6 more, greedy maximal runs
+// within the smallest bound on a run, as this planner cut every launch before it priced segments -- are the budget of the
+// search below: its plan costs no workgroup more and uses no more workgroups than that one.
+long long greedy_workgroups(const std::vector<Blk>& blks, int R) {
+  const int nb = (int)blks.size();
+  auto run = [&](int b0, int b1, long long* wgs) {
+    long long cost = 0;
+    for (int i = b0, j; i < b1; i = j) {
+      for (j = i; j < b1 && blks[j].layer == blks[i].layer;) ++j;
+      const int parts = (j - i + blks[i].maxseg - 1) / blks[i].maxseg;
+      cost += (long long)(j - i) * blks[i].nc + 6 * parts;
+      if (wgs) *wgs += (long long)parts * blks[i].wgs;
+    }
+    return cost;
+  };
+  auto fits = [&](long long bound, long long* wgs) {
+    int b = 0, runs = 0;
+    while (b < nb) {
+      int e = b + 1;
+      if (run(b, e, nullptr) > bound) return false;
+      while (e < nb && run(b, e + 1, nullptr) <= bound) ++e;
+      run(b, e, wgs);
+      b = e;
+      if (++runs > R) return false;
+    }
+    return true;
+  };
+  long long lo = 0, hi = run(0, nb, nullptr);
+  while (lo < hi) {
+    const long long mid = (lo + hi) / 2;
+    if (fits(mid, nullptr)) hi = mid; else lo = mid + 1;
+  }
+  long long wgs = 0;
+  fits(hi, &wgs);
+  return wgs;
+}
+
+// Contiguous runs of the blocks, at most R: the largest cost of a workgroup as small as it can be; among those plans the
+// fewest segments beyond the first of a run, then the smallest sum of squared costs (balance), then the most runs.  A run
+// that holds pieces of two layers walks both contractions: it is taken only where the bound cannot be met without it.
+// K-split launches (a workgroup per segment and slice): the bound is met with at most `wg_budget` workgroups -- ever
+// shorter segments would buy ever cheaper workgroups until they no longer fit the chip at once (measured: Kodak at width
+// 48, 383 workgroups of <= 4 blocks instead of 279 of <= 7 on 256 CUs, 2 % on the step) --, then the fewest.
+std::vector<int> plan_cuts(const std::vector<Blk>& blks, int R, bool ksplit, long long wg_budget) {
+  const int nb = (int)blks.size();
+  const int INF = 1 << 30;
+  struct Best {
+    int extra;                   // segments beyond the first of every run; K-split: workgroups
+    long long sq;
+    int from;
+  };
+  const Best none{INF, 0, -1};
+  std::vector<std::vector<Best>> best;
+  // the best plan of at most R runs within the bound; false: none (K-split: none within the workgroup budget)
+  auto solve = [&](long long bound) {
+    best.assign(R + 1, std::vector<Best>(nb + 1, none));
+    best[0][0] = Best{0, 0, 0};
+    for (int r = 1; r <= R; ++r)
+      for (int e = r; e <= nb; ++e)
+        runs_ending_at(blks, e, ksplit, [&](int b, long long cost, int segs, int wgs) {
+          if (cost <= bound && best[r - 1][b].extra < INF) {
+            const Best c{best[r - 1][b].extra + (ksplit ? wgs : segs - 1), best[r - 1][b].sq + cost * cost, b};
+            Best& t = best[r][e];
+            if (c.extra < t.extra || (c.extra == t.extra && c.sq < t.sq)) t = c;
+          }
+          return ksplit || cost <= bound;          // (one workgroup per run: a longer run costs no less)
+        });
+    int fewest = INF;
+    for (int r = 1; r <= R; ++r) fewest = std::min(fewest, best[r][nb].extra);
+    return fewest < INF && (!ksplit || fewest <= wg_budget);
+  };
+  if (ksplit) {
+    // the largest cost is that of one segment: a short list of candidates
+    std::vector<long long> cand;
+    for (int i = 0; i < nb; ++i)
+      if (i == 0 || blks[i].layer != blks[i - 1].layer)
+        for (int m = 1; m <= blks[i].maxseg; ++m) cand.push_back(piece_cost(blks[i], m, true).cost);
+    std::sort(cand.begin(), cand.end());
+    size_t lo = 0, hi = cand.size() - 1;          // (the largest admits the whole row as one run: every layer in its fewest segments)
+    while (lo < hi) {
+      const size_t mid = (lo + hi) / 2;
+      if (solve(cand[mid])) hi = mid; else lo = mid + 1;
+    }
+    solve(cand[hi]);
+  } else {
+    // binary search on the bound; within a bound, greedy maximal runs are the fewest
+    auto fits = [&](long long bound) {
+      int e = nb, runs = 0;
+      while (e > 0) {
+        int first = e;
+        runs_ending_at(blks, e, false, [&](int b, long long cost, int, int) {
+          if (cost <= bound) first = b;
+          return cost <= bound;
+        });
+        if (first == e || ++runs > R) return false;
+        e = first;
+      }
+      return true;
+    };
+    long long lo = 0, hi = 0;
+    runs_ending_at(blks, nb, false, [&](int, long long cost, int, int) { hi = cost; return true; });
+    while (lo < hi) {
+      const long long mid = (lo + hi) / 2;
+      if (fits(mid)) hi = mid; else lo = mid + 1;
+    }
+    solve(hi);
+  }
+  int runs = 0;
+  for (int r = 1; r <= R; ++r) {
+    const Best &c = best[r][nb], &t = best[runs][nb];
+    if (c.extra < INF && (runs == 0 || c.extra < t.extra || (c.extra == t.extra && c.sq <= t.sq))) runs = r;
+  }
+  std::vector<int> cuts(runs);
+  for (int r = runs, e = nb; r >= 1; --r) {
+    cuts[r - 1] = e;
+    e = best[r][e].from;
+  }
+  return cuts;
 }
 
 }  // namespace
@@ -541,13 +717,11 @@ extern "C" int rcb_atrans_plan(int64_t rows, int32_t n_layers, const int32_t* si
                                int32_t max_ints) {
   RCB_REQUIRE(sizes && (plan || max_ints == 0) && n_layers >= 1 && n_layers <= MAXL && rows >= 1 && n_cu >= 1 && max_ints >= 0,
               RCB_ERR_ARG, "atrans_plan: bad arguments");
-  std::vector<Blk> blks;
+  int nb = 0;
   for (int l = 0; l < n_layers; ++l) {
     RCB_REQUIRE(sizes[l] >= 1, RCB_ERR_ARG, "atrans_plan: layer %d empty", l);
-    const int lp = pad32(sizes[l]);
-    for (int cb = 0; cb < lp / 32; ++cb) blks.push_back(Blk{l, cb, lp / BK, (sizes[l] & 7) ? 2 : MAXSEG});
+    nb += pad32(sizes[l]) / 32;
   }
-  const int nb = (int)blks.size();
   const long long m_tiles = (rows + BM - 1) / BM;
   int R = (int)std::max<long long>(1, n_cu / m_tiles);
   R = std::min(R, (nb + 1) / 2);
@@ -560,36 +734,24 @@ extern "C" int rcb_atrans_plan(int64_t rows, int32_t n_layers, const int32_t* si
     S = (int)std::min<long long>(8, n_cu / (m_tiles * runs_full));
     R = runs_full;
   }
-  // contiguous runs minimising the largest cost: binary search on the bound, greedy maximal runs
-  long long lo = 0, hi = run_cost(blks, 0, nb, nullptr, 0);
-  auto fits = [&](long long bound, std::vector<int>* cuts) {
-    int b = 0, runs = 0;
-    while (b < nb) {
-      int e = b + 1;
-      if (run_cost(blks, b, e, nullptr, 0) > bound) return false;
-      while (e < nb && run_cost(blks, b, e + 1, nullptr, 0) <= bound) ++e;
-      if (cuts) cuts->push_back(e);
-      b = e;
-      if (++runs > R) return false;
-    }
-    return true;
-  };
-  while (lo < hi) {
-    const long long mid = (lo + hi) / 2;
-    if (fits(mid, nullptr)) hi = mid; else lo = mid + 1;
+  int slabs[MAXL];
+  for (int l = 0; l < n_layers; ++l) slabs[l] = std::min(S, pad32(sizes[l]) / BK);
+  std::vector<Blk> blks;
+  for (int l = 0; l < n_layers; ++l) {
+    const int lp = pad32(sizes[l]), nc = lp / BK;
+    const bool ragged = (sizes[l] & 7) != 0;
+    for (int cb = 0; cb < lp / 32; ++cb)
+      blks.push_back(Blk{l, cb, (nc + slabs[l] - 1) / slabs[l], ragged ? 2 : MAXSEG, slabs[l], nc, ragged ? PLAN_F_RAGGED : PLAN_F});
   }
-  std::vector<int> cuts;
-  fits(hi, &cuts);
+  const std::vector<int> cuts = plan_cuts(blks, R, S > 1, S > 1 ? greedy_workgroups(blks, R) : 0);
   const int runs = (int)cuts.size();
   std::vector<int4> segs;          // two entries per segment
   std::vector<int> begin;
-  int slabs[MAXL];
-  for (int l = 0; l < n_layers; ++l) slabs[l] = std::min(S, pad32(sizes[l]) / BK);
   for (long long mt = 0; mt < m_tiles; ++mt) {
     int b = 0;
     for (int ri = 0; ri < runs; ++ri) {
       std::vector<int4> run;
-      run_cost(blks, b, cuts[ri], &run, (int)(mt * BM));
+      run_segments(blks, b, cuts[ri], run, (int)(mt * BM));
       b = cuts[ri];
       if (S == 1) {                       // one workgroup per run: its segments one after the other, whole contraction
         begin.push_back((int)segs.size() / 2);
@@ -828,6 +990,12 @@ extern "C" int rcb_atrans_wgrad_narrow(const float* h, const void* h_hi, const v
 extern "C" int rcb_debug_atrans_stamps(unsigned long long* host, int32_t n) {
   if (n > 8 * 40 * 6) n = 8 * 40 * 6;
   hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * n);
+  return (int)e;
+}
+
+extern "C" int rcb_debug_atrans_wg_stamps(unsigned long long* host, int32_t n_wg) {
+  if (n_wg > WG_STAMPS) n_wg = WG_STAMPS;
+  hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wg_stamps), sizeof(unsigned long long) * 4 * n_wg);
   return (int)e;
 }
 #endif
