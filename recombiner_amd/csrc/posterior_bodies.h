@@ -56,7 +56,9 @@ __device__ __forceinline__ float4 philox_normal4(unsigned long long group, unsig
   const uint4 r = philox4x32_10(make_uint4((unsigned)group, (unsigned)(group >> 32), stream ^ (unsigned)(step >> 32) * 0x85EBCA6Bu,
                                            (unsigned)step),
                                 make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
-  constexpr float K = 1.0f / 16777216.0f;             // 24-bit uniforms: u1 in (0, 1), u2 in [0, 1)
+  // 24-bit uniforms: u2 in [0, 1), u1 in (0, 1] -- (float)(r >> 8) + 0.5f is not representable above 2^23 and rounds to even, so
+  // r >> 8 = 2^24 - 1 gives u1 = 1 exactly and a normal of exactly 0 (one draw in 2^24; pinned by tests/posterior_emul.py)
+  constexpr float K = 1.0f / 16777216.0f;
   const float u1 = ((float)(r.x >> 8) + 0.5f) * K, u2 = (float)(r.y >> 8) * K;
   const float u3 = ((float)(r.z >> 8) + 0.5f) * K, u4 = (float)(r.w >> 8) * K;
   // hardware transcendentals (about 1 ulp: ample for noise): v_log_f32 is log2, v_sin / v_cos take revolutions

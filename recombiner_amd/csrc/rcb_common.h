@@ -32,7 +32,12 @@ int fail(int code, const char* fmt, ...);
 // element and made the "HBM-bound" posterior kernels compute-bound.  These forms use the hardware v_exp / v_log / v_rcp
 // / v_sqrt with one correction step each: <= 2 ulp from the correctly rounded value (the library forms are <= 1 - 2 ulp
 // themselves, and torch's CPU kernels differ from either by an ulp here and there), ~10x fewer instructions.
-// All of them live under the caller's `#pragma clang fp contract(off)`: the fmas below are written out.
+// Their fmas are written out; the functions themselves are defined BEFORE the includers' `#pragma clang fp contract(off)`, so a
+// plain a * b + c in them (kl_elem_f32's var_ratio + t1) may still be contracted, kernel by kernel.
+// Adam's square root and divisions (adam_apply, posterior_bodies.h) are built from div_fast and v_sqrt in the same way and share
+// the PRECONDITION of the helpers below: no denormal intermediate, i.e. a gradient is 0 or |g| >= 1e-15 (w2 g^2 >= 1e-33).  Under
+// it the suite enforces: m and v bit for bit the fp32 chains of torch/optim/adam.py, the parameter within 1/2 ulp +
+// 4 * 2^-23 * step_size * |m / denom| of the fp64 update from them.
 
 // a / b for finite, normal operands: reciprocal + one residual correction (<= 1 ulp)
 __device__ __forceinline__ float div_fast(float a, float b) {
@@ -58,6 +63,10 @@ __device__ __forceinline__ float exp_fast(float x) {
 __device__ __forceinline__ float log_fast(float u) { return __builtin_amdgcn_logf(u) * 0.693147182464599609375f; }
 
 // softplus(x, beta=1, threshold=20) / 6 in fp32  (prior_model.py:88)
+// ENFORCED (tests/test_hip_posterior_exact.py, counted in tests/posterior_emul.py): within 6 ulp of the fp64 value for every x in
+// [-80, 88.7] -- swept over every float around the series / log switch at t = 2^-6 (x = -4.159; log_scale starts at -4) and around
+// the threshold 20 -- and x / 6 to 1/2 ulp above; measured worst 3.9 ulp.  NaN gives NaN.  +-inf give NaN, where softplus gives inf
+// and 0: exp_fast forms inf - inf in `lo`.  Pinned by that test as it is: a log_scale of +-inf is a diverged run either way.
 __device__ __forceinline__ float st_f32(float x) {
   const float t = exp_fast(x);
   // log1p(t): series for t < 2^-6 (truncation error t^5 / 6 relative), otherwise ln(u) + (t - (u - 1)) / u with u = fl(1 + t):
@@ -73,16 +82,25 @@ __device__ __forceinline__ float st_f32(float x) {
   return __builtin_fmaf(__builtin_fmaf(-6.0f, q, sp), 0.16666667163372039794921875f, q);
 }
 // d/dx [softplus(x)/6] = sigmoid(x)/6 (1/6 above the threshold)
+// ENFORCED (same tests): within 5 ulp of the fp64 value on [-80, 80] (measured worst 2.9), exactly fl(1/6) above 20 and for +inf,
+// 0 for -inf; a finite x below -80 gives the value of -80 (3e-36 where sigmoid / 6 goes on to 0).  NaN gives NaN: the clamp is a
+// compare and select, not fminf, which returns its other operand for a NaN and made dst_f32(NaN) the finite value of -80.
 __device__ __forceinline__ float dst_f32(float x) {
-  const float d = 1.0f + exp_fast(fminf(-x, 80.0f));      // (finite: the Newton step below must not see inf * 0)
+  const float nx = -x;
+  const float d = 1.0f + exp_fast(nx > 80.0f ? 80.0f : nx);      // (finite: the Newton step below must not see inf * 0)
   float r = __builtin_amdgcn_rcpf(d);
   r = __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);                            // Newton step: <= 1 ulp
-  const float sg = (x > 20.0f) ? 1.0f : r;
+  float sg = (x > 20.0f) ? 1.0f : r;
+  sg = (x == -__builtin_inff()) ? 0.0f : sg;                                        // sigmoid(-inf) = 0, not the clamped value
   const float q = sg * 0.16666667163372039794921875f;
   return __builtin_fmaf(__builtin_fmaf(-6.0f, q, sg), 0.16666667163372039794921875f, q);
 }
 
 // torch.distributions.kl._kl_normal_normal in fp32
+// ENFORCED (same tests): |result - KL| <= 4.001 * 2^-24 * (ratio^2 + t^2 + 1 + |ln ratio^2|), ratio = sig_q / sig_p, t = (mu_q -
+// mu_p) / sig_p, on a grid with ratio in [2^-8, 2^8] and |t| up to 2^8; exactly 0 for q = p.  This function sits BEFORE the includers'
+// `contract(off)` pragma, so `var_ratio + t1` may become fma(t, t, var_ratio) in one kernel and not in another: the bound covers both,
+// and no test assumes that two kernels agree on its bits.
 __device__ __forceinline__ float kl_elem_f32(float mu_q, float sig_q, float mu_p, float sig_p) {
   const float rp = __builtin_amdgcn_rcpf(sig_p);
   float ratio = sig_q * rp;
