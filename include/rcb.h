@@ -22,9 +22,9 @@ extern "C" {
 #endif
 
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
- * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform).  A binding compares
+ * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23).  A binding compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 407
+#define RCB_VERSION 408
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -532,6 +532,16 @@ int rcb_upconv_wgrad(const void* x, int32_t x_is_f32_preact, const void* dy, int
 int rcb_upconv_bwd_fused(const void* dy, const float* weff, const void* x, void* dx, float* dweff, float* dbias,
                          int32_t batch, int32_t grid, int32_t cout, float* workspace, int64_t workspace_floats,
                          const void* frag_pack, rcb_stream_t stream);
+/* 408: stages 2 and 3 of the CIFAR geometry forward in ONE launch: z1 [batch][8][8][64] -> h2 [batch][16][16][64] (bf16,
+ * LeakyReLU applied; the backward reads it) and pe [batch][32][32][16] (bf16, linear), bit-identical to
+ * rcb_upconv_fwd(grid 8, cout 64) followed by rcb_upconv_fwd(grid 16, cout 16): stage 3 reads every h2 image from LDS,
+ * where stage 2 has just put it, instead of from HBM.  Only z1_is_f32_preact = 2 (bf16 pre-activation),
+ * pe_is_f32_linear = 2 (bf16 linear) and a non-NULL frag_pack exist; every other combination, and a process started with
+ * RCB_UPCONV_HALF_WG=1, returns RCB_ERR_UNSUPPORTED without launching anything (the caller runs the two launches).  The library
+ * reads no switch of its own: RCB_UPCONV_FWD_FUSED=0 is the Python callers' (a field of their step plans) and makes them
+ * keep the two launches.                                                                                              */
+int rcb_upconv_fwd23(const void* z1, int32_t z1_is_f32_preact, const float* b2, const float* b3, void* h2, void* pe,
+                     int32_t pe_is_f32_linear, int32_t batch, const void* frag_pack, rcb_stream_t stream);
 
 /* The phase-form ("effective") weights of the CIFAR-geometry upsampling net from its conv weights, and the
  * transposed map for their gradients (one launch each; prior_model.py:39-57 defines the convolutions):

@@ -64,7 +64,7 @@ class LevelBwd(C.Structure):
 
 _lib = None
 # the header these mirrors were written against (include/rcb.h: RCB_VERSION) and the structures load() verifies by size
-ABI_VERSION = 407
+ABI_VERSION = 408
 _MIRRORS = {0: SirenDesc, 1: Level, 2: LevelBwd, 3: AdamCfg, 4: AdamTensor, 5: RecDesc}
 
 # The prototype of every entry point of include/rcb.h, in header order: name -> (restype, [argtypes]).  load() applies it, so
@@ -116,6 +116,7 @@ PROTOTYPES = {
     "rcb_upconv_wgrad_workspace": (_i64, [_i32, _i32]),
     "rcb_upconv_wgrad": (_int, [_p, _i32, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _i64, _p]),
     "rcb_upconv_bwd_fused": (_int, [_p] * 6 + [_i32, _i32, _i32, _p, _i64, _p, _p]),
+    "rcb_upconv_fwd23": (_int, [_p, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p]),
     "rcb_upconv_weff_build": (_int, [_p] * 6 + [_i32, _p, _p, _p, _p]),
     "rcb_upconv_weff_grad": (_int, [_p, _i32, _p, _p, _p, _p, _p, _p, _i32, _p, _p]),
     "rcb_tile_gather": (_int, [_p, _p] + [_i32] * 10 + [_p]),

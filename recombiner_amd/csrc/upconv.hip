@@ -614,6 +614,205 @@ __global__ void __launch_bounds__(512) upconv_fwd2_reg_kernel(FwdArgs a) {
 #undef RCB_FETCH2
 }
 
+// ------------------------------------------------------------------------------------------------
+// stages 2 + 3 forward in one launch (bf16 pre-activation z1 in, bf16 h2 and bf16 linear pe out): stage 3 reads an INR's h2
+// image from LDS, where stage 2 has just put it, instead of from HBM one launch later (134 MB per 4096 INRs).
+//
+// One wave cannot hold both stages' weight fragments (32 + 16 uint4 = 192 registers beside accumulators, gather ring and the
+// image prefetch, at two waves per SIMD), so the workgroup splits by role, one wave of each role on every SIMD:
+//   waves 0-3: stage 2 of ONE INR per iteration, as a wave of upconv_fwd2_reg_kernel<3> (phase = wave & 3, both tiles, both
+//              halves of the 64 output channels; same MFMA order, same epilogue).  Every 16-byte piece of h2 is stored twice: to
+//              HBM (the backward reads it) and into the LDS image of stage 3, in the layout upconv_fwd3_lds_kernel stages.
+//   waves 4-7: stage 3 of the INR that stage 2 finished one iteration earlier, as the four-wave instance of
+//              upconv_fwd3_lds_kernel<16, 1, 4> deals its tiles (fwd3_body as it is).
+// Iteration k (the workgroup's k-th INR, b = blockIdx.x + k gridDim.x):  stage-2 waves: z1 image k & 1 -> h2 image k & 1 (+ HBM),
+// then they commit the prefetched z1 of INR k + 1 to z1 image (k + 1) & 1 and request that of INR k + 2; stage-3 waves:
+// h2 image (k - 1) & 1 -> pe.  ONE barrier ends the iteration.  What an iteration writes was last read one iteration earlier
+// (h2 image k & 1 by stage 3 in iteration k - 1, z1 image (k + 1) & 1 by stage 2 in iteration k - 1) and is read one iteration
+// later: every reuse has a barrier in between.
+// Barriers: both roles run  1 (halo zeroing) + 1 (first z1 image) + (nloc + 1) iterations, nloc = the workgroup's INR count --
+// the same expression of blockIdx / gridDim / batch in both branches: stage 2 runs nloc loop iterations and one barrier of
+// drain behind them (stage 3 finishes the last INR), stage 3 one barrier of fill in front of its nloc loop iterations; a
+// workgroup without an INR runs 1 + 1 + 1.
+// LDS: 2 x 41 472 B (h2 images) + 2 x 14 400 B (z1 images) + 256 B (stage-2 bias) = 112 000 B.
+// ------------------------------------------------------------------------------------------------
+struct Fwd23Args {
+  const void* z1;
+  const float* b2;
+  const float* b3;
+  void* h2;
+  void* pe;
+  int batch;
+  const uint4* pack;
+};
+
+__global__ void __launch_bounds__(512) upconv_fwd23_kernel(Fwd23Args a) {
+  constexpr int G = 8, HG = 10, RS = 72, COUT = 64, ZIMG = HG * HG * RS;      // stage-2 source image, as upconv_fwd2_reg_kernel
+  constexpr int HG3 = 18, RS3 = 64, HIMG = HG3 * HG3 * RS3;                     // stage-3 source image, as upconv_fwd3_lds_kernel
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __bf16* himg = reinterpret_cast<__bf16*>(smem_raw);                           // [2][HIMG]
+  __bf16* zimg = himg + 2 * HIMG;                                               // [2][ZIMG]
+  float* bs = reinterpret_cast<float*>(zimg + 2 * ZIMG);                        // [64]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int gs = gridDim.x, b0 = blockIdx.x;
+  const int nloc = b0 < a.batch ? (a.batch - b0 + gs - 1) / gs : 0;             // INRs of this workgroup (uniform)
+  for (int e = tid; e < (2 * HIMG + 2 * ZIMG) / 8; e += 512) reinterpret_cast<uint4*>(smem_raw)[e] = make_uint4(0, 0, 0, 0);
+  if (tid < COUT) bs[tid] = a.b2[tid];
+  if (wave < 4) {
+    // ---------------------------------------------------------------- stage 2
+    const int q = lane & 31, h = lane >> 5;
+    const int ph = wave & 3, pa = ph >> 1, pb = ph & 1;
+    uint4 fr[2][2][2][4];   // [mt][ty][tx][kb]
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+        for (int tx = 0; tx < 2; ++tx)
+#pragma unroll
+          for (int kb = 0; kb < 4; ++kb) fr[mt][ty][tx][kb] = a.pack[((((ph * 2 + mt) * 2 + ty) * 2 + tx) * 4 + kb) * 64 + lane];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+      for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+        for (int tx = 0; tx < 2; ++tx)
+#pragma unroll
+          for (int kb = 0; kb < 4; ++kb) pin(fr[mt][ty][tx][kb]);
+    // one z1 image = 64 pixels x 8 chunks of 8 channels = 512 chunks, 2 per thread of the four stage-2 waves
+    Raw8<3> pre[2];
+#define RCB_FETCH23(bb)                                                                                               \
+  _Pragma("unroll") for (int k_ = 0; k_ < 2; ++k_) pre[k_] = raw_load<3>(a.z1, (long long)(bb) * G * G * CIN + 8 * (tid + 256 * k_));
+#define RCB_COMMIT23(dst)                                                                                             \
+  _Pragma("unroll") for (int k_ = 0; k_ < 2; ++k_) {                                                                  \
+    const int e_ = tid + 256 * k_, pix_ = e_ >> 3, c8_ = e_ & 7;                                                      \
+    Frag f_;                                                                                                          \
+    f_.v = raw_frag<3>(pre[k_], true);                                                                                \
+    *reinterpret_cast<uint4*>((dst) + (((pix_ >> 3) + 1) * HG + ((pix_ & 7) + 1)) * RS + 8 * c8_) = f_.u;             \
+  }
+    if (nloc > 0) RCB_FETCH23(b0)
+    __syncthreads();          // barrier 1: the halos are zero
+    if (nloc > 0) RCB_COMMIT23(zimg)
+    if (nloc > 1) RCB_FETCH23(b0 + gs)
+    __syncthreads();          // barrier 2: z1 image 0 is staged
+    // (the tile loop is unrolled and the INR loop has no branch around it: between the request of a z1 image and its commit one
+    // iteration later lie exactly this iteration's eight h2 stores, so the commit waits with a COUNTED vmcnt and not, as behind a
+    // loop or a branch of unknown store count, for the acknowledgement of every store the wave has just issued)
+#pragma unroll 1
+    for (int k = 0; k < nloc; ++k) {
+      {
+        const int b = b0 + k * gs;
+        const __bf16* im = zimg + (k & 1) * ZIMG;
+        __bf16* hd = himg + (k & 1) * HIMG;
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          const int pos = tt * 32 + q, i = pos >> 3, j = pos & 7;
+          f32x16 acc[2];
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+          const __bf16* base = im + ((i + pa) * HG + (j + pb)) * RS + 8 * h;
+#pragma unroll
+          for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+            for (int tx = 0; tx < 2; ++tx)
+#pragma unroll
+              for (int kb = 0; kb < 4; ++kb) {
+                Frag bf, fa;
+                bf.u = *reinterpret_cast<const uint4*>(base + (ty * HG + tx) * RS + 16 * kb);
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt) {
+                  fa.u = fr[mt][ty][tx][kb];
+                  acc[mt] = mfma16(fa.v, bf.v, acc[mt]);
+                }
+              }
+          __builtin_amdgcn_sched_barrier(0);
+          // epilogue of upconv_fwd2_reg_kernel: lane (q, h) ends up with channels 32 mt + 16 h .. + 15 of output pixel (oy, ox)
+          const int oy = 2 * i + pa, ox = 2 * j + pb;
+          const long long opix = ((long long)b * (2 * G) + oy) * (2 * G) + ox;
+          // the same two 16-byte pieces in stage 3's image: pixel (oy + 1, ox + 1) of [18][18][64], chunk c at c ^ ((x >> 1) & 7)
+          __bf16* hpix = hd + ((oy + 1) * HG3 + (ox + 1)) * RS3;
+          const int sw = ((ox + 1) >> 1) & 7;
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt) {
+            float v[16];
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+              const float4 bb = *reinterpret_cast<const float4*>(bs + 32 * mt + 8 * g4 + 4 * h);
+              v[4 * g4 + 0] = lrelu(acc[mt][4 * g4 + 0] + bb.x);
+              v[4 * g4 + 1] = lrelu(acc[mt][4 * g4 + 1] + bb.y);
+              v[4 * g4 + 2] = lrelu(acc[mt][4 * g4 + 2] + bb.z);
+              v[4 * g4 + 3] = lrelu(acc[mt][4 * g4 + 3] + bb.w);
+            }
+            float xa[8], ya[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+              auto s2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[m]), __float_as_uint(v[8 + m]), false, false);
+              xa[m] = __uint_as_float(s2[0]);   // channel 32 mt + 16 h + (m & 3) + 8 (m >> 2)
+              ya[m] = __uint_as_float(s2[1]);   //   ... + 4
+            }
+            Frag o0, o1;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+              o0.v[kk] = (__bf16)xa[kk];     o0.v[4 + kk] = (__bf16)ya[kk];
+              o1.v[kk] = (__bf16)xa[4 + kk]; o1.v[4 + kk] = (__bf16)ya[4 + kk];
+            }
+            uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<__bf16*>(a.h2) + opix * COUT + 32 * mt + 16 * h);
+            dst[0] = o0.u;
+            dst[1] = o1.u;
+            const int c0 = 4 * mt + 2 * h;
+            *reinterpret_cast<uint4*>(hpix + 8 * (c0 ^ sw)) = o0.u;
+            *reinterpret_cast<uint4*>(hpix + 8 * ((c0 + 1) ^ sw)) = o1.u;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if (k + 1 < nloc) RCB_COMMIT23(zimg + ((k + 1) & 1) * ZIMG)
+      if (k + 2 < nloc) RCB_FETCH23(b0 + (k + 2) * gs)
+      __syncthreads();        // ends iteration k
+    }
+    __syncthreads();          // ends iteration nloc (drain: stage 3 finishes the last INR)
+#undef RCB_FETCH23
+#undef RCB_COMMIT23
+  } else {
+    // ---------------------------------------------------------------- stage 3
+    const int w3 = wave - 4, pa = w3 & 1, tp = w3 >> 1;
+    uint4 fr[2][2][2][2];   // [pb][ty][tx][kb2]
+#pragma unroll
+    for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+      for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+        for (int tx = 0; tx < 2; ++tx)
+#pragma unroll
+          for (int kb2 = 0; kb2 < 2; ++kb2)
+            fr[pb][ty][tx][kb2] = a.pack[16384 + ((((pa * 2 + pb) * 2 + ty) * 2 + tx) * 2 + kb2) * 64 + lane];
+#pragma unroll
+    for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+      for (int ty = 0; ty < 2; ++ty)
+#pragma unroll
+        for (int tx = 0; tx < 2; ++tx)
+#pragma unroll
+          for (int kb2 = 0; kb2 < 2; ++kb2) pin(fr[pb][ty][tx][kb2]);
+    float bia[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bia[r] = a.b3[4 * (lane >> 4) + r];
+    const FwdArgs a3{nullptr, nullptr, a.b3, a.pe, a.batch, a.pack};
+    __syncthreads();          // barrier 1
+    __syncthreads();          // barrier 2
+    __syncthreads();          // ends iteration 0 (fill: stage 2 computes the first INR)
+#pragma unroll 1
+    for (int k = 1; k <= nloc; ++k) {
+      const __bf16* im = himg + ((k - 1) & 1) * HIMG;
+#pragma unroll 1
+      for (int t2 = 0; t2 < 2; ++t2) fwd3_body<16, 1>(im, fr, a3, b0 + (k - 1) * gs, pa, tp + 2 * t2, lane, bia);
+      __syncthreads();        // ends iteration k
+    }
+  }
+}
+
 // data gradient of stage 2: D[ci, pos] = sum over the 16 window combos and 64 output channels.  The 128 fragments do
 // not fit one wave, so wave w = (ci half w & 1, tile (w >> 1) & 1, combo half w >> 2) keeps 32 of them and the two
 // combo halves are added through LDS.  The epilogue (combo-half 0 waves) multiplies by LeakyReLU'(x), swaps lane halves
@@ -1565,4 +1764,22 @@ extern "C" int rcb_upconv_bwd_fused(const void* dy, const float* weff, const voi
   upconv_wgrad_reduce_kernel<<<(row + 63) / 64, 256, 0, st>>>(workspace, g, row, 1024 * cout, dweff, dbias);
   RCB_LAUNCH_CHECK();
   return RCB_OK;
+}
+
+// Stages 2 + 3 forward of the CIFAR geometry in one launch (see upconv_fwd23_kernel): bf16 pre-activation z1, bf16 h2, bf16
+// linear pe and the fragment pack only.  Every other combination (and RCB_UPCONV_HALF_WG=1) is refused with
+// RCB_ERR_UNSUPPORTED before anything is launched: the caller keeps the two rcb_upconv_fwd launches.
+extern "C" int rcb_upconv_fwd23(const void* z1, int32_t z1_is_f32_preact, const float* b2, const float* b3, void* h2, void* pe,
+                                int32_t pe_is_f32_linear, int32_t batch, const void* frag_pack, rcb_stream_t stream) {
+  RCB_REQUIRE(z1 && b2 && b3 && h2 && pe, RCB_ERR_ARG, "upconv_fwd23: null pointer");
+  RCB_REQUIRE(batch > 0, RCB_ERR_SHAPE, "upconv_fwd23: empty batch");
+  RCB_REQUIRE((reinterpret_cast<uintptr_t>(frag_pack) & 15) == 0, RCB_ERR_ARG, "upconv_fwd23: frag_pack must be 16-byte aligned");
+  RCB_REQUIRE(z1_is_f32_preact == 2 && pe_is_f32_linear == 2 && frag_pack, RCB_ERR_UNSUPPORTED,
+              "upconv_fwd23: in_mode=%d out_mode=%d pack=%d: only bf16 pre-activation in, bf16 linear out, with the fragment pack",
+              z1_is_f32_preact, pe_is_f32_linear, frag_pack ? 1 : 0);
+  RCB_REQUIRE(!half_wg(batch), RCB_ERR_UNSUPPORTED, "upconv_fwd23: RCB_UPCONV_HALF_WG=1 keeps the two launches");
+  Fwd23Args a{z1, b2, b3, h2, pe, batch, reinterpret_cast<const uint4*>(frag_pack)};
+  static bool done = false;
+  constexpr int kSmem = 2 * 18 * 18 * 64 * 2 + 2 * 10 * 10 * 72 * 2 + 64 * 4;
+  return launch(upconv_fwd23_kernel, a, batch < 256 ? batch : 256, kSmem, (hipStream_t)stream, done);
 }

@@ -20,6 +20,7 @@ f32 = torch.float32
 f64 = torch.float64
 i32 = torch.int32
 bf16 = torch.bfloat16
+RCB_ERR_UNSUPPORTED = -3      # include/rcb.h
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1034,6 +1035,37 @@ def upconv_fwd(x, weff, bias, grid, cout, out_f32, preact=False, linear_bf16=Fal
     _launch("rcb_upconv_fwd", ptr(x), _xmode(x, preact), ptr(weff, f32), ptr(bias, f32), ptr(y), omode, B, grid, cout,
             ptr(pack, None, True))
     return y
+
+
+def upconv_fwd23_enabled():
+    """stages 2 + 3 of the CIFAR upsampling net's forward as one launch (rcb_upconv_fwd23): on unless RCB_UPCONV_FWD_FUSED=0 (a
+    test and same-box A/B switch: the two rcb_upconv_fwd launches write the same bits).  Read where the prior-training step is
+    planned -- the value is a field of StepPlan, hence of the workspace / graph key, and handed down as an argument -- and by
+    upsample_cifar_hip(fwd_fused=None), which a model with frozen mappings (TestBNNmodel) resolves once for its lifetime."""
+    return _os.environ.get("RCB_UPCONV_FWD_FUSED", "1") != "0"
+
+
+def upconv_fwd23(z1, b2, b3, pack, out=None, pe_f32=False, refuse_ok=False):
+    """z1 [B, 8, 8, 64] (pre-activation of stage 1) -> (h2 [B, 16, 16, 64] bf16 with LeakyReLU, pe [B, 32, 32, 16] linear) in ONE
+    launch, bit-identical to upconv_fwd(z1, .., 8, 64, preact=True) followed by upconv_fwd(h2, .., 16, 16, linear_bf16=True).
+    out: optional preallocated (h2, pe).  The library has the bf16 z1 / bf16 pe / packed-fragment combination only and refuses
+    every other one (and RCB_UPCONV_HALF_WG=1) with RCB_ERR_UNSUPPORTED before it launches anything: an RcbError, or with
+    refuse_ok the return value None -- the caller then runs the two launches."""
+    B = z1.shape[0]
+    if tuple(z1.shape) != (B, 8, 8, 64):
+        raise RcbError(f"upconv_fwd23: z1 must be [B, 8, 8, 64], got {list(z1.shape)}")
+    if out is None:
+        out = (torch.empty(B, 16, 16, 64, device=z1.device, dtype=bf16),
+               torch.empty(B, 32, 32, 16, device=z1.device, dtype=f32 if pe_f32 else bf16))
+    h2, pe = out
+    if tuple(h2.shape) != (B, 16, 16, 64) or h2.dtype != bf16 or tuple(pe.shape) != (B, 32, 32, 16) or pe.dtype not in (f32, bf16):
+        raise RcbError("upconv_fwd23: out must be (bf16 [B, 16, 16, 64], bf16 or fp32 [B, 32, 32, 16])")
+    rc = _lib.load().rcb_upconv_fwd23(ptr(z1), _xmode(z1, True), ptr(b2, f32), ptr(b3, f32), ptr(h2), ptr(pe),
+                                      1 if pe.dtype == f32 else 2, B, ptr(pack, None, True), stream_ptr())
+    if rc == RCB_ERR_UNSUPPORTED and refuse_ok:
+        return None
+    check(rc, "rcb_upconv_fwd23")
+    return h2, pe
 
 
 def upconv_dgrad(dy, weff, x, grid, cout, preact=False, want_dbias=False, pack=None):

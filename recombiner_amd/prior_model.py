@@ -77,15 +77,17 @@ class InrGeometry:
             return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
         return None
 
-    def _pe(self, upsample_net, lpe, stitched=False, lpe16=None, weff_cache=None, weight_side_stream=None):
+    def _pe(self, upsample_net, lpe, stitched=False, lpe16=None, weff_cache=None, weight_side_stream=None, fwd_fused=None):
         """lpe [S, N, *lat, C] -> pe [N, S, P, 16]: hand-written phase-conv kernels in the 16-bit modes
         where the geometry is instantiated, the nn.Module (MIOpen) otherwise.  `stitched`: see _pe_layout.
         lpe16: the producer's bf16 copy of lpe [N, Dlpe] (stage-1 operand; saves the cast pass).
         weff_cache: the phase-form weights in _UpsampleCifarFn's cache form: of THIS step (ops.step_prepare), or of frozen mappings.
-        weight_side_stream: second stream for the weight-gradient side of the hand-written kernels' backward."""
+        weight_side_stream: second stream for the weight-gradient side of the hand-written kernels' backward.
+        fwd_fused: stages 2 + 3 of the hand-written forward as one launch (PriorTrainStep: its plan field; None: the
+        environment's, which a model with a frozen weff_cache -- TestBNNmodel -- reads once and keeps, upsample_cifar_hip)."""
         if self.precision != 0 and hip_path_supported(upsample_net, self.pixel_sizes, self.upsample_factors, self.patch, self.data_dim):
             return upsample_cifar_hip(upsample_net, lpe, self.stage1_bf16, self.pe_bf16, frozen_cache=weff_cache, lpe16=lpe16,
-                                      weight_side_stream=weight_side_stream)
+                                      weight_side_stream=weight_side_stream, fwd_fused=fwd_fused)
         net = upsample_net
         if self.precision != 0 and tiled_2d_preferred(upsample_net, self.patch, self.data_dim):
             net = stitched2d_module(upsample_net)                  # stitched 2-D grid: phase-conv kernels on overlapping tiles

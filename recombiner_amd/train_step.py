@@ -26,7 +26,8 @@ SWITCHES = ("precision", "patch", "lowp_gemm", "split_gemm", "split_terms", "spl
             "pe_bf16", "fused_noise", "fuse_next_sample", "operand_planes", "redraw_noise", "hier_rng", "rng_row_offset",
             "rng_seed_override", "force_segments", "capture_collectives")
 StepPlan = collections.namedtuple("StepPlan", SWITCHES + (
-    "n", "n_pix", "n_out", "lr", "training_mappings", "world", "graphable", "fork_mask", "step_fused_env", "posterior_wg_per_cu",
+    "n", "n_pix", "n_out", "lr", "training_mappings", "world", "graphable", "fork_mask", "step_fused_env", "upconv_fwd_fused",
+    "posterior_wg_per_cu",
     "lowp", "split", "sharded", "rng_lpe", "use_rng", "rng_hier", "goff_net", "goff_lpe", "want16", "lpe16_want", "fuse_next",
     "fuse_lpe", "planes", "redraw", "redraw_lpe", "pe_stitched", "capture_coll", "one_graph", "update_last", "fork_bwd",
     "fork_wside", "fork_update", "fused_step", "fused_head", "fused_tail"))
@@ -57,6 +58,9 @@ def plan_step(model, levels, y, lr, training_mappings, upsample_net, verbose=Fal
                          "64 measured no gain or a loss and were removed (DESIGN.md section 4.5 and its round-4 appendix)")
     p.fork_mask = mask if cuda else 0
     p.step_fused_env = os.environ.get("RCB_STEP_FUSED", "1")
+    # stages 2 + 3 of the upsampling net's forward as one launch (upsample_cifar_hip(fwd_fused=); same bits): on unless
+    # RCB_UPCONV_FWD_FUSED=0.  A plan field: a graph captured under one setting is never replayed under the other
+    p.upconv_fwd_fused = bool(ops.upconv_fwd23_enabled())
     # (read by the posterior kernels' launcher when the library loads; rules the combined launches out)
     p.posterior_wg_per_cu = os.environ.get("RCB_POSTERIOR_WG_PER_CU", "0")
     p.lowp = bool(m.lowp_gemm and m.precision != 0)           # the A transform as library GEMMs on 16-bit operands
@@ -282,7 +286,7 @@ class PriorTrainStep:
                 pe_c = m._pe(self.upsample_net, lpe_t, stitched=True)
             else:
                 pe = m._pe(self.upsample_net, lpe_t, lpe16=lpe16, weff_cache=weff_cache,
-                           weight_side_stream=self.side if p.fork_wside else None)      # [N, 1, P, E]
+                           weight_side_stream=self.side if p.fork_wside else None, fwd_fused=p.upconv_fwd_fused)      # [N, 1, P, E]
                 pe_c = pe.reshape(N, pe.shape[2], pe.shape[3]).contiguous()   # (not pe[:, 0]: select's backward
                 #                                                               materialises zeros + a copy)
         return lpe_t, e_lpe, pe_c

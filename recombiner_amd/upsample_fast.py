@@ -443,7 +443,8 @@ class _UpsampleCifarFn(torch.autograd.Function):
     pre-summed 512 x 4096 weight (hipBLASLt); stages 2 and 3 are the rcb_upconv_* kernels."""
 
     @staticmethod
-    def forward(ctx, lpe, W1, b1, W2, b2, W3, b3, stage1_bf16, pe_bf16, cache=None, lpe16=None, weight_side_stream=None):
+    def forward(ctx, lpe, W1, b1, W2, b2, W3, b3, stage1_bf16, pe_bf16, cache=None, lpe16=None, weight_side_stream=None,
+                fwd_fused=False):
         from . import ops
         B = lpe.shape[0]
         ctx.weight_side_stream = weight_side_stream          # see backward
@@ -461,8 +462,16 @@ class _UpsampleCifarFn(torch.autograd.Function):
             # the stage-1 GEMM operand: the producer's bf16 copy (reparam kernel) when there is one, else a cast pass
             lpe = lpe16 if (lpe16 is not None and tuple(lpe16.shape) == tuple(lpe.shape)) else lpe.to(torch.bfloat16)
         z1 = torch.addmm(b1rep, lpe, Weff1).view(B, 8, 8, 64)
-        h2 = ops.upconv_fwd(z1, Weff2, b2.contiguous(), 8, 64, out_f32=False, preact=True, pack=pack)
-        pe = ops.upconv_fwd(h2, Weff3, b3.contiguous(), 16, 16, out_f32=not pe_bf16, linear_bf16=pe_bf16, pack=pack)
+        # fwd_fused (the caller's switch, a field of its step plan): stages 2 and 3 in one launch where the library has the
+        # combination (bf16 z1, bf16 pe, fragment pack) -- the same h2 and pe, bit for bit; it refuses the others
+        out23 = None
+        if fwd_fused and z1.dtype == torch.bfloat16 and pe_bf16 and pack is not None:
+            out23 = ops.upconv_fwd23(z1, b2.contiguous(), b3.contiguous(), pack, refuse_ok=True)
+        if out23 is not None:
+            h2, pe = out23
+        else:
+            h2 = ops.upconv_fwd(z1, Weff2, b2.contiguous(), 8, 64, out_f32=False, preact=True, pack=pack)
+            pe = ops.upconv_fwd(h2, Weff3, b3.contiguous(), 16, 16, out_f32=not pe_bf16, linear_bf16=pe_bf16, pack=pack)
         ctx.save_for_backward(lpe, Weff1, z1, Weff2, h2, Weff3, pack)
         return pe.view(B, 1024, 16)
 
@@ -501,9 +510,9 @@ class _UpsampleCifarFn(torch.autograd.Function):
             dlpe = torch.mm(dz1f, Weff1.t(), out_dtype=torch.float32) if dz1f.dtype == torch.bfloat16 else dz1f @ Weff1.t()
         if side is not None:
             main.wait_stream(side)
-            return dlpe, dW1, db1, dW2, db2, dW3, db3, None, None, None, None, None
+            return dlpe, dW1, db1, dW2, db2, dW3, db3, None, None, None, None, None, None
         if not need_w:
-            return dlpe, None, None, None, None, None, None, None, None, None, None, None
+            return dlpe, None, None, None, None, None, None, None, None, None, None, None, None
         if not fused3:
             dWeff3, db3 = ops.upconv_wgrad(h2, dpe, 16, 16)
         dWeff2, db2 = ops.upconv_wgrad(z1, dz2, 8, 64, preact=True)
@@ -511,20 +520,31 @@ class _UpsampleCifarFn(torch.autograd.Function):
         # rcb_upconv_weff_grad is the faster one: 7.7 vs 11.1 us)
         dWeff1 = (torch.mm(lpe.t(), dz1f, out_dtype=torch.float32) if dz1f.dtype == torch.bfloat16 else lpe.t() @ dz1f)
         dW1, dW2, dW3, db1 = ops.upconv_weff_grad(dWeff1, dWeff2, dWeff3, db1_part)
-        return dlpe, dW1, db1, dW2, db2, dW3, db3, None, None, None, None, None
+        return dlpe, dW1, db1, dW2, db2, dW3, db3, None, None, None, None, None, None
 
 
-def upsample_cifar_hip(net, lpe, stage1_bf16=True, pe_bf16=True, frozen_cache=None, lpe16=None, weight_side_stream=None):
+def upsample_cifar_hip(net, lpe, stage1_bf16=True, pe_bf16=True, frozen_cache=None, lpe16=None, weight_side_stream=None,
+                       fwd_fused=None):
     """lpe [S, N, 2, 2, 128] -> pe [N, S, 1024, 16] (contiguous) through the HIP phase-conv kernels.
     `stage1_bf16` runs the stage-1 library GEMMs (fwd, dgrad, wgrad) with bf16 operands / fp32 accumulation and keeps
     z1 in bf16.  `pe_bf16` stores pe (and hence its gradient) as bf16: the 16-bit SIREN kernels and the stage-3
     gradient kernels round both to bf16 for their MFMA operands anyway, so the results are bit-identical to fp32
     storage at half the traffic.  The (small) lpe is reordered to INR-major so that pe needs no transpose.
-    `weight_side_stream`: a second stream for the weight-gradient side of the backward (_UpsampleCifarFn.backward)."""
+    `weight_side_stream`: a second stream for the weight-gradient side of the backward (_UpsampleCifarFn.backward).
+    `fwd_fused`: stages 2 and 3 of the forward as one launch (rcb_upconv_fwd23) where the combination exists -- bf16 z1 and
+    bf16 pe; same bits.  PriorTrainStep passes the field of its plan.  None takes ops.upconv_fwd23_enabled(), i.e. on unless
+    RCB_UPCONV_FWD_FUSED=0 -- and a caller with a `frozen_cache` (TestBNNmodel: one dict for the model's lifetime) takes it
+    ONCE, at its first call, and keeps it in that dict: the step graphs such a model captures are never replayed under another
+    setting than the one they were recorded with, whatever the environment says later."""
+    from . import ops
+    if fwd_fused is None:
+        fwd_fused = ops.upconv_fwd23_enabled()
+        if frozen_cache is not None:
+            fwd_fused = frozen_cache.setdefault("fwd_fused", fwd_fused)
     S, N = lpe.shape[:2]
     pe = _UpsampleCifarFn.apply(lpe.permute(1, 0, 2, 3, 4).reshape(N * S, 512), net.conv1.weight, net.conv1.bias,
                                 net.conv2.weight, net.conv2.bias, net.conv3.weight, net.conv3.bias, bool(stage1_bf16),
-                                bool(pe_bf16), frozen_cache, lpe16 if S == 1 else None, weight_side_stream)
+                                bool(pe_bf16), frozen_cache, lpe16 if S == 1 else None, weight_side_stream, bool(fwd_fused))
     return pe.view(N, S, 1024, 16)
 
 
