@@ -59,11 +59,11 @@ int64_t rcb_struct_bytes(int32_t which);
  * `wvec` row g holds the layer vectors back to back, each `[bias(out) | W(in,out) row-major]`
  * (prior_model.py:125-126); rows are w_row_stride floats apart.  G = N*S; sample s of INR n is
  * row g = n*S + s; targets / xf are indexed by n = g / S.
- * Hidden width 16, 24, 32, 48 or 64 in the 16-bit modes (16 / 24: one wave per row, siren_mlp_narrow.hip, F and E <= 32 each);
+ * Hidden width 16, 24, 32, 48 or 64 in the 16-bit modes (16 / 24: one wave per row, siren_mlp_rowwave.hip, F and E <= 32 each);
  * any width up to 64 in the fp32 mode (32 on the matrix cores, the others on a plain-FMA parity kernel, reference
  * prior_model.py:84-85); 1..7 hidden layers (8 linear layers: the A transform's RCB_ATRANS_MAX_LAYERS), out_dim <= 32,
  * F + E <= 64.  5..7 hidden layers take one width for every layer (no hidden_dims list): 16, 24 or 32 in the 16-bit modes (one
- * wave per row, siren_mlp_deep.hip, F, E and out_dim <= 32 each), any width up to 64 in the fp32 mode (plain-FMA parity kernel).
+ * wave per row, siren_mlp_rowwave.hip, F, E and out_dim <= 32 each), any width up to 64 in the fp32 mode (plain-FMA parity kernel).
  * precision: 0 = fp32 MFMA (exact fp32 products); 1 = bf16 operands, 2 = f16 operands (both fp32 accumulate;
  * f16 carries gradients scaled by 2^10 internally).
  * ------------------------------------------------------------------------------------------- */

@@ -22,14 +22,12 @@ using namespace rcb;
 #include "siren_common.h"
 
 namespace rcb {
-// uniform hidden width 16 or 24 in the 16-bit modes (siren_mlp_narrow.hip)
-int siren_narrow_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);
-inline bool siren_narrow(const rcb_siren_desc* d) {
-  return d->precision >= 1 && (d->hidden == 16 || d->hidden == 24) && d->hidden_dims[0] == 0 && d->n_hidden <= 4;
+// one wave per row in the 16-bit modes (siren_mlp_rowwave.hip): uniform hidden width 16 or 24 at 1 .. 4 hidden layers, and every
+// descriptor of 5 .. 7 hidden layers (one width 16, 24 or 32: fill_args)
+int siren_rowwave_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);
+inline bool siren_rowwave(const rcb_siren_desc* d) {
+  return d->precision >= 1 && (d->n_hidden >= 5 || ((d->hidden == 16 || d->hidden == 24) && d->hidden_dims[0] == 0));
 }
-// 5 .. 7 hidden layers of one width 16, 24 or 32 in the 16-bit modes (siren_mlp_deep.hip)
-int siren_deep_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);
-inline bool siren_deep(const rcb_siren_desc* d) { return d->precision >= 1 && d->n_hidden >= 5; }
 }  // namespace rcb
 
 namespace {
@@ -527,8 +525,7 @@ extern "C" int rcb_siren_fwd(const rcb_siren_desc* d, const float* xf, const voi
   a.pe = static_cast<const float*>(pe);
   a.wvec = wvec;
   a.yout = y_out;
-  if (siren_deep(d)) return siren_deep_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
-  if (siren_narrow(d)) return siren_narrow_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
+  if (siren_rowwave(d)) return siren_rowwave_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
   return dispatch<MODE_FWD>(d, a, (hipStream_t)stream);
 }
@@ -547,8 +544,7 @@ extern "C" int rcb_siren_bwd(const rcb_siren_desc* d, const float* xf, const voi
   a.yin = dy;
   a.dwvec = dwvec;
   a.dpe = static_cast<float*>(dpe);
-  if (siren_deep(d)) return siren_deep_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
-  if (siren_narrow(d)) return siren_narrow_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
+  if (siren_rowwave(d)) return siren_rowwave_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
   return dispatch<MODE_BWD>(d, a, (hipStream_t)stream);
 }
@@ -570,8 +566,7 @@ extern "C" int rcb_siren_loss_bwd(const rcb_siren_desc* d, const float* xf, cons
   a.dwvec = dwvec;
   a.dpe = static_cast<float*>(dpe);
   a.dy_scale = dy_scale;
-  if (siren_deep(d)) return siren_deep_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
-  if (siren_narrow(d)) return siren_narrow_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
+  if (siren_rowwave(d)) return siren_rowwave_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
   if (d->precision >= 1) return siren_16bit_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
   return dispatch<MODE_LOSS>(d, a, (hipStream_t)stream);
 }

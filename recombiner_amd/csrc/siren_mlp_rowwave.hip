@@ -1,10 +1,10 @@
-// Narrow SIRENs in the 16-bit modes: uniform hidden width 16 or 24, forward / backward / fused loss + backward.
+// One wave per row: the 16-bit SIREN kernels of the narrow family (uniform hidden width 16 or 24, 1 to 4 hidden layers) and of the
+// deep family (5 to 7 hidden layers of one width 16, 24 or 32), forward / backward / fused loss + backward.
 //
-// One WAVE (a 64-thread workgroup) per row of wvec -- an (INR, sample) -- or per pixel chunk of it.  At these widths everything a
-// row reuses fits in the wave's registers: the weight fragments of every layer in both orientations, the biases and the
-// weight-gradient accumulators of the whole row (layer 0 at F + E = 32, width 16: 2 tiles of 16 x 16, 8 registers per lane).  So
-// there is no barrier, no cross-wave reduction and no atomic: the pixel tiles of a row are summed in ascending order and the
-// row's gradient leaves straight from the accumulators -- the family is bitwise deterministic and batch invariant.
+// One WAVE (a 64-thread workgroup) per row of wvec -- an (INR, sample) -- or per pixel chunk of it.  There is no barrier across
+// waves, no cross-wave reduction and no atomic: the pixel tiles of a row are summed in ascending order and the row's gradient
+// leaves straight from the accumulators; which tiles a wave takes depends on P and pixel_chunks only, so the kernels are bitwise
+// deterministic and batch invariant.
 //
 // Matrix instruction: v_mfma_f32_16x16x32_{bf16,f16}, in the transposed orientation of the other SIREN kernels
 //      Z^T[out, pix] = W^T[out, in] * H^T[in, pix]        (N = 16 pixels on lane & 15, M = 16 output features, K = 32 inputs)
@@ -14,9 +14,20 @@
 // accumulator registers of a lane ARE its B operand, no data moves between lanes.  Width 16 leaves block 1 empty (zeros);
 // width 24 is carried as two blocks whose padding units 24..31 have zero weights and biases, so they are exactly 0 through
 // sin.  Their sines are not evaluated: the valid half-waves of block 1 of the tile's two 16-pixel halves are brought
-// together by v_permlane32_swap, one sin / cos per register pair instead of two.
+// together by v_permlane32_swap, one sin / cos per register pair instead of two.  Width 32 is two full blocks.
 // Layer 0 takes its K from both input halves at once: k-slot (g, j) of step s is Fourier feature 16 s + 8 g + j for g < 2 and
 // pe feature 16 s + 8 (g - 2) + j for g >= 2 -- a lane loads 8 consecutive features (16 bytes of a 16-bit row) of its pixel.
+//
+// Where a row's weights live is the one thing that differs between the families, and it is a type (the weights store):
+//   * RegStore (1 to 4 layers): at these depths everything a row reuses fits in the wave's registers -- the weight fragments of
+//     every layer in both orientations and the biases, next to the weight-gradient accumulators of the whole row.  The row of
+//     layer vectors is staged through LDS once, in the area the tile images use afterwards.
+//   * LdsStore (5 to 7 layers): 7 layers of width 32 would be ~ 270 registers of weights next to the accumulators.  The fragments
+//     are built once per row into LDS in lane order (slot k: 64 lanes x 16 bytes, one conflict-free ds_read_b128 per MFMA
+//     operand), the biases as 16 floats per 16-unit block (read by k-group).  The row is staged one layer vector at a time (the
+//     largest is 32 x 65 floats) through the image area, so that the LDS of a wave is the fragments plus the images: <= 60 KB.
+// Both are addressed by the slot map of Geo, and the fragment values are built by one routine.  The kernel body only calls the
+// store; a fragment is fetched once and used for both halves of the tile.
 //
 // Weight gradient dW^T[out, in] += dZ^T[out, pix] H[pix, in] contracts over pixels, which sit on the lanes: the tile's layer
 // inputs (written in the forward pass) and its dz (written in the backward pass) go through the wave's LDS as [feature][pixel]
@@ -25,9 +36,11 @@
 // 80 bytes apart: conflict-free).  Bias gradients are the sums of the same dz operands (v_dot2 against ones).
 //
 // Rounding is that of the width-32 16-bit kernels: weights, layer inputs, sines and dz rounded to the operand type, fp32
-// accumulation; the sine layers work in revolutions (w0 / 2 pi folded into their forward fragments and biases), the
-// data-gradient fragments of the hidden and output layers carry w0, f16 scales weights and gradients by 2^10 (Op16).
+// accumulation and fp32 cosines; the sine layers work in revolutions (w0 / 2 pi folded into their forward fragments and biases),
+// the data-gradient fragments of the hidden and output layers carry w0, f16 scales weights and gradients by 2^10 (Op16).
 // Matches prior_model.py:168-179,237 and test_model.py:347-355,625-627 like the kernels it stands beside.
+#include <type_traits>
+
 #include "siren_op16.h"
 
 using namespace rcb;
@@ -49,17 +62,74 @@ constexpr int IST = 40;   // row stride of the LDS images in 16-bit elements (32
 
 // KS: k-steps of layer 0 (1: F, E <= 16; 2: F, E <= 32); also the bound on the 16-wide blocks of out_dim and pe_dim
 template <int NH, int HW, int KS>
-struct NGeo {
+struct Geo {
   static constexpr int HB = (HW + 15) / 16;        // 16-feature blocks of a hidden layer
   static constexpr int NL = NH + 1;
   static constexpr int IB0 = 2 * KS;               // 16-feature blocks of layer 0's input (at most)
   static constexpr int CB = KS, EB = KS;           // ... of out_dim, of pe_dim (at most)
   static constexpr int DZB = HB > CB ? HB : CB;
+  // fragment slots (64 lanes x 8 16-bit elements each)
+  static constexpr int S_F0 = 0;                   // forward, layer 0: [KS][HB]
+  static constexpr int S_FH = S_F0 + KS * HB;      // forward, hidden layers 1 .. NH - 1: [NH - 1][HB]
+  static constexpr int S_FO = S_FH + (NH - 1) * HB;   // forward, output layer: [CB]
+  static constexpr int S_BO = S_FO + CB;           // data gradient through the output layer: [HB]
+  static constexpr int S_BH = S_BO + HB;           // ... through hidden layers 1 .. NH - 1: [NH - 1][HB]
+  static constexpr int S_BE = S_BH + (NH - 1) * HB;   // ... of pe through layer 0: [EB]
+  static constexpr int NFRAG = S_BE + EB;
+  static constexpr int NBIAS = NH * HB + CB;       // bias blocks (16 floats each): block b of layer l is l * HB + b
   // LDS image rows: layer 0's input, the inputs of layers 1 .. NH (sines), dz
   static constexpr int X_ROWS = 16 * IB0;
   static constexpr int S_ROWS = 16 * HB;
   static constexpr int ROWS = X_ROWS + NH * S_ROWS + 16 * DZB;
   static constexpr int IMG_BYTES = ROWS * IST * 2;
+  // floats of the largest layer vector, bias and weights: layer 0 (32 KS inputs) or a layer of 32 KS outputs
+  static constexpr int LAYER_MAX = HW * (32 * KS + 1) > 32 * KS * (HW + 1) ? HW * (32 * KS + 1) : 32 * KS * (HW + 1);
+  // the input rows of the next tile are loaded during this one, except at 7 layers of width 24 / 32 with two k-steps in layer 0,
+  // where their 32 registers would push the accumulators into scratch: there the tile's rows are loaded at its start
+  static constexpr bool PREFETCH = !(NH == 7 && HB == 2 && KS == 2);
+};
+
+// ---- the weights stores: a row's fragments (by slot) and bias blocks; the LDS behind the fixed part is the work area, which
+// holds the staged layer vectors first and the tile images afterwards ----------------------------------------------------------
+template <typename T, class G>
+struct RegStore {
+  using v8 = typename Op16<T>::v8;
+  static constexpr bool WHOLE_ROW = true;          // the row of layer vectors is staged once, then every layer is built
+  static constexpr int STAGE_LOADS = 16;           // global loads a lane keeps in flight while staging
+  static constexpr int FIXED_BYTES = 0;
+  static size_t lds_bytes(int dnet) { return (size_t)(G::IMG_BYTES > dnet * 4 ? G::IMG_BYTES : dnet * 4); }
+  // every loop over slots is fully unrolled: the indices are constants and the arrays are registers
+  v8 fr[G::NFRAG];
+  f32x4 bi[G::NBIAS];
+  __device__ __forceinline__ RegStore(unsigned char*, int) {}
+  __device__ __forceinline__ void put_frag(int slot, const v8& v) { fr[slot] = v; }
+  __device__ __forceinline__ void put_bias(int blk, const f32x4& v) { bi[blk] = v; }
+  __device__ __forceinline__ v8 frag(int slot) const { return fr[slot]; }
+  __device__ __forceinline__ f32x4 bias(int blk) const { return bi[blk]; }
+};
+
+template <typename T, class G>
+struct LdsStore {
+  using v8 = typename Op16<T>::v8;
+  static constexpr bool WHOLE_ROW = false;         // one layer vector at a time: stage, build, next
+  static constexpr int STAGE_LOADS = 8;
+  static constexpr int FRAG_BYTES = G::NFRAG * 64 * 16;
+  static constexpr int FIXED_BYTES = FRAG_BYTES + G::NBIAS * 16 * 4;
+  static constexpr int LDS_BYTES = FIXED_BYTES + (G::IMG_BYTES > 4 * G::LAYER_MAX ? G::IMG_BYTES : 4 * G::LAYER_MAX);
+  static_assert(LDS_BYTES <= 64 * 1024, "one wave's LDS stays within the default dynamic limit");
+  static size_t lds_bytes(int) { return LDS_BYTES; }
+  T* const my_frag;             // this lane's 16 bytes of slot 0
+  float* const my_bias;         // this lane's k-group of bias block 0
+  const bool writes_bias;
+  __device__ __forceinline__ LdsStore(unsigned char* smem, int lane)
+      : my_frag(reinterpret_cast<T*>(smem) + lane * 8), my_bias(reinterpret_cast<float*>(smem + FRAG_BYTES) + 4 * (lane >> 4)),
+        writes_bias((lane & 15) == 0) {}
+  __device__ __forceinline__ void put_frag(int slot, const v8& v) { *reinterpret_cast<v8*>(my_frag + slot * 512) = v; }
+  __device__ __forceinline__ void put_bias(int blk, const f32x4& v) {
+    if (writes_bias) *reinterpret_cast<f32x4*>(my_bias + blk * 16) = v;
+  }
+  __device__ __forceinline__ v8 frag(int slot) const { return *reinterpret_cast<const v8*>(my_frag + slot * 512); }
+  __device__ __forceinline__ f32x4 bias(int blk) const { return *reinterpret_cast<const f32x4*>(my_bias + blk * 16); }
 };
 
 // k-slot (g, j) of a B operand packed from accumulator blocks -> feature index
@@ -83,15 +153,25 @@ __device__ __forceinline__ f32x4 zero4() {
   return z;
 }
 
+// A dz is an fp32 product, rounded to fp32 and then to the operand type.  Left to itself the compiler merges product and
+// conversion of the f16 instances into one v_fma_mixlo_f16 -- a single rounding -- but only where both land in one basic block,
+// so that the rounding of a dz element depended on code placement (of the two halves of a tile, one was merged).  The product
+// passes through here before its conversion and reaches it as an fp32 value.
+template <typename T>
+__device__ __forceinline__ float fp32_value(float x) {
+  if constexpr (!Op16<T>::IS_BF16) asm("" : "+v"(x));
+  return x;
+}
+
 __device__ __forceinline__ float swap_lo_hi(float& x, float y) {   // x <- [x.lo | y.lo], returns [x.hi | y.hi]
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
   x = __uint_as_float(r[0]);
   return __uint_as_float(r[1]);
 }
 
-template <typename T, int NH, int HW, int KS, bool FWD>
-__global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
-  using G = NGeo<NH, HW, KS>;
+template <typename T, int NH, int HW, int KS, bool FWD, class Store>
+__global__ void __launch_bounds__(64) siren_rowwave_kernel(SirenArgs a) {
+  using G = Geo<NH, HW, KS>;
   using v8 = typename Op16<T>::v8;
   using v2 = typename Op16<T>::v2;
   constexpr float GS = Op16<T>::GRAD_SCALE;
@@ -112,115 +192,130 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
   auto loff = [&](int l) { return l == 0 ? 0 : off1 + (l - 1) * HW * (HW + 1); };
   const int offo = loff(NH);
 
-  // ---- stage the row of layer vectors in LDS, build the fragments ---------------------------------------------------
-  float* wl = reinterpret_cast<float*>(smem_raw);
-  {
-    const float* src = a.wvec + (long long)row * a.w_stride;
-    for (int i0 = lane; i0 < a.dnet; i0 += 16 * 64) {
-      float st[16];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int i = i0 + 64 * k;
-        st[k] = src[i < a.dnet ? i : a.dnet - 1];
-      }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const int i = i0 + 64 * k;
-        if (i < a.dnet) wl[i] = st[k];
-      }
-    }
-    __syncthreads();
-  }
-  const float kw = a.k_hi * WS;                // sine layers: revolutions, f16 weight scale
-  // forward A fragments: lane (m, g4) element j = W[in of k-slot (g4, j)][out 16 ob + m]
-  v8 fr0[KS][HB], frh[NH > 1 ? NH - 1 : 1][HB], fro[G::CB];
-  // data-gradient A fragments: lane (m, g4) element j = W[in 16 ib + m][out of k-slot (g4, j)]
-  v8 fbo[HB], fbh[NH > 1 ? NH - 1 : 1][HB], fbe[G::EB];
-  f32x4 bias[NH][HB], biaso[G::CB];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int kf = kfeat(g4, j);
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const int f0 = 16 * s + 8 * (g4 & 1) + j;
-      const bool ok_in = g4 < 2 ? f0 < F : f0 < E;
-      const int in = g4 < 2 ? f0 : F + f0;
-#pragma unroll
-      for (int ob = 0; ob < HB; ++ob) {
-        const int out = 16 * ob + m;
-        const bool ok = ok_in && out < HW;
-        const float v = wl[ok ? HW + in * HW + out : 0];
-        fr0[s][ob][j] = (T)(ok ? v * kw : 0.f);
-      }
-    }
-#pragma unroll
-    for (int l = 1; l < NH; ++l) {
-#pragma unroll
-      for (int ob = 0; ob < HB; ++ob) {
-        const int out = 16 * ob + m;
-        const bool ok = kf < HW && out < HW;
-        const float v = wl[ok ? loff(l) + HW + kf * HW + out : 0];
-        frh[l - 1][ob][j] = (T)(ok ? v * kw : 0.f);
-      }
-#pragma unroll
-      for (int ib = 0; ib < HB; ++ib) {
-        const int in = 16 * ib + m;
-        const bool ok = kf < HW && in < HW;
-        const float v = wl[ok ? loff(l) + HW + in * HW + kf : 0];
-        fbh[l - 1][ib][j] = (T)(ok ? v * a.w0 : 0.f);
-      }
-    }
-#pragma unroll
-    for (int cb = 0; cb < G::CB; ++cb) {
-      const int out = 16 * cb + m;
-      const bool ok = kf < HW && out < C;
-      const float v = wl[ok ? offo + C + kf * C + out : 0];
-      fro[cb][j] = (T)(ok ? v * WS : 0.f);
-    }
-#pragma unroll
-    for (int ib = 0; ib < HB; ++ib) {
-      const int in = 16 * ib + m;
-      const bool ok = kf < C && in < HW;
-      const float v = wl[ok ? offo + C + in * C + kf : 0];
-      fbo[ib][j] = (T)(ok ? v * a.w0 : 0.f);
-    }
-#pragma unroll
-    for (int eb = 0; eb < G::EB; ++eb) {
-      const int e = 16 * eb + m;
-      const bool ok = kf < HW && e < E;
-      const float v = wl[ok ? HW + (F + e) * HW + kf : 0];
-      fbe[eb][j] = (T)(ok ? v * WS : 0.f);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int l = 0; l < NH; ++l)
-#pragma unroll
-      for (int ob = 0; ob < HB; ++ob) {
-        const int f = 16 * ob + 4 * g4 + i;
-        const float v = wl[loff(l) + (f < HW ? f : 0)];
-        bias[l][ob][i] = f < HW ? v * kw : 0.f;
-      }
-#pragma unroll
-    for (int cb = 0; cb < G::CB; ++cb) {
-      const int c = 16 * cb + 4 * g4 + i;
-      const float v = wl[offo + (c < C ? c : 0)];
-      biaso[cb][i] = c < C ? v : 0.f;
-    }
-  }
-  __syncthreads();          // the images below reuse the staging area
+  Store W(smem_raw, lane);
+  unsigned char* const work = smem_raw + Store::FIXED_BYTES;
 
-  T* const img = reinterpret_cast<T*>(smem_raw);
+  // ---- fragments and biases of the row, from its layer vectors staged in the work area ---------------------------------------
+  const float kw = a.k_hi * WS;                // sine layers: revolutions, f16 weight scale
+  {
+    const float* src_row = a.wvec + (long long)row * a.w_stride;
+    float* const wl = reinterpret_cast<float*>(work);
+    auto stage = [&](const float* src, float* dst, int len) {
+      for (int i0 = lane; i0 < len; i0 += Store::STAGE_LOADS * 64) {
+        float st[Store::STAGE_LOADS];
+#pragma unroll
+        for (int k = 0; k < Store::STAGE_LOADS; ++k) {
+          const int i = i0 + 64 * k;
+          st[k] = src[i < len ? i : len - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < Store::STAGE_LOADS; ++k) {
+          const int i = i0 + 64 * k;
+          if (i < len) dst[i] = st[k];
+        }
+      }
+      __syncthreads();
+    };
+    // an A fragment: element j of lane (m, g4) is wv[idx] * scale rounded to the operand type where at(j, idx) holds, else 0
+    // (validity and index stay two values: folded into one signed index, the scalar registers of the tile loop spill twice as much)
+    auto a_frag = [&](const float* wv, float scale, auto at) -> v8 {
+      v8 fr;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        int i;
+        const bool ok = at(j, i);
+        const float v = wv[ok ? i : 0];
+        fr[j] = (T)(ok ? v * scale : 0.f);
+      }
+      return fr;
+    };
+    // layer l from its vector wv = [bias | W(in, out)].  Forward fragments: element j = W[in of k-slot (g4, j)][out 16 ob + m];
+    // data-gradient fragments: element j = W[in 16 ib + m][out of k-slot (g4, j)]
+    auto build_layer = [&](int l, const float* wv) {
+      if (l == 0) {
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+#pragma unroll
+          for (int ob = 0; ob < HB; ++ob)
+            W.put_frag(G::S_F0 + s * HB + ob, a_frag(wv, kw, [&](int j, int& idx) {
+              const int f0 = 16 * s + 8 * (g4 & 1) + j, out = 16 * ob + m;
+              const bool ok_in = g4 < 2 ? f0 < F : f0 < E;
+              idx = HW + (g4 < 2 ? f0 : F + f0) * HW + out;
+              return ok_in && out < HW;
+            }));
+#pragma unroll
+        for (int eb = 0; eb < G::EB; ++eb)       // pe data gradient: rows F + 16 eb + m
+          W.put_frag(G::S_BE + eb, a_frag(wv, WS, [&](int j, int& idx) {
+            const int kf = kfeat(g4, j), e = 16 * eb + m;
+            idx = HW + (F + e) * HW + kf;
+              return kf < HW && e < E;
+          }));
+      } else if (l < NH) {
+#pragma unroll
+        for (int b = 0; b < HB; ++b) {
+          const int u = 16 * b + m;
+          W.put_frag(G::S_FH + (l - 1) * HB + b, a_frag(wv, kw, [&](int j, int& idx) {
+            const int kf = kfeat(g4, j);
+            idx = HW + kf * HW + u;
+              return kf < HW && u < HW;
+          }));
+          W.put_frag(G::S_BH + (l - 1) * HB + b, a_frag(wv, a.w0, [&](int j, int& idx) {
+            const int kf = kfeat(g4, j);
+            idx = HW + u * HW + kf;
+              return kf < HW && u < HW;
+          }));
+        }
+      } else {
+#pragma unroll
+        for (int cb = 0; cb < G::CB; ++cb)
+          W.put_frag(G::S_FO + cb, a_frag(wv, WS, [&](int j, int& idx) {
+            const int kf = kfeat(g4, j), out = 16 * cb + m;
+            idx = C + kf * C + out;
+              return kf < HW && out < C;
+          }));
+#pragma unroll
+        for (int ib = 0; ib < HB; ++ib)
+          W.put_frag(G::S_BO + ib, a_frag(wv, a.w0, [&](int j, int& idx) {
+            const int kf = kfeat(g4, j), in = 16 * ib + m;
+            idx = C + in * C + kf;
+              return kf < C && in < HW;
+          }));
+      }
+      // bias blocks: lane (m, g4) holds units 16 b + 4 g4 + 0..3, in revolutions for the sine layers
+#pragma unroll
+      for (int b = 0; b < G::DZB; ++b) {
+        if (b >= (l < NH ? HB : G::CB)) continue;
+        f32x4 bv;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int u = 16 * b + 4 * g4 + i;
+          const bool ok = u < (l < NH ? HW : C);
+          const float v = wv[ok ? u : 0];
+          bv[i] = ok ? (l < NH ? v * kw : v) : 0.f;
+        }
+        W.put_bias(l * HB + b, bv);
+      }
+    };
+    if constexpr (Store::WHOLE_ROW) {
+      stage(src_row, wl, a.dnet);
+#pragma unroll
+      for (int l = 0; l < NL; ++l) build_layer(l, wl + loff(l));
+      __syncthreads();        // the images below reuse the staging area
+    } else {
+#pragma unroll 1
+      for (int l = 0; l < NL; ++l) {
+        stage(src_row + loff(l), wl, l == 0 ? off1 : (l == NH ? C * (HW + 1) : HW * (HW + 1)));
+        build_layer(l, wl);
+        __syncthreads();      // the next layer (or the images) reuse the staging area
+      }
+    }
+  }
+
+  T* const img = reinterpret_cast<T*>(work);
   T* const x_img = img;                                                        // layer 0's input: rows = input features
   auto s_img = [&](int l) { return img + (G::X_ROWS + (l - 1) * G::S_ROWS) * IST; };   // input of layer l >= 1
   T* const dz_img = img + (G::X_ROWS + NH * G::S_ROWS) * IST;
-  // a feature's pixel pair (2 m, 2 m + 1) -> one 4-byte store
-  auto put_pair = [&](T* im, int r, float v0, float v1) {
-    v2 pr = {(T)v0, (T)v1};
-    *reinterpret_cast<v2*>(im + r * IST + 2 * m) = pr;
-  };
-  auto put_pair16 = [&](T* im, int r, T v0, T v1) {
+  auto put_pair16 = [&](T* im, int r, T v0, T v1) {       // a feature's pixel pair (2 m, 2 m + 1) -> one 4-byte store
     v2 pr = {v0, v1};
     *reinterpret_cast<v2*>(im + r * IST + 2 * m) = pr;
   };
@@ -325,9 +420,10 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
   };
 
   const int t0 = (int)((long long)chunk * ntiles / a.chunks), t1 = (int)((long long)(chunk + 1) * ntiles / a.chunks);
-  fetch(t0);
+  if (G::PREFETCH) fetch(t0);
   fetch_y(t0);
   for (int t = t0; t < t1; ++t) {
+    if (!G::PREFETCH) fetch(t);
     bool valid[2];
     int pix[2];
 #pragma unroll
@@ -349,7 +445,7 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) yv[ph][cb][i] = ynext[ph][cb][i];
     }
-    fetch(t + 1 < t1 ? t + 1 : t);
+    if (G::PREFETCH) fetch(t + 1 < t1 ? t + 1 : t);
     fetch_y(t + 1 < t1 ? t + 1 : t);
 
     // ---- forward ----------------------------------------------------------------------------------------------------
@@ -369,29 +465,38 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
     for (int l = 0; l < NH; ++l) {
       f32x4 z[2][HB];
 #pragma unroll
-      for (int ph = 0; ph < 2; ++ph)
+      for (int ob = 0; ob < HB; ++ob) {
+        const f32x4 b0 = W.bias(l * HB + ob);
+        f32x4 acc[2] = {b0, b0};
+        if (l == 0) {
 #pragma unroll
-        for (int ob = 0; ob < HB; ++ob) {
-          f32x4 acc = bias[l][ob];
-          if (l == 0) {
+          for (int s = 0; s < KS; ++s) {
+            const v8 w = W.frag(G::S_F0 + s * HB + ob);
 #pragma unroll
-            for (int s = 0; s < KS; ++s) acc = mfma16<T>(fr0[s][ob], xb[ph][s], acc);
-          } else {
-            acc = mfma16<T>(frh[l - 1][ob], hb[ph], acc);
+            for (int ph = 0; ph < 2; ++ph) acc[ph] = mfma16<T>(w, xb[ph][s], acc[ph]);
           }
+        } else {
+          const v8 w = W.frag(G::S_FH + (l - 1) * HB + ob);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) z[ph][ob][i] = (WS == 1.0f) ? acc[i] : acc[i] * (1.0f / WS);   // revolutions
+          for (int ph = 0; ph < 2; ++ph) acc[ph] = mfma16<T>(w, hb[ph], acc[ph]);
         }
+#pragma unroll
+        for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) z[ph][ob][i] = (WS == 1.0f) ? acc[ph][i] : acc[ph][i] * (1.0f / WS);   // revolutions
+      }
       f32x4 sv[2][HB], cv[2][HB];
+      constexpr int FULL = HW / 16;                  // blocks with 16 units
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          sv[ph][0][i] = __builtin_amdgcn_sinf(z[ph][0][i]);
-          if (!FWD) cv[ph][0][i] = __builtin_amdgcn_cosf(z[ph][0][i]);
-        }
-      if constexpr (HB == 2) {
-        static_assert(HW == 24, "block 1 holds 8 units: lanes 0..31");
+        for (int ob = 0; ob < FULL; ++ob)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            sv[ph][ob][i] = __builtin_amdgcn_sinf(z[ph][ob][i]);
+            if (!FWD) cv[ph][ob][i] = __builtin_amdgcn_cosf(z[ph][ob][i]);
+          }
+      if constexpr (HW == 24) {
         // block 1: units 16..23 sit in lanes 0..31; the two halves' valid lanes are paired in one register
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -424,14 +529,17 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
     }
     f32x4 yo[2][G::CB];
 #pragma unroll
-    for (int ph = 0; ph < 2; ++ph)
+    for (int cb = 0; cb < G::CB; ++cb) {
+      if (cb >= cb_n) continue;
+      const v8 w = W.frag(G::S_FO + cb);
+      const f32x4 bo = W.bias(NH * HB + cb);
 #pragma unroll
-      for (int cb = 0; cb < G::CB; ++cb) {
-        if (cb >= cb_n) continue;
-        f32x4 acc = mfma16<T>(fro[cb], hb[ph], zero4());
+      for (int ph = 0; ph < 2; ++ph) {
+        const f32x4 acc = mfma16<T>(w, hb[ph], zero4());
 #pragma unroll
-        for (int i = 0; i < 4; ++i) yo[ph][cb][i] = ((WS == 1.0f) ? acc[i] : acc[i] * (1.0f / WS)) + biaso[cb][i];
+        for (int i = 0; i < 4; ++i) yo[ph][cb][i] = ((WS == 1.0f) ? acc[i] : acc[i] * (1.0f / WS)) + bo[i];
       }
+    }
     if (FWD) {
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph) {
@@ -463,7 +571,7 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
           if (loss) {
             const float diff = ok ? yo[ph][b][i] - yv[ph][b][i] : 0.f;
             sse_local += diff * diff;
-            dz[ph][b][i] = (2.0f * GS) * a.dy_scale * diff;
+            dz[ph][b][i] = fp32_value<T>((2.0f * GS) * a.dy_scale * diff);
           } else {
             dz[ph][b][i] = ok ? yv[ph][b][i] * GS : 0.f;
           }
@@ -471,12 +579,12 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
       }
 
     // ---- backward, output layer down to layer 0 ----------------------------------------------------------------------
+    v8 dzb[2];
+#pragma unroll
+    for (int ph = 0; ph < 2; ++ph) dzb[ph] = pack_blocks<T>(dz[ph][0], dz[ph][G::DZB - 1], G::DZB == 2 && cb_n == 2);
 #pragma unroll
     for (int l = NL - 1; l >= 0; --l) {
       const int nb = (l == NL - 1) ? cb_n : HB;           // 16-row blocks of dz_l
-      v8 dzb[2];
-#pragma unroll
-      for (int ph = 0; ph < 2; ++ph) dzb[ph] = pack_blocks<T>(dz[ph][0], dz[ph][G::DZB - 1], G::DZB == 2 && nb == 2);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
       for (int b = 0; b < G::DZB; ++b) {
@@ -486,25 +594,29 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
       }
       // (1) data gradient: dH_{l-1}^T[in, pix] = W_l[in, :] dz_l  (w0 in the fragments), times the cosine of layer l - 1
       if (l > 0) {
+        f32x4 dh[2][HB];
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph)
+        for (int ib = 0; ib < HB; ++ib) {
+          const v8 w = W.frag(l == NL - 1 ? G::S_BO + ib : G::S_BH + (l - 1) * HB + ib);
 #pragma unroll
-          for (int ib = 0; ib < HB; ++ib) {
-            const f32x4 dh = mfma16<T>(l == NL - 1 ? fbo[ib] : fbh[l - 1 < NH - 1 ? l - 1 : 0][ib], dzb[ph], zero4());
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dz[ph][ib][i] = dh[i] * Cf[l - 1][ph][ib][i];
-          }
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-          for (int b = HB; b < G::DZB; ++b) dz[ph][b] = zero4();
-      } else if (a.dpe != nullptr) {
+          for (int ph = 0; ph < 2; ++ph) dh[ph][ib] = mfma16<T>(w, dzb[ph], zero4());
+        }
 #pragma unroll
         for (int ph = 0; ph < 2; ++ph) {
 #pragma unroll
-          for (int eb = 0; eb < G::EB; ++eb) {
-            if (eb >= eb_n) continue;
-            const f32x4 dx = mfma16<T>(fbe[eb], dzb[ph], zero4());
+          for (int j = 0; j < 4; ++j) {
+            dzb[ph][j] = (T)fp32_value<T>(dh[ph][0][j] * Cf[l - 1][ph][0][j]);
+            dzb[ph][4 + j] = HB == 2 ? (T)fp32_value<T>(dh[ph][HB - 1][j] * Cf[l - 1][ph][HB - 1][j]) : (T)0.0f;
+          }
+        }
+      } else if (a.dpe != nullptr) {
+#pragma unroll
+        for (int eb = 0; eb < G::EB; ++eb) {
+          if (eb >= eb_n) continue;
+          const v8 w = W.frag(G::S_BE + eb);
+#pragma unroll
+          for (int ph = 0; ph < 2; ++ph) {
+            const f32x4 dx = mfma16<T>(w, dzb[ph], zero4());
             if (!valid[ph]) continue;
             const int e0 = 16 * eb + 4 * g4;
             const long long o = (pe_row + pe_pix_off(a, pix[ph])) * E + e0;
@@ -618,45 +730,64 @@ __global__ void __launch_bounds__(64) siren_narrow_kernel(SirenArgs a) {
   }
 }
 
+// up to 4 hidden layers keep the row's weights in registers, 5 to 7 in LDS
 template <typename T, int NH, int HW, int KS>
 int launch(int mode, const SirenArgs& a, hipStream_t st) {
-  using G = NGeo<NH, HW, KS>;
-  const size_t lds = (size_t)(G::IMG_BYTES > a.dnet * 4 ? G::IMG_BYTES : a.dnet * 4);
-  if (mode == MODE_FWD) siren_narrow_kernel<T, NH, HW, KS, true><<<a.G * a.chunks, 64, lds, st>>>(a);
-  else siren_narrow_kernel<T, NH, HW, KS, false><<<a.G * a.chunks, 64, lds, st>>>(a);
+  using G = Geo<NH, HW, KS>;
+  using Store = std::conditional_t<(NH <= 4), RegStore<T, G>, LdsStore<T, G>>;
+  const size_t lds = Store::lds_bytes(a.dnet);
+  if (mode == MODE_FWD) siren_rowwave_kernel<T, NH, HW, KS, true, Store><<<a.G * a.chunks, 64, lds, st>>>(a);
+  else siren_rowwave_kernel<T, NH, HW, KS, false, Store><<<a.G * a.chunks, 64, lds, st>>>(a);
   RCB_LAUNCH_CHECK();
   return RCB_OK;
 }
 
 template <typename T, int HW, int KS>
 int launch_nh(int mode, int nh, const SirenArgs& a, hipStream_t st) {
+  if constexpr (HW < 32) {          // 1 .. 4 layers of width 32 belong to the workgroup and wave families
+    switch (nh) {
+      case 1: return launch<T, 1, HW, KS>(mode, a, st);
+      case 2: return launch<T, 2, HW, KS>(mode, a, st);
+      case 3: return launch<T, 3, HW, KS>(mode, a, st);
+      case 4: return launch<T, 4, HW, KS>(mode, a, st);
+      default: break;
+    }
+  }
   switch (nh) {
-    case 1: return launch<T, 1, HW, KS>(mode, a, st);
-    case 2: return launch<T, 2, HW, KS>(mode, a, st);
-    case 3: return launch<T, 3, HW, KS>(mode, a, st);
-    default: return launch<T, 4, HW, KS>(mode, a, st);
+    case 5: return launch<T, 5, HW, KS>(mode, a, st);
+    case 6: return launch<T, 6, HW, KS>(mode, a, st);
+    case 7: return launch<T, 7, HW, KS>(mode, a, st);
+    default: return rcb::fail(RCB_ERR_UNSUPPORTED, "siren: no one-wave-per-row instance for %d hidden layers of width %d", nh, HW);
   }
 }
 
 template <typename T>
 int launch_t(int mode, const rcb_siren_desc* d, const SirenArgs& a, hipStream_t st) {
   const bool small = d->fourier_dim <= 16 && d->pe_dim <= 16 && d->out_dim <= 16;
-  if (d->hidden == 16) return small ? launch_nh<T, 16, 1>(mode, d->n_hidden, a, st) : launch_nh<T, 16, 2>(mode, d->n_hidden, a, st);
-  return small ? launch_nh<T, 24, 1>(mode, d->n_hidden, a, st) : launch_nh<T, 24, 2>(mode, d->n_hidden, a, st);
+  const int nh = d->n_hidden;
+  if (d->hidden == 16) return small ? launch_nh<T, 16, 1>(mode, nh, a, st) : launch_nh<T, 16, 2>(mode, nh, a, st);
+  if (d->hidden == 24) return small ? launch_nh<T, 24, 1>(mode, nh, a, st) : launch_nh<T, 24, 2>(mode, nh, a, st);
+  return small ? launch_nh<T, 32, 1>(mode, nh, a, st) : launch_nh<T, 32, 2>(mode, nh, a, st);
 }
 
 }  // namespace
 
 namespace rcb {
-// hidden width 16 / 24, one width for every hidden layer, 16-bit modes (descriptor checked by siren_mlp.hip's fill_args)
-int siren_narrow_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
-  RCB_REQUIRE(d->fourier_dim <= 32 && d->pe_dim <= 32, RCB_ERR_UNSUPPORTED,
-              "siren(narrow): F=%d E=%d (the width-16 / 24 kernels take up to 32 features from each input half)", d->fourier_dim,
-              d->pe_dim);
-  RCB_REQUIRE(d->clock_probe == nullptr, RCB_ERR_UNSUPPORTED, "siren(narrow): clock_probe exists in the width-32 kernel only");
-  RCB_REQUIRE(mode != MODE_LOSS || a.sse != nullptr, RCB_ERR_ARG, "siren(narrow): sse");
-  const int in0 = d->fourier_dim + d->pe_dim, hw = d->hidden;
-  a.dnet = hw * (in0 + 1) + (d->n_hidden - 1) * hw * (hw + 1) + d->out_dim * (hw + 1);
+// 16-bit modes, one width for every hidden layer: 1 .. 4 layers of width 16 / 24 (narrow), 5 .. 7 layers of width 16 / 24 / 32
+// (deep); the descriptor is checked by siren_mlp.hip's fill_args
+int siren_rowwave_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
+  const int nh = d->n_hidden, hw = d->hidden;
+  const char* fam = nh >= 5 ? "deep" : "narrow";
+  RCB_REQUIRE(nh >= 1 && nh <= 7 && (hw == 16 || hw == 24 || (hw == 32 && nh >= 5)) && d->hidden_dims[0] == 0, RCB_ERR_UNSUPPORTED,
+              "siren(%s): %d hidden layers of width %d (1..4 layers of one width 16 or 24, 5..7 layers of one width 16, 24 or 32)", fam,
+              nh, hw);
+  RCB_REQUIRE(d->fourier_dim <= 32 && d->pe_dim <= 32 && d->out_dim <= 32, RCB_ERR_UNSUPPORTED,
+              "siren(%s): F=%d E=%d C=%d (the one-wave-per-row kernels take up to 32 features from each input half and 32 outputs)", fam,
+              d->fourier_dim, d->pe_dim, d->out_dim);
+  RCB_REQUIRE(d->clock_probe == nullptr, RCB_ERR_UNSUPPORTED, "siren(%s): clock_probe exists in the width-32 kernel of 1..4 layers only", fam);
+  RCB_REQUIRE(mode != MODE_LOSS || a.sse != nullptr, RCB_ERR_ARG, "siren(%s): sse", fam);
+  const int in0 = d->fourier_dim + d->pe_dim;
+  a.dnet = hw * (in0 + 1) + (nh - 1) * hw * (hw + 1) + d->out_dim * (hw + 1);
   if (mode == MODE_BWD) a.sse = nullptr;          // the kernel tells loss from backward by the sse pointer
   return d->precision == 2 ? launch_t<_Float16>(mode, d, a, st) : launch_t<__bf16>(mode, d, a, st);
 }

@@ -1,4 +1,4 @@
-"""The arithmetic of the 16-bit SIREN kernels (recombiner_amd/csrc/siren_mlp_{bf16,wave,wide,narrow,deep}.hip) in fp64 on the CPU.
+"""The arithmetic of the 16-bit SIREN kernels (recombiner_amd/csrc/siren_mlp_{bf16,wave,wide,rowwave}.hip) in fp64 on the CPU.
 
 Plain torch, float64.  Values are rounded to the operand type (bf16 or f16, round to nearest even) at exactly the points where
 the kernels round them; sums, products, sines and cosines in between are fp64, i.e. exact at the scale of anything compared

@@ -1,4 +1,4 @@
-"""Deep SIRENs (5 to 7 hidden layers of one width): the 16-bit kernel family (siren_mlp_deep.hip) against an fp32 restatement of
+"""Deep SIRENs (5 to 7 hidden layers of one width): the 16-bit kernel family (siren_mlp_rowwave.hip) against an fp32 restatement of
 the MLP and a CPU emulation of its operand rounding, its input layouts and options against the plain launch, the fp32 parity
 path at depth, and the models / drivers at depth against the CPU oracle (run with -m gpu; the descriptor check runs without)."""
 import math

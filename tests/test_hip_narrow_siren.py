@@ -1,4 +1,4 @@
-"""Narrow SIRENs (uniform hidden width 16 / 24) in the 16-bit modes (siren_mlp_narrow.hip): the kernel family against an fp32
+"""Narrow SIRENs (uniform hidden width 16 / 24) in the 16-bit modes (siren_mlp_rowwave.hip): the kernel family against an fp32
 restatement of the MLP, its input layouts and options against the plain launch, and the models / drivers at these widths
 against the CPU oracle (run with -m gpu)."""
 import os
