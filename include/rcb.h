@@ -22,9 +22,10 @@ extern "C" {
 #endif
 
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
- * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23).  A binding compares
+ * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23;
+ * 409: rcb_recon_finish).  A binding compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 408
+#define RCB_VERSION 409
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -654,6 +655,34 @@ int rcb_phase_bigweight_grad(const void* dbig, int32_t in_bf16, float* dwt, int3
 
 /* sigma = softplus(log_scale)/6 elementwise (prior_model.py:88).                                */
 int rcb_softplus_scale(const float* log_scale, float* scale, int64_t n, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (409): the decoder's last step and the distortion figure.  Replaces utils.py:200-260 (clip, x 255, np.round, / 255 and the
+ * squared-error mean, in numpy on a host copy of the whole reconstruction) and its caller main_compression.py:154-167.
+ * y [n_rows][n_pix][channels] fp32, 1 <= channels <= 32.  nd = 0: every row is a datapoint.  nd = 1..3: the rows are the PATCHES
+ * of stitched signals, addressed as rcb_siren_desc.pe_grid_dims addresses them: row n is patch n % prod(patch_nums) (row-major)
+ * of datapoint n / prod(patch_nums), its pixel p the row-major position inside the patch; prod(patch_size) = n_pix and n_rows is
+ * a multiple of prod(patch_nums).  patch_nums / patch_size: HOST arrays of nd entries (ignored for nd = 0).
+ * n_data = n_rows / prod(patch_nums) (n_rows for nd = 0).  `target`: nullable, the layout of y.
+ *   mode 0 (8-bit): q = rintf(fminf(fmaxf(x, 0), 1) * 255.0f) -- an fp32 multiply, half to even as np.round -- and
+ *                   v = (float)q / 255.0f, an IEEE fp32 division as numpy's;  mode 1 (raw: audio, protein): v = x.
+ * Outputs, each nullable:
+ *   u8    [n_data][G_0]..[G_nd-1][channels] uint8, G_i = patch_nums[i] * patch_size[i] ([n_rows][n_pix][channels] for nd = 0): q,
+ *         mode 0 only; a NaN x gives 0
+ *   whole the same stitched layout, fp32: v, either mode
+ *   sse   [n_data] fp64: the sum over the datapoint's elements of (double)d * (double)d, d = t - v as an fp32 subtraction (what
+ *         numpy forms elementwise); needs `target`
+ *   n_bad [n_data] int32: the elements whose x or t is not finite (an element with both counts twice).  A datapoint with any has
+ *         sse = NaN; no other datapoint is touched.
+ * The sum uses no floating-point atomics: which elements a workgroup adds and the order of every addition depend on the geometry
+ * of ONE datapoint alone, so a datapoint's sse is bitwise the same alone and inside any batch, and from run to run.
+ * `workspace`: rcb_recon_workspace_bytes(n_data, elements per datapoint) bytes (-1: shape refused), 8-byte aligned,
+ * caller-allocated.  Refused (RCB_ERR_*): nd > 3, channels out of range, n_pix != prod(patch_size), n_rows no multiple of
+ * prod(patch_nums), u8 with mode 1, sse without target, more than 2^31 - 1 elements per datapoint, a workspace that is too small. */
+int64_t rcb_recon_workspace_bytes(int64_t n_data, int64_t elems_per_datapoint);
+int rcb_recon_finish(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
+                     const int32_t* patch_nums, const int32_t* patch_size, int32_t mode, uint8_t* u8, float* whole, double* sse,
+                     int32_t* n_bad, void* workspace, int64_t workspace_bytes, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

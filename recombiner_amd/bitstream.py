@@ -114,9 +114,7 @@ def apply_indices(model, levels):
                        enc_sample=lv.sample, enc_mask=lv.mask, done=lv.d_done, beta=lv.kl_beta, idx_groupwise=lv.d_idx)
 
 
-def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0):
-    """Standalone decoder: prior checkpoint (drivers.load_checkpoint) + bitstream -> reconstruction [N, P, C].
-    x: the coordinate features the encoder used ([P, F] or [N, P, F]); n_datapoints: INRs (patches) in the stream."""
+def _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision):
     from .drivers import build_test_model
     levels = unpack_indices(blob)
     if levels[0].shape[0] != n_datapoints:
@@ -125,4 +123,32 @@ def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", se
     model.precision = precision
     apply_indices(model, levels)
     with torch.no_grad():
-        return model.predict(x.to(device))
+        return model, model.predict(x.to(device))
+
+
+def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False):
+    """Standalone decoder: prior checkpoint (drivers.load_checkpoint) + bitstream -> reconstruction [N, P, C].
+    x: the coordinate features the encoder used ([P, F] or [N, P, F]); n_datapoints: INRs (patches) in the stream.
+    as_uint8 (image / video presets): the 8-bit whole signals instead, uint8 [n_signals, *grid, C] with the patches of the
+    patched presets stitched -- clip, x 255, round half to even, as the metric rounds (rcb_recon_finish).  audio / protein
+    have no 8-bit form (their metric does not round): ValueError; `decode_signal` gives their fp32 whole signals."""
+    if as_uint8:
+        return decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8=True)
+    return _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision)[1]
+
+
+def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False):
+    """`decode`, finished on the device to WHOLE signals [n_signals, *grid, C] (n_signals = n_datapoints / patches per signal;
+    [N, P, C] for the unpatched presets): fp32 -- on the 8-bit lattice k / 255 for the image / video presets, the raw values
+    for audio / protein -- or, with as_uint8 (image / video only), the uint8 k themselves."""
+    from . import ops
+    from .utils import METRIC_ROUNDS
+    if dataset not in METRIC_ROUNDS:
+        raise ValueError(dataset)
+    if as_uint8 and not METRIC_ROUNDS[dataset]:
+        raise ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+    model, y = _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision)
+    mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
+    u8, whole, _, _ = ops.recon_finish(y.to(torch.float32).contiguous(), layout=model.recon_layout(), mode=mode,
+                                       want_u8=as_uint8, want_whole=not as_uint8)
+    return u8 if as_uint8 else whole

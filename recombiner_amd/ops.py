@@ -1152,6 +1152,68 @@ def tile_fold(tiles, n, H, W, Ty, Tx, off):
     return _tile_to_img("rcb_tile_fold", tiles, n, H, W, Ty, Tx, off)
 
 
+# ---------------------------------------------------------------------------------------------------
+# N4: the decoder's last step and the distortion figure (rcb_recon_finish)
+# ---------------------------------------------------------------------------------------------------
+RECON_8BIT, RECON_RAW = 0, 1
+
+
+def recon_whole_shape(shape, layout=None):
+    """shape of the whole signals of a reconstruction [N, P, C]: [n_data, *(patch_nums[i] * patch_size[i]), C] for a PeLayout,
+    [N, P, C] itself without one"""
+    N, P, Cc = shape
+    if layout is None:
+        return (N, P, Cc)
+    per = int(np.prod(layout.patch_nums))
+    return (N // per,) + tuple(a * b for a, b in zip(layout.patch_nums, layout.patch_size)) + (Cc,)
+
+
+def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, want_whole=False, out=None):
+    """The last step of a reconstruction y [N, P, C] (fp32; the rows are datapoints, or with `layout` = PeLayout(patch_nums,
+    patch_size) the patches of stitched signals) and its score against `target` (same layout), in one pass (rcb_recon_finish):
+    mode RECON_8BIT rounds to the 8-bit lattice as the reference's metric does (clip, x 255, round half to even, / 255),
+    RECON_RAW keeps the values (audio, protein).
+    -> (u8 uint8 whole signals or None, whole fp32 whole signals of the rounded / raw values or None,
+        sse fp64 [n_data] = per-datapoint sum of squared errors (None without target; NaN for a datapoint with a non-finite
+        element), n_bad int32 [n_data] = its non-finite elements of y and target).
+    sse is bitwise reproducible and the same for a datapoint alone or inside a batch.  Nothing is read back: no host sync.
+    out: optional preallocated (u8, whole, sse, n_bad) -- entries None are allocated here."""
+    lib = _lib.load()
+    if y.dim() != 3 or y.dtype != f32 or not y.is_cuda or not y.is_contiguous():
+        raise RcbError("recon_finish: y must be a contiguous fp32 GPU tensor [N, P, C]")
+    if target is not None and (tuple(target.shape) != tuple(y.shape) or target.dtype != f32 or not target.is_contiguous()
+                               or target.device != y.device):
+        raise RcbError(f"recon_finish: target must be a contiguous fp32 tensor {list(y.shape)} on the device of y")
+    N, P, Cc = (int(v) for v in y.shape)
+    nd = 0 if layout is None else len(layout.patch_nums)
+    if nd > 3 or (layout is not None and len(layout.patch_size) != nd):
+        raise RcbError(f"recon_finish: {nd} grid dimensions (a PeLayout of 1 to 3 axes, or None)")
+    pn = (C.c_int32 * 3)(*(list(layout.patch_nums) + [0] * (3 - nd) if nd else [0] * 3))
+    ps = (C.c_int32 * 3)(*(list(layout.patch_size) + [0] * (3 - nd) if nd else [0] * 3))
+    per = int(np.prod(layout.patch_nums)) if nd else 1
+    n_data = N // max(per, 1)
+    n_ws = int(lib.rcb_recon_workspace_bytes(max(n_data, 1), per * P * Cc)) if N and P and Cc else -1
+    dev = y.device
+    shape = recon_whole_shape((N, P, Cc), layout) if per > 0 and N % per == 0 else (N, P, Cc)
+    u8, whole, sse, n_bad = out if out is not None else (None,) * 4
+    if want_u8 and u8 is None:
+        u8 = torch.empty(shape, device=dev, dtype=torch.uint8)
+    if want_whole and whole is None:
+        whole = torch.empty(shape, device=dev, dtype=f32)
+    if target is not None and sse is None:
+        sse = torch.empty(n_data, device=dev, dtype=f64)
+    if n_bad is None:
+        n_bad = torch.empty(n_data, device=dev, dtype=i32)
+    for t_, want, dt in ((u8, shape, torch.uint8), (whole, shape, f32), (sse, (n_data,), f64), (n_bad, (n_data,), i32)):
+        if t_ is not None and (tuple(t_.shape) != tuple(want) or t_.dtype != dt or t_.device != dev or not t_.is_contiguous()):
+            raise RcbError(f"recon_finish: output of shape {tuple(t_.shape)} {t_.dtype}, expected contiguous {tuple(want)} {dt} "
+                           "on the device of y")
+    ws = torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8)       # (a refused shape: the library says why)
+    _launch("rcb_recon_finish", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps, int(mode),
+            ptr(u8, torch.uint8, True), ptr(whole, f32, True), ptr(sse, f64, True), ptr(n_bad, i32), ptr(ws), max(n_ws, 8))
+    return u8, whole, sse, n_bad
+
+
 def _win_geo(shape):
     nd = len(shape) - 2
     if nd < 1 or nd > 3 or shape[-1] % 8:

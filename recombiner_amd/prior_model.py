@@ -21,7 +21,7 @@ from . import train_step
 from .ops import LevelSpec, SirenMeta
 from .upsample_fast import (hip_path_supported, tiled_2d_preferred, phase_form_preferred, phase_module,
                             stitched2d_module, upsample_cifar_hip)
-from .utils import count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs
+from .utils import count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs, metric_device
 from .utils import map_hierarchical_model_to_int_weights  # noqa: F401  (module-level name, as upstream imports it)
 
 
@@ -110,6 +110,23 @@ class InrGeometry:
         # reference API: the slice of a layer-vector row (.. x D_net) that belongs to layer `layer_idx`
         lo, hi = self._layer_slices()[layer_idx]
         return param[..., lo:hi]
+
+    def recon_layout(self):
+        """how the rows of a reconstruction [N, P, C] make up whole signals: ops.PeLayout of the patched presets, else None"""
+        if self.patch:
+            return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
+        return None
+
+    def report(self, x, y, on_device=True):
+        """TestBNNmodel (the model with `predict`, `dataset` and `_report`; it lives here because both models share this mixin):
+        the distortion figure of `_report` -- an array per datapoint (cifar, protein) or one float -- without the host copy of the
+        reconstruction: rounding and squared error run in rcb_recon_finish and only the per-datapoint fp64 sums come back
+        (utils.metric_device).  Agrees with `_report` to the rounding of its float32 evaluation; on_device=False is `_report`."""
+        if not on_device:
+            return self._report(x, y)
+        with torch.no_grad():
+            y_pred = self.predict(x.to(self.loc.device))
+        return metric_device(y, y_pred, self.dataset, self.recon_layout())
 
 
 class PriorBNNmodel(nn.Module, InrGeometry):

@@ -209,3 +209,42 @@ def metric(original, compressed, dataset):
     if dataset == "protein":
         return batch_RMSD(original, compressed, scale_factor=25)
     raise ValueError(dataset)
+
+
+# ---------------------------------------------------------------------------------------------
+# the same figures from exact per-datapoint sums formed on the device (rcb_recon_finish)
+# ---------------------------------------------------------------------------------------------
+METRIC_ROUNDS = {"cifar": True, "kodak": True, "video": True, "audio": False, "protein": False}
+
+
+def metric_from_sse(sse, n_elems, dataset):
+    """`metric` from the per-datapoint fp64 sums of squared errors `sse` [n_data] (ops.recon_finish: 8-bit mode for cifar /
+    kodak / video, raw mode for audio / protein) and the element count of one datapoint, all in fp64:
+    cifar -> PSNR per datapoint [n_data]; kodak / video / audio -> one PSNR over the whole batch (a float); protein ->
+    RMSD per datapoint, 25 * sqrt(3 * sse / n).  Where `metric` takes a float32 mean in numpy's pairwise order, this divides
+    an fp64 sum once."""
+    if dataset not in METRIC_ROUNDS:
+        raise ValueError(dataset)
+    sse = np.asarray(sse, dtype=np.float64).reshape(-1)
+    n = float(n_elems)
+    if dataset == "cifar":
+        return -10.0 * np.log10(sse / n)
+    if dataset == "protein":
+        return 25.0 * np.sqrt(3.0 * sse / n)
+    return (-10.0 * np.log10(sse.sum() / (n * sse.size))).item()
+
+
+def metric_device(y_true, y_pred, dataset, layout=None):
+    """`metric(y_true, y_pred, dataset)` for GPU tensors [N, P, C] without copying them to the host: one pass of
+    rcb_recon_finish (rounding to 8 bits where the dataset's metric does), then only the per-datapoint sums -- and the counts
+    of non-finite elements, which make a datapoint's figure NaN as numpy's would be -- are read back.  layout: ops.PeLayout
+    of a patched preset (rows = patches of stitched signals) or None (rows = datapoints); the batch-wide figures do not
+    depend on it."""
+    from . import ops
+    if dataset not in METRIC_ROUNDS:
+        raise ValueError(dataset)
+    mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
+    y_pred = y_pred.detach().to(torch.float32).contiguous()
+    y_true = y_true.detach().to(device=y_pred.device, dtype=torch.float32).contiguous()
+    _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode)
+    return metric_from_sse(sse.cpu().numpy(), y_pred.numel() // sse.numel(), dataset)
