@@ -23,9 +23,9 @@ extern "C" {
 
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
  * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23;
- * 409: rcb_recon_finish).  A binding compares
+ * 409: rcb_recon_finish; 410: rcb_signal_patch).  A binding compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 409
+#define RCB_VERSION 410
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -683,6 +683,31 @@ int64_t rcb_recon_workspace_bytes(int64_t n_data, int64_t elems_per_datapoint);
 int rcb_recon_finish(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
                      const int32_t* patch_nums, const int32_t* patch_size, int32_t mode, uint8_t* u8, float* whole, double* sse,
                      int32_t* n_bad, void* workspace, int64_t workspace_bytes, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (410): the encoder's first step, whole signals -> the patch targets y.  Replaces data/image.py:30-46, data/video.py:54-73 and
+ * data/audio.py:125-140 (a host loop of slices per patch, each flattened by utils.py:287-298) and the / 255 of ToTensor
+ * (data/image.py:17) and of data/video.py:31.
+ * `src` addresses n_data signals on the grid G_i = patch_nums[i] * patch_size[i], nd = 1..3, 1 <= channels <= 32: element
+ * (d, g_0 .. g_nd-1, c) lies at src + d * data_stride + sum g_i * axis_stride[i] + c * channel_stride.  Strides are in ELEMENTS and
+ * >= 0; patch_nums / patch_size / axis_stride: HOST arrays of nd entries.  The one rule covers channel-last and channel-first
+ * sources, transposed axes, a window cut out of a larger signal and a broadcast channel (stride 0).  Unpatched presets pass
+ * patch_nums of all ones.
+ *   src_kind 0 (uint8): y = (float)q / 255.0f, one IEEE fp32 division (what ToTensor and `video / 255` give on the CPU)
+ *   src_kind 1 (fp32):  the 32 bits unchanged -- NaN payloads, +-0, infinities and denormals keep their bits
+ * y [n_data * prod(patch_nums)][prod(patch_size)][channels] fp32, contiguous, in the row order of rcb_recon_finish and of
+ * rcb_siren_desc.pe_grid_dims: row n is patch n % prod(patch_nums) (row-major over patch_nums) of signal n / prod(patch_nums), its
+ * pixel p the row-major position inside the patch.  rcb_recon_finish on this y with the same geometry gives the signals back.
+ * Memory: quads of 4 consecutive elements of y.  With channel_stride = 1, axis_stride[nd-1] = channels, patch_size[nd-1] * channels a
+ * multiple of 4 and the base pointers, data_stride and the outer strides keeping every run start on a 4-element boundary (y: 16
+ * bytes), a quad is one 4-byte (uint8) / 16-byte (fp32) load and one 16-byte store; otherwise the same quads move element by
+ * element.  The entry decides; both paths give the same bits.  Source offsets are 64-bit.
+ * n_data = 0 succeeds and launches nothing.  Refused (RCB_ERR_*), nothing launched: nd outside 1..3, channels out of range, a
+ * non-positive patch count or size, an unknown src_kind, a negative stride, more than 2^31 - 1 elements per signal, null src or y
+ * with n_data > 0. */
+int rcb_signal_patch(const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,
+                     const int32_t* patch_size, int32_t channels, int64_t data_stride, const int64_t* axis_stride,
+                     int64_t channel_stride, float* y, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

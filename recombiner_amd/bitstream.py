@@ -122,13 +122,17 @@ def _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, 
     model = build_test_model(config, dataset, checkpoint, n_datapoints, device, seed)
     model.precision = precision
     apply_indices(model, levels)
+    if x is None:
+        from .utils import preset_inputs
+        x = preset_inputs(config)
     with torch.no_grad():
         return model, model.predict(x.to(device))
 
 
 def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False):
     """Standalone decoder: prior checkpoint (drivers.load_checkpoint) + bitstream -> reconstruction [N, P, C].
-    x: the coordinate features the encoder used ([P, F] or [N, P, F]); n_datapoints: INRs (patches) in the stream.
+    x: the coordinate features the encoder used ([P, F] or [N, P, F]; None: the preset's own, utils.preset_inputs(config));
+    n_datapoints: INRs (patches) in the stream.
     as_uint8 (image / video presets): the 8-bit whole signals instead, uint8 [n_signals, *grid, C] with the patches of the
     patched presets stitched -- clip, x 255, round half to even, as the metric rounds (rcb_recon_finish).  audio / protein
     have no 8-bit form (their metric does not round): ValueError; `decode_signal` gives their fp32 whole signals."""

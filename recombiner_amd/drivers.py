@@ -268,6 +268,21 @@ def compress(config, dataset, checkpoint, x, y, device="cuda", seed=42, n_epochs
     return distortion, model
 
 
+def compress_signals(config, dataset, checkpoint, signals, x=None, channels_first=False, origin=None, landscape=True, **kw):
+    """`compress` on whole signals in memory -- uint8 (q / 255, as ToTensor and `video / 255`) or fp32, [n, *spatial, C] or
+    [n, C, *spatial] with channels_first -- instead of patch targets: the preset's window of each signal (utils.signal_view,
+    which also documents origin / landscape) is cut into y [N, P, C] on the device (rcb_signal_patch), where the reference's
+    loaders slice on the host (data/image.py:30-46, data/video.py:54-73, data/audio.py:125-140).  x None: the preset's own
+    coordinate features (utils.preset_inputs) shared by all rows.  Every other argument, and the result, is `compress`'s."""
+    from . import utils
+    device = kw.get("device", "cuda")
+    view = utils.signal_view(config, signals.to(device), channels_first=channels_first, origin=origin, landscape=landscape)
+    y = ops.signal_patch(view, utils.signal_layout(config))
+    if x is None:
+        x = utils.preset_inputs(config, device)[None].expand(y.shape[0], -1, -1)
+    return compress(config, dataset, checkpoint, x, y, **kw)
+
+
 def rd_point(config, dataset, X, Y_train, Y_test, max_bitrate, device="cuda", seed=42, n_em_iter=550, first_epochs=200, epochs=100,
              lr=2e-4, n_opt=30000, finetune_epochs=None, precision=0, noise_source=None):
     """One rate-distortion point from scratch with the product alone: learn the prior (and the mappings) on Y_train

@@ -1214,6 +1214,46 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
     return u8, whole, sse, n_bad
 
 
+# ---------------------------------------------------------------------------------------------------
+# N4: the encoder's first step, whole signals -> patch targets (rcb_signal_patch)
+# ---------------------------------------------------------------------------------------------------
+SIGNAL_KINDS = {torch.uint8: 0, f32: 1}
+
+
+def signal_patch(signals, layout, out=None):
+    """Whole signals -> the targets y [N, P, C] (fp32) of the INRs, in the row order recon_finish reads (rcb_signal_patch):
+    `signals` is a GPU tensor viewed as [n, *G, C], G_i = patch_nums[i] * patch_size[i] of `layout` = PeLayout(patch_nums,
+    patch_size) (all ones for an unpatched preset), uint8 (y = q / 255 as one IEEE fp32 division) or fp32 (the bits are kept),
+    with ANY strides and storage offset -- channel-first storage, transposed axes, a window of a larger signal, an expanded
+    channel: the strides go to the kernel as they are and nothing is copied.  recon_finish(y, layout=layout) stitches y back.
+    out: optional preallocated contiguous fp32 [N, P, C].  No host sync."""
+    if not isinstance(signals, torch.Tensor) or not signals.is_cuda:
+        raise RcbError("signal_patch: signals must be a GPU tensor (the HIP path has no CPU fallback)")
+    if signals.dtype not in SIGNAL_KINDS:
+        raise RcbError(f"signal_patch: signals must be uint8 or fp32, got {signals.dtype}")
+    pn, ps = list(layout.patch_nums), list(layout.patch_size)
+    nd = len(pn)
+    if len(ps) != nd or signals.dim() != nd + 2:
+        raise RcbError(f"signal_patch: signals of {signals.dim()} axes for a layout of {nd} ([n, *grid, C] expected)")
+    grid = tuple(a * b for a, b in zip(pn, ps))
+    n, Cc = int(signals.shape[0]), int(signals.shape[-1])
+    if tuple(signals.shape[1:-1]) != grid:
+        raise RcbError(f"signal_patch: signals on the grid {tuple(signals.shape[1:-1])}, the layout's is {grid}")
+    per, P = int(np.prod(pn)) if nd else 1, int(np.prod(ps)) if nd else 1
+    shape = (n * per, P, Cc)
+    fits = 0 <= per * P * Cc <= 0x7fffffff                   # (a refused shape gets no buffer: the library says why)
+    if out is None:
+        out = torch.empty(shape if fits else (1,), device=signals.device, dtype=f32)
+    elif tuple(out.shape) != shape or out.dtype != f32 or out.device != signals.device or not out.is_contiguous():
+        raise RcbError(f"signal_patch: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {f32} on the "
+                       "device of signals")
+    st = [int(v) for v in signals.stride()]
+    arr = max(nd, 1)
+    _launch("rcb_signal_patch", C.c_void_p(signals.data_ptr()), SIGNAL_KINDS[signals.dtype], n, nd, (C.c_int32 * arr)(*pn),
+            (C.c_int32 * arr)(*ps), Cc, st[0], (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
+    return out
+
+
 def _win_geo(shape):
     nd = len(shape) - 2
     if nd < 1 or nd > 3 or shape[-1] % 8:

@@ -128,6 +128,18 @@ class InrGeometry:
             y_pred = self.predict(x.to(self.loc.device))
         return metric_device(y, y_pred, self.dataset, self.recon_layout())
 
+    def patch_signals(self, signals):
+        """whole signals [n, *grid, C] on the GPU (uint8 or fp32, any strides: utils.signal_view) -> the targets y [N, P, C] of
+        this model's INRs, cut on the device in the row order of recon_layout (rcb_signal_patch); the inverse of the stitching
+        in ops.recon_finish.  The unpatched presets are one patch per signal."""
+        dd = self.data_dim
+        layout = self.recon_layout() or ops.PeLayout([1] * dd, self.pixel_sizes[:dd])
+        return ops.signal_patch(signals, layout)
+
+    def report_signals(self, x, signals):
+        """`report` against whole signals instead of patch targets"""
+        return self.report(x, self.patch_signals(signals))
+
 
 class PriorBNNmodel(nn.Module, InrGeometry):
     """Training-set posteriors + batched INR evaluation (prior_model.py:62-262)."""

@@ -172,6 +172,61 @@ def synthetic_inputs(pixel_sizes, fourier_dim, n_inr, out_dim, seed=0):
     return X, Y
 
 
+def preset_inputs(config, device=None):
+    """The coordinate features of one patch (one datapoint of an unpatched preset), X [P, F]: the grid of `pixel_sizes`
+    embedded with `fourier_dim` features (data/image.py:24-27) -- what synthetic_inputs returns as X.  Evaluated on the CPU,
+    like the reference's loaders, then moved to `device`: one array shared by all rows."""
+    coords, _ = to_grid_coordinates_and_features(torch.zeros(1, *config["pixel_sizes"]))
+    X = fourier_embed(coords, config["fourier_dim"])
+    return X if device is None else X.to(device)
+
+
+# ---------------------------------------------------------------------------------------------
+# whole signals in memory -> what rcb_signal_patch reads (data/image.py:17-46, data/video.py:40-73, data/audio.py:112-140)
+# ---------------------------------------------------------------------------------------------
+def preset_grid(config):
+    """(patch_nums, patch_size) of a preset's whole signal: its patch grid, or one patch for the unpatched presets"""
+    dd = config["data_dim"]
+    ps = [int(v) for v in config["pixel_sizes"][:dd]]
+    pn = [int(v) for v in config["patch_nums"][:dd]] if config["patch"] else [1] * dd
+    return pn, ps
+
+
+def signal_layout(config):
+    """ops.PeLayout of a preset's whole signals (ops.signal_patch / ops.recon_finish); patch_nums of ones when unpatched"""
+    from . import ops
+    return ops.PeLayout(*preset_grid(config))
+
+
+def signal_view(config, tensor, channels_first=False, origin=None, landscape=True):
+    """A VIEW [n, *G, C] of signals in memory -- [n, *spatial, C], or [n, C, *spatial] with channels_first -- on the preset's grid G = patch_nums * pixel_sizes (pixel_sizes when unpatched): the channel axis moved
+    last and the window of that size at `origin` (default 0 on every axis: the leading whole patches, which is what the
+    reference's `range(x // patch_sizes[i])` loops keep).  landscape (2-D presets): the two spatial axes are swapped when the
+    first is longer than the second, as data/image.py:18-19 rotates a portrait image; origin then counts on the swapped axes.
+    Nothing is copied: ops.signal_patch takes the strides as they are.  ValueError when the signal is smaller than the preset
+    (or the window leaves it), or its channels are not the preset's."""
+    dd = config["data_dim"]
+    if tensor.dim() != dd + 2:
+        raise ValueError("signal_view: %d axes for a %d-D preset ([n, *spatial, C] expected)" % (tensor.dim(), dd))
+    if channels_first:
+        tensor = tensor.movedim(1, -1)
+    if dd == 2 and landscape and tensor.shape[1] > tensor.shape[2]:
+        tensor = tensor.transpose(1, 2)
+    if tensor.shape[-1] != config["output_dim"]:
+        raise ValueError("signal_view: %d channels, the preset has %d" % (tensor.shape[-1], config["output_dim"]))
+    pn, ps = preset_grid(config)
+    origin = [0] * dd if origin is None else [int(v) for v in origin]
+    if len(origin) != dd:
+        raise ValueError("signal_view: origin of %d entries for a %d-D preset" % (len(origin), dd))
+    for i in range(dd):
+        size = pn[i] * ps[i]
+        if origin[i] < 0 or origin[i] + size > tensor.shape[1 + i]:
+            raise ValueError("signal_view: axis %d of the signal has %d pixels, the preset's window [%d, %d) does not fit"
+                             % (i, tensor.shape[1 + i], origin[i], origin[i] + size))
+        tensor = tensor.narrow(1 + i, origin[i], size)
+    return tensor
+
+
 # ---------------------------------------------------------------------------------------------
 # metrics (utils.py:200-260) -- host numpy, as in the reference
 # ---------------------------------------------------------------------------------------------
