@@ -23,9 +23,9 @@ extern "C" {
 
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
  * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23;
- * 409: rcb_recon_finish; 410: rcb_signal_patch).  A binding compares
+ * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop).  A binding compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 410
+#define RCB_VERSION 411
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -708,6 +708,36 @@ int rcb_recon_finish(const float* y, const float* target, int64_t n_rows, int32_
 int rcb_signal_patch(const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,
                      const int32_t* patch_size, int32_t channels, int64_t data_stride, const int64_t* axis_stride,
                      int64_t channel_stride, float* y, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (411): signals of any size.  The encoder replicates a signal's edge samples out to the grid the model accepts, the decoder
+ * crops back, and the distortion figure counts the real samples only.
+ *
+ * rcb_signal_patch_pad is rcb_signal_patch for signals that hold only size[i] positions per axis, 1 <= size[i] <= G_i =
+ * patch_nums[i] * patch_size[i] (`size`: a HOST array of nd entries; `src` addresses only that extent): grid position g_i reads
+ * source position min(g_i, size[i] - 1) -- edge replication on the far side of every axis (np.pad(mode="edge") after the
+ * signal).  Row order, q / 255 as one IEEE fp32 division, the bit-preserving fp32 move, 64-bit source offsets and any
+ * non-negative strides are rcb_signal_patch's.  A quad of y that is 4 consecutive EXISTING source elements on a 4-element boundary
+ * (the conditions of rcb_signal_patch, on the strides of the axes with more than one position) is one 4- / 16-byte load; every
+ * other quad moves element by element through the clipped index; both give the same bits.  No read leaves the extent.
+ * With size = G every bit of y is rcb_signal_patch's.  Refused: what rcb_signal_patch refuses, a null `size`, a size[i] outside
+ * [1, G_i]. */
+int rcb_signal_patch_pad(const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,
+                         const int32_t* patch_size, const int32_t* size, int32_t channels, int64_t data_stride,
+                         const int64_t* axis_stride, int64_t channel_stride, float* y, rcb_stream_t stream);
+
+/* rcb_recon_finish_crop is rcb_recon_finish (nd = 1..3; unpatched presets pass patch_nums of ones) for datapoints of which only
+ * the leading size[i] <= G_i positions per axis are real (`size`: a HOST array of nd entries).  Per element the arithmetic is
+ * rcb_recon_finish's.  u8 / whole are contiguous [n_data][size_0]..[size_nd-1][channels]; only positions inside the extent are
+ * written.  sse / n_bad keep the chunks and the order of additions of rcb_recon_finish over the PADDED datapoint (the same
+ * workspace: rcb_recon_workspace_bytes(n_data, padded elements per datapoint)): an element outside the extent adds +0.0 and is
+ * never counted as non-finite, whatever y and target hold there.  So sse is the sum over the real samples, bitwise what
+ * rcb_recon_finish gives for a target that equals v outside the extent, and bitwise the same alone, in any batch and from run to
+ * run (no floating-point atomics).  With size = G every output bit is rcb_recon_finish's.
+ * Refused: what rcb_recon_finish refuses, nd = 0, a null `size`, a size[i] outside [1, G_i]. */
+int rcb_recon_finish_crop(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
+                          const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t mode, uint8_t* u8,
+                          float* whole, double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,13 @@ parameters equal the encoder's bit for bit.
 
 Container (little endian):  b"RCB1" | u16 version | u8 n_levels | u8 bits | per level: u32 rows, u32 n_groups |
 payload: for each level (1, then 2 and 3 for patched presets) rows x n_groups uint16 indices, row-major | u32 CRC-32 of
-the payload."""
+the payload.
+
+Version 2 (signals of any size, drivers.compress_signals_any): after the per-level shapes comes  u8 nd | nd x u32 size  -- the
+signals' own extent per spatial axis; the model's grid is utils.fit_config(config, size), the signals were edge-padded to it and
+`decode_signal_any` crops back -- and the CRC-32 covers that block and the payload, so a flipped size byte is rejected.  Rate of a
+version-2 stream: bpp = payload_bits / (n_signals * prod(size)), bits per REAL sample position (the padding costs bits, it is not
+counted as signal)."""
 import struct
 import zlib
 
@@ -21,15 +27,25 @@ import torch
 
 MAGIC = b"RCB1"
 VERSION = 1
+VERSION_EXTENT = 2
 
 
-def pack_indices(levels, bits=16):
-    """levels: list of integer arrays [rows, n_groups] with values < 2**bits  ->  bytes."""
+def _extent_block(extent):
+    size = [int(v) for v in extent]
+    if not 1 <= len(size) <= 3 or any(not 1 <= v <= 0xFFFFFFFF for v in size):
+        raise ValueError("extent %r: 1 to 3 sizes in [1, 2^32) expected" % (tuple(extent),))
+    return struct.pack("<B", len(size)) + struct.pack("<%dI" % len(size), *size)
+
+
+def pack_indices(levels, bits=16, extent=None):
+    """levels: list of integer arrays [rows, n_groups] with values < 2**bits  ->  bytes.  extent None: version 1; a tuple of the
+    signals' size per spatial axis: version 2, which carries it."""
     if bits != 16:
         raise ValueError("only 16 bits per group are defined (K = 65536 candidates, test_model.py:441-444)")
     if not 1 <= len(levels) <= 3:
         raise ValueError("1 to 3 levels expected")
-    head = MAGIC + struct.pack("<HBB", VERSION, len(levels), bits)
+    ext = b"" if extent is None else _extent_block(extent)
+    head = MAGIC + struct.pack("<HBB", VERSION if extent is None else VERSION_EXTENT, len(levels), bits)
     body = b""
     for a in levels:
         a = np.asarray(a)
@@ -39,15 +55,16 @@ def pack_indices(levels, bits=16):
             raise ValueError("index out of range for %d bits" % bits)
         head += struct.pack("<II", a.shape[0], a.shape[1])
         body += np.ascontiguousarray(a.astype("<u2")).tobytes()
-    return head + body + struct.pack("<I", zlib.crc32(body) & 0xFFFFFFFF)
+    return head + ext + body + struct.pack("<I", zlib.crc32(ext + body) & 0xFFFFFFFF)
 
 
-def unpack_indices(blob):
-    """bytes -> list of int64 arrays [rows, n_groups]; raises ValueError on a malformed or corrupted stream."""
+def unpack(blob):
+    """bytes (either version) -> (list of int64 arrays [rows, n_groups], extent: the tuple a version-2 stream carries, None
+    for version 1); raises ValueError on a malformed or corrupted stream."""
     if len(blob) < 12 or blob[:4] != MAGIC:
         raise ValueError("not an RCB1 bitstream")
     version, n_levels, bits = struct.unpack_from("<HBB", blob, 4)
-    if version != VERSION or bits != 16 or not 1 <= n_levels <= 3:
+    if version not in (VERSION, VERSION_EXTENT) or bits != 16 or not 1 <= n_levels <= 3:
         raise ValueError("unsupported bitstream header (version %d, %d levels, %d bits)" % (version, n_levels, bits))
     off = 8
     shapes = []
@@ -56,18 +73,36 @@ def unpack_indices(blob):
             raise ValueError("truncated header")
         shapes.append(struct.unpack_from("<II", blob, off))
         off += 8
+    start, extent = off, None
+    if version == VERSION_EXTENT:
+        if off + 1 > len(blob):
+            raise ValueError("truncated header")
+        nd = blob[off]
+        if not 1 <= nd <= 3:
+            raise ValueError("unsupported bitstream header (an extent of %d axes)" % nd)
+        if off + 1 + 4 * nd > len(blob):
+            raise ValueError("truncated header")
+        extent = tuple(int(v) for v in struct.unpack_from("<%dI" % nd, blob, off + 1))
+        if min(extent) < 1:
+            raise ValueError("bitstream extent %r has an empty axis" % (extent,))
+        off += 1 + 4 * nd
     n_bytes = sum(r * g for r, g in shapes) * 2
     if len(blob) != off + n_bytes + 4:
         raise ValueError("bitstream length %d does not match its header (%d expected)" % (len(blob), off + n_bytes + 4))
     body = blob[off:off + n_bytes]
     (crc,) = struct.unpack_from("<I", blob, off + n_bytes)
-    if zlib.crc32(body) & 0xFFFFFFFF != crc:
+    if zlib.crc32(blob[start:off + n_bytes]) & 0xFFFFFFFF != crc:
         raise ValueError("bitstream checksum mismatch")
     out, p = [], 0
     for r, g in shapes:
         out.append(np.frombuffer(body, dtype="<u2", count=r * g, offset=p).reshape(r, g).astype(np.int64))
         p += r * g * 2
-    return out
+    return out, extent
+
+
+def unpack_indices(blob):
+    """bytes (either version) -> list of int64 arrays [rows, n_groups]; raises ValueError on a malformed or corrupted stream."""
+    return unpack(blob)[0]
 
 
 def payload_bits(blob):
@@ -79,13 +114,14 @@ def _levels_of(model):
     return [model._l1] + ([model._l2, model._l3] if model.patch else [])
 
 
-def encode(model):
-    """bitstream of a fully compressed TestBNNmodel (every group of every level encoded)."""
+def encode(model, extent=None):
+    """bitstream of a fully compressed TestBNNmodel (every group of every level encoded).  extent: the size of the signals
+    when they were edge-padded to the model's grid (a version-2 stream, decode_signal_any); None: version 1, as ever."""
     lvls = _levels_of(model)
     for lv in lvls:
         if not lv.mask_groupwise.all():
             raise ValueError("level %r has %d groups that are not encoded yet" % (lv.pre, int((~lv.mask_groupwise).sum())))
-    return pack_indices([lv.idx_groupwise for lv in lvls])
+    return pack_indices([lv.idx_groupwise for lv in lvls], extent=extent)
 
 
 def apply_indices(model, levels):
@@ -135,16 +171,17 @@ def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", se
     n_datapoints: INRs (patches) in the stream.
     as_uint8 (image / video presets): the 8-bit whole signals instead, uint8 [n_signals, *grid, C] with the patches of the
     patched presets stitched -- clip, x 255, round half to even, as the metric rounds (rcb_recon_finish).  audio / protein
-    have no 8-bit form (their metric does not round): ValueError; `decode_signal` gives their fp32 whole signals."""
+    have no 8-bit form (their metric does not round): ValueError; `decode_signal` gives their fp32 whole signals.
+    A version-2 stream is decoded like a version-1 stream: this is the patch level, `config` names the (fitted) grid and the
+    result covers all of it, padding included; `decode_signal_any` crops to the size the stream carries."""
     if as_uint8:
-        return decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8=True)
+        return _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8=True)
     return _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision)[1]
 
 
-def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False):
-    """`decode`, finished on the device to WHOLE signals [n_signals, *grid, C] (n_signals = n_datapoints / patches per signal;
-    [N, P, C] for the unpatched presets): fp32 -- on the 8-bit lattice k / 255 for the image / video presets, the raw values
-    for audio / protein -- or, with as_uint8 (image / video only), the uint8 k themselves."""
+def _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8):
+    # the whole GRID of `config`, for either version: `decode` is the patch-level decoder -- its caller names the (fitted) config
+    # and the number of patches, and knows what the grid holds
     from . import ops
     from .utils import METRIC_ROUNDS
     if dataset not in METRIC_ROUNDS:
@@ -154,5 +191,52 @@ def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cu
     model, y = _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision)
     mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
     u8, whole, _, _ = ops.recon_finish(y.to(torch.float32).contiguous(), layout=model.recon_layout(), mode=mode,
+                                       want_u8=as_uint8, want_whole=not as_uint8)
+    return u8 if as_uint8 else whole
+
+
+def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False):
+    """`decode`, finished on the device to WHOLE signals [n_signals, *grid, C] (n_signals = n_datapoints / patches per signal;
+    [N, P, C] for the unpatched presets): fp32 -- on the 8-bit lattice k / 255 for the image / video presets, the raw values
+    for audio / protein -- or, with as_uint8 (image / video only), the uint8 k themselves.
+    A version-2 stream is refused (ValueError): its signals are smaller than the grid, decode_signal_any crops them back."""
+    from .utils import METRIC_ROUNDS
+    if dataset not in METRIC_ROUNDS:
+        raise ValueError(dataset)
+    if as_uint8 and not METRIC_ROUNDS[dataset]:
+        raise ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+    extent = unpack(blob)[1]
+    if extent is not None:
+        raise ValueError("a version-2 bitstream: its signals of size %r were edge-padded to the model's grid -- decode them with "
+                         "decode_signal_any, which crops back (this decoder would return the padding)" % (extent,))
+    return _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8)
+
+
+def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42, precision=0, as_uint8=False):
+    """The decoder of drivers.compress_signals_any: prior checkpoint + version-2 bitstream -> the signals [n, *size, C] at their
+    own size.  `config` is the PRESET: the stream's extent fits it (utils.fit_config), the number of signals follows from the
+    level-1 rows (ValueError when they are no whole number of signals), the patches are decoded with the preset's own coordinate
+    features, and rcb_recon_finish_crop stitches, rounds (image / video presets) and crops on the device.  fp32 -- on the 8-bit
+    lattice k / 255 for the image / video presets, raw for audio / protein -- or, with as_uint8 (image / video only), the k."""
+    from . import ops
+    from .utils import METRIC_ROUNDS, fit_config, preset_grid
+    if dataset not in METRIC_ROUNDS:
+        raise ValueError(dataset)
+    if as_uint8 and not METRIC_ROUNDS[dataset]:
+        raise ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+    levels, extent = unpack(blob)
+    if extent is None:
+        raise ValueError("a version-1 bitstream carries no signal size: decode it with decode_signal")
+    if len(extent) != config["data_dim"]:
+        raise ValueError("bitstream extent %r for a %d-D preset" % (extent, config["data_dim"]))
+    fitted = fit_config(config, extent)
+    pn, ps = preset_grid(fitted)
+    per = int(np.prod(pn))
+    rows = int(levels[0].shape[0])
+    if rows == 0 or rows % per:
+        raise ValueError("bitstream holds %d rows, signals of size %r take %d patches each" % (rows, extent, per))
+    _, y = _decode_patches(fitted, dataset, checkpoint, blob, None, rows, device, seed, precision)
+    mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
+    u8, whole, _, _ = ops.recon_finish(y.to(torch.float32).contiguous(), layout=ops.PeLayout(pn, ps), size=extent, mode=mode,
                                        want_u8=as_uint8, want_whole=not as_uint8)
     return u8 if as_uint8 else whole

@@ -21,6 +21,8 @@
 // whole datapoint for nd = 0), is a multiple of 4 and the pointers are 16-byte aligned, a quad never straddles a run: one 16-byte
 // load per input, one 16-byte store to `whole`, one 4-byte store to `u8`, coalesced along C x pixels of the patch row.  Otherwise the
 // same quads are moved element by element.  HBM-bound: bytes = y + target + outputs.
+//
+// rcb_recon_finish_crop is the same kernel (template parameter CROP) for datapoints of which only a leading extent is real.
 #include "rcb_common.h"
 
 #pragma clang fp contract(off)
@@ -53,6 +55,29 @@ __device__ __forceinline__ int whole_offset(const ReconGeo& g, int run, int off)
   const int g0 = b0 * g.ps[0] + p0, g1 = b1 * g.ps[1] + p1;
   // ((g0 * G1 + g1) * G2 + b2 * ps2) * C + off, with G2 * C = pn2 * R and ps2 * C = R
   return ((g0 * (g.pn[1] * g.ps[1]) + g1) * g.pn[2] + b2) * g.R + off;
+}
+
+// rcb_recon_finish_crop: the datapoint's own extent inside the stitched grid.  The elements of grid row (g0, g1) are numbered
+// e = b2 * R + off; the first L = size[last] * C of them exist.  An element outside adds +0.0 to the sum, is never counted and
+// is not written; the outputs are contiguous over the extent.
+struct CropGeo {
+  int sz[3];              // extent per axis, right-aligned (leading axes 1)
+  int L;                  // sz[2] * C
+  int vec_out;            // L % 4 == 0 and aligned outputs: a quad inside the extent is one 16-byte / 4-byte store
+  long long Ec;           // elements of one cropped datapoint
+};
+
+// grid row of run `run` inside the cropped datapoint: -> offset of its element 0, or -1 when the row lies outside; e0 = b2 * R
+__device__ __forceinline__ int crop_row(const ReconGeo& g, const CropGeo& x, int run, int& e0) {
+  int r = run;
+  const int p1 = r % g.ps[1]; r /= g.ps[1];
+  const int p0 = r % g.ps[0]; r /= g.ps[0];
+  const int b2 = r % g.pn[2]; r /= g.pn[2];
+  const int b1 = r % g.pn[1];
+  const int b0 = r / g.pn[1];
+  const int g0 = b0 * g.ps[0] + p0, g1 = b1 * g.ps[1] + p1;
+  e0 = b2 * g.R;
+  return (g0 < x.sz[0] && g1 < x.sz[1]) ? (g0 * x.sz[1] + g1) * x.L : -1;
 }
 
 struct Elem {
@@ -99,10 +124,13 @@ __device__ __forceinline__ bool block_sum(double& acc, int& bad) {
   return true;
 }
 
-template <bool VEC>
+// CROP: rcb_recon_finish_crop -- the same loads, the same additions in the same order; only what an element outside the extent
+// contributes (+0.0, no count) and where the outputs go differ
+template <bool VEC, bool CROP>
 __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict__ y, const float* __restrict__ target,
                                                          uint8_t* __restrict__ u8, float* __restrict__ whole,
-                                                         double* __restrict__ part_sse, int* __restrict__ part_bad, ReconGeo g) {
+                                                         double* __restrict__ part_sse, int* __restrict__ part_bad, ReconGeo g,
+                                                         CropGeo x) {
   const long long blk = blockIdx.x;
   const long long d = blk / g.n_chunks;
   const int chunk = (int)(blk % g.n_chunks);
@@ -115,11 +143,11 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
     const long long s0l = (long long)chunk * kChunk + ((long long)it * kThreads + threadIdx.x) * 4;
     if (s0l >= g.E) break;
     const int s0 = (int)s0l;
-    float x[4], t[4] = {0.f, 0.f, 0.f, 0.f};
+    float xs[4], t[4] = {0.f, 0.f, 0.f, 0.f};
     int n = 4;
     if (VEC) {                                           // E % 4 == 0: whole quads only
       const float4 xv = *reinterpret_cast<const float4*>(yd + s0);
-      x[0] = xv.x; x[1] = xv.y; x[2] = xv.z; x[3] = xv.w;
+      xs[0] = xv.x; xs[1] = xv.y; xs[2] = xv.z; xs[3] = xv.w;
       if (td) {
         const float4 tv = *reinterpret_cast<const float4*>(td + s0);
         t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
@@ -128,23 +156,61 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
       n = g.E - s0 < 4 ? g.E - s0 : 4;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        x[k] = k < n ? yd[s0 + k] : 0.0f;
+        xs[k] = k < n ? yd[s0 + k] : 0.0f;
         if (td) t[k] = k < n ? td[s0 + k] : 0.0f;
+      }
+    }
+    long long co[4] = {-1, -1, -1, -1};                  // CROP: offset inside the cropped datapoint, -1 outside the extent
+    if (CROP) {
+      if (VEC) {
+        int e0;
+        const int row = crop_row(g, x, s0 / g.R, e0);
+        e0 += s0 % g.R;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) co[k] = (row >= 0 && e0 + k < x.L) ? (long long)row + e0 + k : -1;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (k < n) {
+            int e0;
+            const int row = crop_row(g, x, (s0 + k) / g.R, e0);
+            e0 += (s0 + k) % g.R;
+            co[k] = (row >= 0 && e0 < x.L) ? (long long)row + e0 : -1;
+          }
+        }
       }
     }
     Elem e[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      e[k] = finish(x[k], g.mode);
+      e[k] = finish(xs[k], g.mode);
       if (k < n) {
+        const bool in = !CROP || co[k] >= 0;
         const bool b = e[k].bad || !(fabsf(t[k]) < __builtin_inff());
-        bad += (int)e[k].bad + (int)!(fabsf(t[k]) < __builtin_inff());
+        bad += in ? (int)e[k].bad + (int)!(fabsf(t[k]) < __builtin_inff()) : 0;
         const float df = t[k] - e[k].v;
         const double dd = (double)df;
-        acc += b ? 0.0 : dd * dd;                        // (a bad element makes the datapoint's sse NaN in the second kernel)
+        acc += (b || !in) ? 0.0 : dd * dd;               // (a bad element makes the datapoint's sse NaN in the second kernel)
       }
     }
-    if (u8 || whole) {
+    if (CROP) {
+      if (u8 || whole) {
+        const long long cbase = d * x.Ec;
+        if (VEC && x.vec_out && co[0] >= 0 && co[3] >= 0) {
+          const long long o = cbase + co[0];
+          if (whole) *reinterpret_cast<float4*>(whole + o) = make_float4(e[0].v, e[1].v, e[2].v, e[3].v);
+          if (u8) *reinterpret_cast<unsigned*>(u8 + o) = e[0].q | (e[1].q << 8) | (e[2].q << 16) | (e[3].q << 24);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            if (k < n && co[k] >= 0) {
+              if (whole) whole[cbase + co[k]] = e[k].v;
+              if (u8) u8[cbase + co[k]] = (uint8_t)e[k].q;
+            }
+          }
+        }
+      }
+    } else if (u8 || whole) {
       if (VEC) {
         const long long o = base + whole_offset(g, s0 / g.R, s0 % g.R);
         if (whole) *reinterpret_cast<float4*>(whole + o) = make_float4(e[0].v, e[1].v, e[2].v, e[3].v);
@@ -194,43 +260,51 @@ extern "C" int64_t rcb_recon_workspace_bytes(int64_t n_data, int64_t elems_per_d
   return n_data * n_chunks * (int64_t)(sizeof(double) + sizeof(int));
 }
 
-extern "C" int rcb_recon_finish(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
-                                const int32_t* patch_nums, const int32_t* patch_size, int32_t mode, uint8_t* u8, float* whole,
-                                double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes, rcb_stream_t stream) {
-  RCB_REQUIRE(y && workspace, RCB_ERR_ARG, "recon_finish: null y or workspace");
-  RCB_REQUIRE(mode == 0 || mode == 1, RCB_ERR_ARG, "recon_finish: mode %d (0 = 8-bit, 1 = raw)", mode);
-  RCB_REQUIRE(nd >= 0 && nd <= 3, RCB_ERR_UNSUPPORTED, "recon_finish: %d grid dimensions (0 .. 3)", nd);
-  RCB_REQUIRE(nd == 0 || (patch_nums && patch_size), RCB_ERR_ARG, "recon_finish: null patch geometry");
-  RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "recon_finish: %d channels (1 .. 32)", channels);
-  RCB_REQUIRE(n_rows > 0 && n_pix > 0, RCB_ERR_SHAPE, "recon_finish: %lld rows of %d pixels", (long long)n_rows, n_pix);
-  RCB_REQUIRE(!(u8 && mode == 1), RCB_ERR_ARG, "recon_finish: the raw mode has no 8-bit output");
-  RCB_REQUIRE(!(sse && !target), RCB_ERR_ARG, "recon_finish: sse needs a target");
+// both entries: `size` null is rcb_recon_finish (every datapoint fills its grid)
+static int finish_entry(const char* who, const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels,
+                        int32_t nd, const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t mode,
+                        uint8_t* u8, float* whole, double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes,
+                        rcb_stream_t stream) {
+  RCB_REQUIRE(y && workspace, RCB_ERR_ARG, "%s: null y or workspace", who);
+  RCB_REQUIRE(mode == 0 || mode == 1, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw)", who, mode);
+  RCB_REQUIRE(nd >= (size ? 1 : 0) && nd <= 3, RCB_ERR_UNSUPPORTED, "%s: %d grid dimensions (%d .. 3)", who, nd, size ? 1 : 0);
+  RCB_REQUIRE(nd == 0 || (patch_nums && patch_size), RCB_ERR_ARG, "%s: null patch geometry", who);
+  RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "%s: %d channels (1 .. 32)", who, channels);
+  RCB_REQUIRE(n_rows > 0 && n_pix > 0, RCB_ERR_SHAPE, "%s: %lld rows of %d pixels", who, (long long)n_rows, n_pix);
+  RCB_REQUIRE(!(u8 && mode == 1), RCB_ERR_ARG, "%s: the raw mode has no 8-bit output", who);
+  RCB_REQUIRE(!(sse && !target), RCB_ERR_ARG, "%s: sse needs a target", who);
   ReconGeo g;
+  CropGeo x;
   long long per = 1, P = 1;
-  for (int i = 0; i < 3; ++i) g.pn[i] = g.ps[i] = 1;
+  for (int i = 0; i < 3; ++i) g.pn[i] = g.ps[i] = x.sz[i] = 1;
   for (int i = 0; i < nd; ++i) {
-    RCB_REQUIRE(patch_nums[i] > 0 && patch_size[i] > 0, RCB_ERR_SHAPE, "recon_finish: axis %d has %d patches of %d pixels", i,
+    RCB_REQUIRE(patch_nums[i] > 0 && patch_size[i] > 0, RCB_ERR_SHAPE, "%s: axis %d has %d patches of %d pixels", who, i,
                 patch_nums[i], patch_size[i]);
     g.pn[3 - nd + i] = patch_nums[i];
     g.ps[3 - nd + i] = patch_size[i];
     per *= patch_nums[i];
     P *= patch_size[i];
-    RCB_REQUIRE(per <= 0x7fffffffLL && P <= 0x7fffffffLL, RCB_ERR_SHAPE, "recon_finish: patch geometry overflows");
+    RCB_REQUIRE(per <= 0x7fffffffLL && P <= 0x7fffffffLL, RCB_ERR_SHAPE, "%s: patch geometry overflows", who);
+    if (size) {
+      RCB_REQUIRE(size[i] >= 1 && size[i] <= (long long)patch_nums[i] * patch_size[i], RCB_ERR_SHAPE,
+                  "%s: axis %d of the signal has %d positions (1 .. %lld)", who, i, size[i], (long long)patch_nums[i] * patch_size[i]);
+      x.sz[3 - nd + i] = size[i];
+    }
   }
   if (nd == 0) g.ps[2] = n_pix, P = n_pix;
-  RCB_REQUIRE(P == n_pix, RCB_ERR_SHAPE, "recon_finish: the patch has %lld pixels, the rows %d", P, n_pix);
-  RCB_REQUIRE(n_rows % per == 0, RCB_ERR_SHAPE, "recon_finish: %lld rows are no whole number of datapoints of %lld patches",
+  RCB_REQUIRE(P == n_pix, RCB_ERR_SHAPE, "%s: the patch has %lld pixels, the rows %d", who, P, n_pix);
+  RCB_REQUIRE(n_rows % per == 0, RCB_ERR_SHAPE, "%s: %lld rows are no whole number of datapoints of %lld patches", who,
               (long long)n_rows, per);
-  RCB_REQUIRE(per * P <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED, "recon_finish: %lld pixels per datapoint (elements: up to 2^31 - 1)",
+  RCB_REQUIRE(per * P <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED, "%s: %lld pixels per datapoint (elements: up to 2^31 - 1)", who,
               per * P);                                      // (per, P < 2^31: the product fits 64 bits)
   const long long E = per * P * channels;
-  RCB_REQUIRE(E <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED, "recon_finish: %lld elements per datapoint (up to 2^31 - 1)", E);
+  RCB_REQUIRE(E <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED, "%s: %lld elements per datapoint (up to 2^31 - 1)", who, E);
   const long long n_data = n_rows / per;
   const int64_t need = rcb_recon_workspace_bytes(n_data, E);
-  RCB_REQUIRE(need > 0, RCB_ERR_UNSUPPORTED, "recon_finish: %lld datapoints of %lld elements need more than 2^31 - 1 workgroups",
+  RCB_REQUIRE(need > 0, RCB_ERR_UNSUPPORTED, "%s: %lld datapoints of %lld elements need more than 2^31 - 1 workgroups", who,
               n_data, E);
   RCB_REQUIRE(workspace_bytes >= need && aligned(workspace, 8), RCB_ERR_SHAPE,
-              "recon_finish: workspace of %lld bytes (8-byte aligned), %lld needed", (long long)workspace_bytes, (long long)need);
+              "%s: workspace of %lld bytes (8-byte aligned), %lld needed", who, (long long)workspace_bytes, (long long)need);
   g.C = channels;
   g.R = g.ps[2] * channels;
   g.E = (int)E;
@@ -239,16 +313,42 @@ extern "C" int rcb_recon_finish(const float* y, const float* target, int64_t n_r
   const long long blocks = n_data * g.n_chunks;
   double* part_sse = static_cast<double*>(workspace);
   int* part_bad = reinterpret_cast<int*>(part_sse + blocks);
-  const bool vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16)) && (!whole || aligned(whole, 16)) &&
-                   (!u8 || aligned(u8, 4));
-  if (vec)
-    recon_kernel<true><<<(unsigned)blocks, kThreads, 0, (hipStream_t)stream>>>(y, target, u8, whole, part_sse, part_bad, g);
-  else
-    recon_kernel<false><<<(unsigned)blocks, kThreads, 0, (hipStream_t)stream>>>(y, target, u8, whole, part_sse, part_bad, g);
+  hipStream_t st = (hipStream_t)stream;
+  if (!size) {
+    x.L = x.vec_out = 0, x.Ec = 0;
+    const bool vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16)) && (!whole || aligned(whole, 16)) &&
+                     (!u8 || aligned(u8, 4));
+    if (vec) recon_kernel<true, false><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, g, x);
+    else recon_kernel<false, false><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, g, x);
+  } else {
+    // the 16-byte loads need only the inputs aligned; the stores go by quad (vec_out), the cropped rows seldom being multiples of 4
+    x.L = x.sz[2] * channels;                                // (<= E: the products below fit)
+    x.Ec = (long long)x.sz[0] * x.sz[1] * x.L;
+    const bool vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16));
+    x.vec_out = x.L % 4 == 0 && (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, 4));
+    if (vec) recon_kernel<true, true><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, g, x);
+    else recon_kernel<false, true><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, g, x);
+  }
   RCB_LAUNCH_CHECK();
   if (sse || n_bad) {
-    recon_reduce_kernel<<<(unsigned)n_data, kThreads, 0, (hipStream_t)stream>>>(part_sse, part_bad, g.n_chunks, sse, n_bad);
+    recon_reduce_kernel<<<(unsigned)n_data, kThreads, 0, st>>>(part_sse, part_bad, g.n_chunks, sse, n_bad);
     RCB_LAUNCH_CHECK();
   }
   return RCB_OK;
+}
+
+extern "C" int rcb_recon_finish(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
+                                const int32_t* patch_nums, const int32_t* patch_size, int32_t mode, uint8_t* u8, float* whole,
+                                double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes, rcb_stream_t stream) {
+  return finish_entry("recon_finish", y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, nullptr, mode, u8, whole, sse,
+                      n_bad, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rcb_recon_finish_crop(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels,
+                                     int32_t nd, const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size,
+                                     int32_t mode, uint8_t* u8, float* whole, double* sse, int32_t* n_bad, void* workspace,
+                                     int64_t workspace_bytes, rcb_stream_t stream) {
+  RCB_REQUIRE(size, RCB_ERR_ARG, "recon_finish_crop: null size");
+  return finish_entry("recon_finish_crop", y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, size, mode, u8, whole,
+                      sse, n_bad, workspace, workspace_bytes, stream);
 }

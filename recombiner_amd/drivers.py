@@ -283,6 +283,41 @@ def compress_signals(config, dataset, checkpoint, signals, x=None, channels_firs
     return compress(config, dataset, checkpoint, x, y, **kw)
 
 
+def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_first=False, bitstream_path=None, **kw):
+    """`compress_signals` for signals of ANY size that the preset can be fitted to: `signals` is [n, *size, C] (or [n, C, *size]
+    with channels_first), uint8 or fp32, one size per call.  The config is fitted (utils.fit_config: patched presets get the
+    next whole patch grid that level 2 divides; unpatched presets keep theirs and take signals up to it), the signals'
+    edge samples are replicated out to that grid while they are cut into y on the device (rcb_signal_patch_pad), and `compress`
+    runs with the fitted config -- a checkpoint trained at the preset's patch_nums drives it, its priors being per parameter.
+    -> (distortion, model, fitted_config).  `distortion` counts the REAL samples only (rcb_recon_finish_crop); the training
+    loss does not: padded samples are fitted at full weight and cost rate, and a wholly padded patch still costs its groups.
+    The bitstream (bitstream_path) is version 2 and carries `size`; bitstream.decode_signal_any decodes and crops it.
+    Rate: bpp = bitstream.payload_bits(blob) / (n * prod(size)), bits per real sample position.
+    There is no landscape swap and no origin: the signals are coded in the orientation they are passed in -- a portrait photograph
+    on a landscape-trained prior is the caller's to transpose.  Every other argument is `compress`'s."""
+    from . import bitstream, utils
+    device = kw.get("device", "cuda")
+    dd = config["data_dim"]
+    if signals.dim() != dd + 2:
+        raise ValueError("compress_signals_any: %d axes for a %d-D preset ([n, *size, C] expected)" % (signals.dim(), dd))
+    view = signals.to(device)
+    if channels_first:
+        view = view.movedim(1, -1)
+    if view.shape[-1] != config["output_dim"]:
+        raise ValueError("compress_signals_any: %d channels, the preset has %d" % (view.shape[-1], config["output_dim"]))
+    size = tuple(int(v) for v in view.shape[1:-1])
+    fitted = utils.fit_config(config, size)
+    y = ops.signal_patch_pad(view, utils.signal_layout(fitted))
+    if x is None:
+        x = utils.preset_inputs(fitted, device)[None].expand(y.shape[0], -1, -1)
+    _, model = compress(fitted, dataset, checkpoint, x, y, **kw)
+    distortion = model.report(x, y, size=size)
+    if bitstream_path is not None:
+        with open(bitstream_path, "wb") as f:
+            f.write(bitstream.encode(model, extent=size))
+    return distortion, model, fitted
+
+
 def rd_point(config, dataset, X, Y_train, Y_test, max_bitrate, device="cuda", seed=42, n_em_iter=550, first_epochs=200, epochs=100,
              lr=2e-4, n_opt=30000, finetune_epochs=None, precision=0, noise_source=None):
     """One rate-distortion point from scratch with the product alone: learn the prior (and the mappings) on Y_train

@@ -1168,7 +1168,7 @@ def recon_whole_shape(shape, layout=None):
     return (N // per,) + tuple(a * b for a, b in zip(layout.patch_nums, layout.patch_size)) + (Cc,)
 
 
-def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, want_whole=False, out=None):
+def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, want_whole=False, out=None, size=None):
     """The last step of a reconstruction y [N, P, C] (fp32; the rows are datapoints, or with `layout` = PeLayout(patch_nums,
     patch_size) the patches of stitched signals) and its score against `target` (same layout), in one pass (rcb_recon_finish):
     mode RECON_8BIT rounds to the 8-bit lattice as the reference's metric does (clip, x 255, round half to even, / 255),
@@ -1177,7 +1177,11 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
         sse fp64 [n_data] = per-datapoint sum of squared errors (None without target; NaN for a datapoint with a non-finite
         element), n_bad int32 [n_data] = its non-finite elements of y and target).
     sse is bitwise reproducible and the same for a datapoint alone or inside a batch.  Nothing is read back: no host sync.
-    out: optional preallocated (u8, whole, sse, n_bad) -- entries None are allocated here."""
+    out: optional preallocated (u8, whole, sse, n_bad) -- entries None are allocated here.
+    size (needs a layout; patch_nums of ones for an unpatched preset): only the leading size[i] <= G_i positions per axis of
+    every signal are real, the rest what signal_patch_pad replicated (rcb_recon_finish_crop): u8 / whole are [n_data, *size, C],
+    and an element outside that extent adds +0.0 to sse and is never counted in n_bad.  The additions and their order are
+    those without a size, and with size = G so is every output bit."""
     lib = _lib.load()
     if y.dim() != 3 or y.dtype != f32 or not y.is_cuda or not y.is_contiguous():
         raise RcbError("recon_finish: y must be a contiguous fp32 GPU tensor [N, P, C]")
@@ -1195,6 +1199,14 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
     n_ws = int(lib.rcb_recon_workspace_bytes(max(n_data, 1), per * P * Cc)) if N and P and Cc else -1
     dev = y.device
     shape = recon_whole_shape((N, P, Cc), layout) if per > 0 and N % per == 0 else (N, P, Cc)
+    crop = []
+    if size is not None:
+        size = [int(v) for v in size]
+        if nd == 0 or len(size) != nd:
+            raise RcbError(f"recon_finish: size of {len(size)} entries for a layout of {nd} axes (a PeLayout of as many)")
+        if len(shape) == nd + 2 and all(1 <= s <= g for s, g in zip(size, shape[1:-1])):      # (else: the library says why)
+            shape = (n_data, *size, Cc)
+        crop = [(C.c_int32 * 3)(*(size + [0] * (3 - nd)))]
     u8, whole, sse, n_bad = out if out is not None else (None,) * 4
     if want_u8 and u8 is None:
         u8 = torch.empty(shape, device=dev, dtype=torch.uint8)
@@ -1209,8 +1221,9 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
             raise RcbError(f"recon_finish: output of shape {tuple(t_.shape)} {t_.dtype}, expected contiguous {tuple(want)} {dt} "
                            "on the device of y")
     ws = torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8)       # (a refused shape: the library says why)
-    _launch("rcb_recon_finish", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps, int(mode),
-            ptr(u8, torch.uint8, True), ptr(whole, f32, True), ptr(sse, f64, True), ptr(n_bad, i32), ptr(ws), max(n_ws, 8))
+    _launch("rcb_recon_finish_crop" if crop else "rcb_recon_finish", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps,
+            *crop, int(mode), ptr(u8, torch.uint8, True), ptr(whole, f32, True), ptr(sse, f64, True), ptr(n_bad, i32), ptr(ws),
+            max(n_ws, 8))
     return u8, whole, sse, n_bad
 
 
@@ -1227,30 +1240,43 @@ def signal_patch(signals, layout, out=None):
     with ANY strides and storage offset -- channel-first storage, transposed axes, a window of a larger signal, an expanded
     channel: the strides go to the kernel as they are and nothing is copied.  recon_finish(y, layout=layout) stitches y back.
     out: optional preallocated contiguous fp32 [N, P, C].  No host sync."""
+    return _signal_patch("signal_patch", signals, layout, out, pad=False)
+
+
+def signal_patch_pad(signals, layout, out=None):
+    """`signal_patch` for signals SMALLER than the layout's grid G: `signals` is [n, *size, C] with 1 <= size[i] <= G_i (read from
+    its shape; any strides, uint8 or fp32) and grid position g_i takes the sample at min(g_i, size[i] - 1) -- the edge samples
+    replicated on the far side of every axis (rcb_signal_patch_pad).  With size = G the result is signal_patch's bit for bit.
+    recon_finish(y, layout=layout, size=size) gives the signals back.  out: optional contiguous fp32 [N, P, C].  No host sync."""
+    return _signal_patch("signal_patch_pad", signals, layout, out, pad=True)
+
+
+def _signal_patch(what, signals, layout, out, pad):
     if not isinstance(signals, torch.Tensor) or not signals.is_cuda:
-        raise RcbError("signal_patch: signals must be a GPU tensor (the HIP path has no CPU fallback)")
+        raise RcbError(f"{what}: signals must be a GPU tensor (the HIP path has no CPU fallback)")
     if signals.dtype not in SIGNAL_KINDS:
-        raise RcbError(f"signal_patch: signals must be uint8 or fp32, got {signals.dtype}")
+        raise RcbError(f"{what}: signals must be uint8 or fp32, got {signals.dtype}")
     pn, ps = list(layout.patch_nums), list(layout.patch_size)
     nd = len(pn)
     if len(ps) != nd or signals.dim() != nd + 2:
-        raise RcbError(f"signal_patch: signals of {signals.dim()} axes for a layout of {nd} ([n, *grid, C] expected)")
+        raise RcbError(f"{what}: signals of {signals.dim()} axes for a layout of {nd} ([n, *grid, C] expected)")
     grid = tuple(a * b for a, b in zip(pn, ps))
     n, Cc = int(signals.shape[0]), int(signals.shape[-1])
-    if tuple(signals.shape[1:-1]) != grid:
-        raise RcbError(f"signal_patch: signals on the grid {tuple(signals.shape[1:-1])}, the layout's is {grid}")
+    if not pad and tuple(signals.shape[1:-1]) != grid:       # (pad: the library holds the extent to [1, G])
+        raise RcbError(f"{what}: signals on the grid {tuple(signals.shape[1:-1])}, the layout's is {grid}")
     per, P = int(np.prod(pn)) if nd else 1, int(np.prod(ps)) if nd else 1
     shape = (n * per, P, Cc)
     fits = 0 <= per * P * Cc <= 0x7fffffff                   # (a refused shape gets no buffer: the library says why)
     if out is None:
         out = torch.empty(shape if fits else (1,), device=signals.device, dtype=f32)
     elif tuple(out.shape) != shape or out.dtype != f32 or out.device != signals.device or not out.is_contiguous():
-        raise RcbError(f"signal_patch: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {f32} on the "
+        raise RcbError(f"{what}: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {f32} on the "
                        "device of signals")
     st = [int(v) for v in signals.stride()]
     arr = max(nd, 1)
-    _launch("rcb_signal_patch", C.c_void_p(signals.data_ptr()), SIGNAL_KINDS[signals.dtype], n, nd, (C.c_int32 * arr)(*pn),
-            (C.c_int32 * arr)(*ps), Cc, st[0], (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
+    size = [(C.c_int32 * arr)(*signals.shape[1:-1])] if pad else []
+    _launch("rcb_" + what, C.c_void_p(signals.data_ptr()), SIGNAL_KINDS[signals.dtype], n, nd, (C.c_int32 * arr)(*pn),
+            (C.c_int32 * arr)(*ps), *size, Cc, st[0], (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
     return out
 
 

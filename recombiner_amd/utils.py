@@ -6,6 +6,8 @@ utils.py (names and argument meaning).  The arithmetic-heavy helper of the refer
 kernel on their own parameters, the function of that name below keeps the reference's signature
 for code that calls it directly.
 """
+import copy
+
 import numpy as np
 import torch
 
@@ -227,6 +229,32 @@ def signal_view(config, tensor, channels_first=False, origin=None, landscape=Tru
     return tensor
 
 
+def fit_config(config, size):
+    """A copy of the preset `config` whose grid holds a signal of `size` (one entry per spatial axis); the preset itself is
+    never changed.  Patched presets: patch_nums[i] = ceil(size[i] / pixel_sizes[i]) rounded up to a multiple of
+    hierarchical_patch_nums["level2"][i] (level 2 groups that many patches per axis), level3 = the new patch_nums, level2 as
+    it is.  Unpatched presets: the config is unchanged and a size[i] > pixel_sizes[i] is a ValueError (one INR, one grid).
+    The signal is then edge-padded to the grid (ops.signal_patch_pad) and cropped after decoding (ops.recon_finish(size=)).  The
+    priors and groupings of a checkpoint are per parameter, so one trained at the preset's patch_nums drives any fitted config."""
+    dd = config["data_dim"]
+    size = [int(v) for v in size]
+    if len(size) != dd or min(size) < 1:
+        raise ValueError("fit_config: size %r for a %d-D preset (one positive entry per axis)" % (size, dd))
+    ps = [int(v) for v in config["pixel_sizes"][:dd]]
+    out = copy.deepcopy(config)
+    if not config["patch"]:
+        for i in range(dd):
+            if size[i] > ps[i]:
+                raise ValueError("fit_config: axis %d of the signal has %d positions, the unpatched preset's grid %d"
+                                 % (i, size[i], ps[i]))
+        return out
+    l2 = [int(v) for v in config["hierarchical_patch_nums"]["level2"][:dd]]
+    pn = [-(-(-(-size[i] // ps[i])) // l2[i]) * l2[i] for i in range(dd)]
+    out["patch_nums"] = pn + list(config["patch_nums"][dd:])
+    out["hierarchical_patch_nums"]["level3"] = list(out["patch_nums"])
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # metrics (utils.py:200-260) -- host numpy, as in the reference
 # ---------------------------------------------------------------------------------------------
@@ -289,17 +317,21 @@ def metric_from_sse(sse, n_elems, dataset):
     return (-10.0 * np.log10(sse.sum() / (n * sse.size))).item()
 
 
-def metric_device(y_true, y_pred, dataset, layout=None):
+def metric_device(y_true, y_pred, dataset, layout=None, size=None):
     """`metric(y_true, y_pred, dataset)` for GPU tensors [N, P, C] without copying them to the host: one pass of
     rcb_recon_finish (rounding to 8 bits where the dataset's metric does), then only the per-datapoint sums -- and the counts
     of non-finite elements, which make a datapoint's figure NaN as numpy's would be -- are read back.  layout: ops.PeLayout
     of a patched preset (rows = patches of stitched signals) or None (rows = datapoints); the batch-wide figures do not
-    depend on it."""
+    depend on it.
+    size (needs a layout; patch_nums of ones for an unpatched preset): only the leading size[i] positions per axis of every
+    signal are real, the rest edge padding (ops.signal_patch_pad) -- the figure is over the real samples alone
+    (rcb_recon_finish_crop), the mean over prod(size) * C elements per signal."""
     from . import ops
     if dataset not in METRIC_ROUNDS:
         raise ValueError(dataset)
     mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
     y_pred = y_pred.detach().to(torch.float32).contiguous()
     y_true = y_true.detach().to(device=y_pred.device, dtype=torch.float32).contiguous()
-    _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode)
-    return metric_from_sse(sse.cpu().numpy(), y_pred.numel() // sse.numel(), dataset)
+    _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode, size=size)
+    n_elems = y_pred.numel() // sse.numel() if size is None else int(np.prod([int(v) for v in size])) * y_pred.shape[-1]
+    return metric_from_sse(sse.cpu().numpy(), n_elems, dataset)
