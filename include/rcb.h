@@ -697,7 +697,8 @@ int rcb_recon_finish(const float* y, const float* target, int64_t n_rows, int32_
  *   src_kind 1 (fp32):  the 32 bits unchanged -- NaN payloads, +-0, infinities and denormals keep their bits
  * y [n_data * prod(patch_nums)][prod(patch_size)][channels] fp32, contiguous, in the row order of rcb_recon_finish and of
  * rcb_siren_desc.pe_grid_dims: row n is patch n % prod(patch_nums) (row-major over patch_nums) of signal n / prod(patch_nums), its
- * pixel p the row-major position inside the patch.  rcb_recon_finish on this y with the same geometry gives the signals back.
+ * pixel p the row-major position inside the patch.  rcb_recon_finish on this y with the same geometry gives the signals back
+ * (both ends, and their _pad / _crop forms, decode that row order with the one routine of csrc/patch_grid.h).
  * Memory: quads of 4 consecutive elements of y.  With channel_stride = 1, axis_stride[nd-1] = channels, patch_size[nd-1] * channels a
  * multiple of 4 and the base pointers, data_stride and the outer strides keeping every run start on a 4-element boundary (y: 16
  * bytes), a quad is one 4-byte (uint8) / 16-byte (fp32) load and one 16-byte store; otherwise the same quads move element by

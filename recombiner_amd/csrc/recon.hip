@@ -23,7 +23,9 @@
 // same quads are moved element by element.  HBM-bound: bytes = y + target + outputs.
 //
 // rcb_recon_finish_crop is the same kernel (template parameter CROP) for datapoints of which only a leading extent is real.
-#include "rcb_common.h"
+// Where a run lies in the stitched signal, the chunking and the validation of the patch grid are patch_grid.h's, shared with
+// signal.hip, which cuts the signals the other way.
+#include "patch_grid.h"
 
 #pragma clang fp contract(off)
 
@@ -31,53 +33,30 @@ using namespace rcb;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kQuadsPerThread = 8;
-constexpr int kChunk = kThreads * 4 * kQuadsPerThread;      // 8192 elements of one datapoint per workgroup
-
+// rcb_recon_finish_crop: of the grid row (g0, g1) of g only the first g.L elements e = b2 * R + off exist, and only for g0 < sz[0],
+// g1 < sz[1].  An element outside adds +0.0 to the sum, is never counted and is not written; the outputs are contiguous over the
+// extent.
 struct ReconGeo {
-  int pn[3], ps[3];       // patches per axis / pixels per axis of a patch, right-aligned (leading axes 1)
-  int C;                  // channels
-  int R;                  // floats of one contiguous run: ps[2] * C
-  int E;                  // elements of one datapoint
-  int n_chunks;           // ceil(E / kChunk)
+  PatchGeo g;
   int mode;
+  int vec_out;            // crop: L % 4 == 0 and aligned outputs: a quad inside the extent is one 16-byte / 4-byte store
+  long long Ec;           // crop: elements of one cropped datapoint
 };
 
 // offset of source element s (a multiple of R plus `off` < R) of a datapoint inside its stitched signal
-__device__ __forceinline__ int whole_offset(const ReconGeo& g, int run, int off) {
-  int r = run;
-  const int p1 = r % g.ps[1]; r /= g.ps[1];
-  const int p0 = r % g.ps[0]; r /= g.ps[0];
-  const int b2 = r % g.pn[2]; r /= g.pn[2];
-  const int b1 = r % g.pn[1];
-  const int b0 = r / g.pn[1];
-  const int g0 = b0 * g.ps[0] + p0, g1 = b1 * g.ps[1] + p1;
+__device__ __forceinline__ int whole_offset(const PatchGeo& g, int run, int off) {
+  int g0, g1, b2;
+  decode_run<false>(g, run, g0, g1, b2);
   // ((g0 * G1 + g1) * G2 + b2 * ps2) * C + off, with G2 * C = pn2 * R and ps2 * C = R
   return ((g0 * (g.pn[1] * g.ps[1]) + g1) * g.pn[2] + b2) * g.R + off;
 }
 
-// rcb_recon_finish_crop: the datapoint's own extent inside the stitched grid.  The elements of grid row (g0, g1) are numbered
-// e = b2 * R + off; the first L = size[last] * C of them exist.  An element outside adds +0.0 to the sum, is never counted and
-// is not written; the outputs are contiguous over the extent.
-struct CropGeo {
-  int sz[3];              // extent per axis, right-aligned (leading axes 1)
-  int L;                  // sz[2] * C
-  int vec_out;            // L % 4 == 0 and aligned outputs: a quad inside the extent is one 16-byte / 4-byte store
-  long long Ec;           // elements of one cropped datapoint
-};
-
 // grid row of run `run` inside the cropped datapoint: -> offset of its element 0, or -1 when the row lies outside; e0 = b2 * R
-__device__ __forceinline__ int crop_row(const ReconGeo& g, const CropGeo& x, int run, int& e0) {
-  int r = run;
-  const int p1 = r % g.ps[1]; r /= g.ps[1];
-  const int p0 = r % g.ps[0]; r /= g.ps[0];
-  const int b2 = r % g.pn[2]; r /= g.pn[2];
-  const int b1 = r % g.pn[1];
-  const int b0 = r / g.pn[1];
-  const int g0 = b0 * g.ps[0] + p0, g1 = b1 * g.ps[1] + p1;
+__device__ __forceinline__ int crop_row(const PatchGeo& g, int run, int& e0) {
+  int g0, g1, b2;
+  decode_run<false>(g, run, g0, g1, b2);
   e0 = b2 * g.R;
-  return (g0 < x.sz[0] && g1 < x.sz[1]) ? (g0 * x.sz[1] + g1) * x.L : -1;
+  return (g0 < g.sz[0] && g1 < g.sz[1]) ? (g0 * g.sz[1] + g1) * g.L : -1;
 }
 
 struct Elem {
@@ -129,8 +108,8 @@ __device__ __forceinline__ bool block_sum(double& acc, int& bad) {
 template <bool VEC, bool CROP>
 __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict__ y, const float* __restrict__ target,
                                                          uint8_t* __restrict__ u8, float* __restrict__ whole,
-                                                         double* __restrict__ part_sse, int* __restrict__ part_bad, ReconGeo g,
-                                                         CropGeo x) {
+                                                         double* __restrict__ part_sse, int* __restrict__ part_bad, ReconGeo x) {
+  const PatchGeo& g = x.g;
   const long long blk = blockIdx.x;
   const long long d = blk / g.n_chunks;
   const int chunk = (int)(blk % g.n_chunks);
@@ -164,18 +143,18 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
     if (CROP) {
       if (VEC) {
         int e0;
-        const int row = crop_row(g, x, s0 / g.R, e0);
+        const int row = crop_row(g, s0 / g.R, e0);
         e0 += s0 % g.R;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) co[k] = (row >= 0 && e0 + k < x.L) ? (long long)row + e0 + k : -1;
+        for (int k = 0; k < 4; ++k) co[k] = (row >= 0 && e0 + k < g.L) ? (long long)row + e0 + k : -1;
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           if (k < n) {
             int e0;
-            const int row = crop_row(g, x, (s0 + k) / g.R, e0);
+            const int row = crop_row(g, (s0 + k) / g.R, e0);
             e0 += (s0 + k) % g.R;
-            co[k] = (row >= 0 && e0 < x.L) ? (long long)row + e0 : -1;
+            co[k] = (row >= 0 && e0 < g.L) ? (long long)row + e0 : -1;
           }
         }
       }
@@ -183,7 +162,7 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
     Elem e[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      e[k] = finish(xs[k], g.mode);
+      e[k] = finish(xs[k], x.mode);
       if (k < n) {
         const bool in = !CROP || co[k] >= 0;
         const bool b = e[k].bad || !(fabsf(t[k]) < __builtin_inff());
@@ -249,8 +228,6 @@ __global__ void __launch_bounds__(kThreads) recon_reduce_kernel(const double* __
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int64_t rcb_recon_workspace_bytes(int64_t n_data, int64_t elems_per_datapoint) {
@@ -273,25 +250,11 @@ static int finish_entry(const char* who, const float* y, const float* target, in
   RCB_REQUIRE(n_rows > 0 && n_pix > 0, RCB_ERR_SHAPE, "%s: %lld rows of %d pixels", who, (long long)n_rows, n_pix);
   RCB_REQUIRE(!(u8 && mode == 1), RCB_ERR_ARG, "%s: the raw mode has no 8-bit output", who);
   RCB_REQUIRE(!(sse && !target), RCB_ERR_ARG, "%s: sse needs a target", who);
-  ReconGeo g;
-  CropGeo x;
-  long long per = 1, P = 1;
-  for (int i = 0; i < 3; ++i) g.pn[i] = g.ps[i] = x.sz[i] = 1;
-  for (int i = 0; i < nd; ++i) {
-    RCB_REQUIRE(patch_nums[i] > 0 && patch_size[i] > 0, RCB_ERR_SHAPE, "%s: axis %d has %d patches of %d pixels", who, i,
-                patch_nums[i], patch_size[i]);
-    g.pn[3 - nd + i] = patch_nums[i];
-    g.ps[3 - nd + i] = patch_size[i];
-    per *= patch_nums[i];
-    P *= patch_size[i];
-    RCB_REQUIRE(per <= 0x7fffffffLL && P <= 0x7fffffffLL, RCB_ERR_SHAPE, "%s: patch geometry overflows", who);
-    if (size) {
-      RCB_REQUIRE(size[i] >= 1 && size[i] <= (long long)patch_nums[i] * patch_size[i], RCB_ERR_SHAPE,
-                  "%s: axis %d of the signal has %d positions (1 .. %lld)", who, i, size[i], (long long)patch_nums[i] * patch_size[i]);
-      x.sz[3 - nd + i] = size[i];
-    }
-  }
-  if (nd == 0) g.ps[2] = n_pix, P = n_pix;
+  ReconGeo x;
+  PatchGeo& g = x.g;
+  long long per, P;
+  if (const int err = grid_axes(who, nd, patch_nums, patch_size, size, nullptr, g, per, P)) return err;
+  if (nd == 0) g.ps[2] = g.sz[2] = n_pix, P = n_pix;        // the rows are datapoints: one run each
   RCB_REQUIRE(P == n_pix, RCB_ERR_SHAPE, "%s: the patch has %lld pixels, the rows %d", who, P, n_pix);
   RCB_REQUIRE(n_rows % per == 0, RCB_ERR_SHAPE, "%s: %lld rows are no whole number of datapoints of %lld patches", who,
               (long long)n_rows, per);
@@ -305,29 +268,25 @@ static int finish_entry(const char* who, const float* y, const float* target, in
               n_data, E);
   RCB_REQUIRE(workspace_bytes >= need && aligned(workspace, 8), RCB_ERR_SHAPE,
               "%s: workspace of %lld bytes (8-byte aligned), %lld needed", who, (long long)workspace_bytes, (long long)need);
-  g.C = channels;
-  g.R = g.ps[2] * channels;
-  g.E = (int)E;
-  g.n_chunks = (int)((E + kChunk - 1) / kChunk);
-  g.mode = mode;
+  grid_elems(g, channels, E);
+  x.mode = mode;
   const long long blocks = n_data * g.n_chunks;
   double* part_sse = static_cast<double*>(workspace);
   int* part_bad = reinterpret_cast<int*>(part_sse + blocks);
   hipStream_t st = (hipStream_t)stream;
   if (!size) {
-    x.L = x.vec_out = 0, x.Ec = 0;
+    x.vec_out = 0, x.Ec = 0;
     const bool vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16)) && (!whole || aligned(whole, 16)) &&
                      (!u8 || aligned(u8, 4));
-    if (vec) recon_kernel<true, false><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, g, x);
-    else recon_kernel<false, false><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, g, x);
+    if (vec) recon_kernel<true, false><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+    else recon_kernel<false, false><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
   } else {
     // the 16-byte loads need only the inputs aligned; the stores go by quad (vec_out), the cropped rows seldom being multiples of 4
-    x.L = x.sz[2] * channels;                                // (<= E: the products below fit)
-    x.Ec = (long long)x.sz[0] * x.sz[1] * x.L;
+    x.Ec = (long long)g.sz[0] * g.sz[1] * g.L;               // (L <= E: the products fit)
     const bool vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16));
-    x.vec_out = x.L % 4 == 0 && (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, 4));
-    if (vec) recon_kernel<true, true><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, g, x);
-    else recon_kernel<false, true><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, g, x);
+    x.vec_out = g.L % 4 == 0 && (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, 4));
+    if (vec) recon_kernel<true, true><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+    else recon_kernel<false, true><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
   }
   RCB_LAUNCH_CHECK();
   if (sse || n_bad) {

@@ -4,8 +4,8 @@
 // rcb_signal_patch reads n_data signals on the grid G_i = patch_nums[i] * patch_size[i] through ONE addressing rule -- element
 // (d, g_0 .. g_nd-1, c) at src + d * data_stride + sum g_i * axis_stride[i] + c * channel_stride, strides in elements, >= 0 -- and
 // writes y contiguous in the row order rcb_recon_finish reads: row n is patch n % prod(patch_nums) (row-major) of signal
-// n / prod(patch_nums), its pixel p the row-major position inside the patch.  The index arithmetic is recon.hip's whole_offset with
-// the strides of the source in place of the contiguous whole signal.
+// n / prod(patch_nums), its pixel p the row-major position inside the patch.  Which grid row a run of y comes from is
+// patch_grid.h's decode_run, shared with recon.hip; here the strides of the source stand in place of the contiguous whole signal.
 //
 //   src_kind 0 (uint8):  y = (float)q / 255.0f         (one IEEE fp32 division: ToTensor's and numpy's)
 //   src_kind 1 (fp32):   the 32 bits of the source, unchanged (moved as integers: NaN payloads, -0, denormals keep their bits)
@@ -16,8 +16,13 @@
 // (uint8) or 16-byte (fp32) load and one 16-byte store.  Otherwise the same quads are moved element by element.  The host entry
 // decides; both paths give the same bits.  Pure data movement: bytes = src + y.  No LDS, no atomics.
 //
-// rcb_signal_patch_pad (below) is the same cut of signals smaller than the grid, their edge samples replicated out to it.
-#include "rcb_common.h"
+// rcb_signal_patch_pad (template parameter PAD) is the same cut of a signal that holds only size[i] <= G_i positions per axis:
+// grid position g_i reads source position min(g_i, size[i] - 1), the edge sample replicated on the far side of every axis.  Of a
+// grid row (g0, g1), numbered e = b2 * R + off, the first L = size[last] * C elements exist: with VEC (the same conditions, on the
+// strides of the axes that still have more than one position) a quad whose 4 elements lie below L is 4 consecutive source elements
+// on a 4-element boundary; any other quad moves element by element through the clipped index.  Every read is at a clipped
+// position: inside the source.
+#include "patch_grid.h"
 
 #pragma clang fp contract(off)
 
@@ -25,134 +30,52 @@ using namespace rcb;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kQuadsPerThread = 8;
-constexpr int kChunk = kThreads * 4 * kQuadsPerThread;      // 8192 elements of one signal per workgroup
-
 struct SignalGeo {
-  int pn[3], ps[3];           // patches per axis / pixels per axis of a patch, right-aligned (leading axes 1)
-  int C;                      // channels
-  int R;                      // elements of one run of y: ps[2] * C
-  int E;                      // elements of one signal
-  int n_chunks;               // ceil(E / kChunk)
+  PatchGeo g;
   long long ds, as[3], cs;    // source strides in elements: signal, axes (right-aligned, leading 0), channel
 };
 
-// source offset of pixel 0, channel 0 of run `run` of a signal's y: the run order is that of recon.hip's whole_offset
-// (patch b0 b1 b2 row-major, then the patch's rows p0 p1), the grid position g_i = b_i * ps_i + p_i
-__device__ __forceinline__ long long run_offset(const SignalGeo& g, int run) {
-  int r = run;
-  const int p1 = r % g.ps[1]; r /= g.ps[1];
-  const int p0 = r % g.ps[0]; r /= g.ps[0];
-  const int b2 = r % g.pn[2]; r /= g.pn[2];
-  const int b1 = r % g.pn[1];
-  const int b0 = r / g.pn[1];
-  const long long g0 = (long long)b0 * g.ps[0] + p0, g1 = (long long)b1 * g.ps[1] + p1, g2 = (long long)b2 * g.ps[2];
-  return g0 * g.as[0] + g1 * g.as[1] + g2 * g.as[2];
-}
-
 __device__ __forceinline__ unsigned unit8(unsigned q) { return __float_as_uint((float)q / 255.0f); }
 
-template <int KIND, bool VEC>
-__global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __restrict__ src, unsigned* __restrict__ y, SignalGeo g) {
+// PAD false never reads the extent (g.sz, g.L)
+template <int KIND, bool VEC, bool PAD>
+__global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __restrict__ src, unsigned* __restrict__ y, SignalGeo x) {
+  const PatchGeo& g = x.g;
   const long long blk = blockIdx.x;
   const long long d = blk / g.n_chunks;
   const int chunk = (int)(blk % g.n_chunks);
-  const uint8_t* s8 = static_cast<const uint8_t*>(src) + d * g.ds;
-  const unsigned* s32 = static_cast<const unsigned*>(src) + d * g.ds;
-  unsigned* yd = y + d * (long long)g.E;
-  for (int it = 0; it < kQuadsPerThread; ++it) {
-    const long long s0l = (long long)chunk * kChunk + ((long long)it * kThreads + threadIdx.x) * 4;
-    if (s0l >= g.E) break;
-    const int s0 = (int)s0l;
-    if (VEC) {                                           // R % 4 == 0: whole quads inside one run, 4 consecutive source elements
-      const long long o = run_offset(g, s0 / g.R) + s0 % g.R;
-      uint4 v;
-      if (KIND == 0) {
-        const unsigned w = *reinterpret_cast<const unsigned*>(s8 + o);
-        v = make_uint4(unit8(w & 0xffu), unit8((w >> 8) & 0xffu), unit8((w >> 16) & 0xffu), unit8(w >> 24));
-      } else {
-        v = *reinterpret_cast<const uint4*>(s32 + o);
-      }
-      *reinterpret_cast<uint4*>(yd + s0) = v;
-    } else {
-      const int n = g.E - s0 < 4 ? g.E - s0 : 4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (k < n) {
-          const int s = s0 + k, off = s % g.R;
-          const long long o = run_offset(g, s / g.R) + (long long)(off / g.C) * g.as[2] + (long long)(off % g.C) * g.cs;
-          yd[s] = KIND == 0 ? unit8(s8[o]) : s32[o];
-        }
-      }
-    }
-  }
-}
-
-// rcb_signal_patch_pad: the same cut of a signal that holds only size[i] <= G_i positions per axis -- grid position g_i reads source
-// position min(g_i, size[i] - 1), the edge sample replicated on the far side of every axis.  Element s of a signal's y decodes as in
-// signal_patch_kernel; e = b2 * R + off is its element inside the grid row (g0, g1), whose first L = size[last] * C elements exist.
-// VEC (the host entry's conditions of signal_patch_kernel, on the strides of the axes that still have more than one position): a quad
-// whose 4 elements lie below L is 4 consecutive source elements on a 4-element boundary; any other quad, and every quad without
-// VEC, moves element by element through the clipped index.  Every read is at a clipped position: inside the source.
-struct PadGeo {
-  SignalGeo g;
-  int sz[3];                  // the signal's own extent per axis, right-aligned (leading axes 1)
-  int L;                      // existing elements of one grid row: sz[2] * C
-};
-
-template <int KIND, bool VEC>
-__global__ void __launch_bounds__(kThreads) signal_patch_pad_kernel(const void* __restrict__ src, unsigned* __restrict__ y, PadGeo x) {
-  const SignalGeo& g = x.g;
-  const long long blk = blockIdx.x;
-  const long long d = blk / g.n_chunks;
-  const int chunk = (int)(blk % g.n_chunks);
-  const uint8_t* s8 = static_cast<const uint8_t*>(src) + d * g.ds;
-  const unsigned* s32 = static_cast<const unsigned*>(src) + d * g.ds;
+  const uint8_t* s8 = static_cast<const uint8_t*>(src) + d * x.ds;
+  const unsigned* s32 = static_cast<const unsigned*>(src) + d * x.ds;
   unsigned* yd = y + d * (long long)g.E;
   for (int it = 0; it < kQuadsPerThread; ++it) {
     const long long s0l = (long long)chunk * kChunk + ((long long)it * kThreads + threadIdx.x) * 4;
     if (s0l >= g.E) break;
     const int s0 = (int)s0l;
     const int n = g.E - s0 < 4 ? g.E - s0 : 4;
-    unsigned v[4] = {0u, 0u, 0u, 0u};
-    bool done = false;
+    int g0, g1, b2, e = 0;
     if (VEC) {                                           // R % 4 == 0: the quad lies inside one run
-      int r = s0 / g.R;
-      const int off = s0 % g.R;
-      const int p1 = r % g.ps[1]; r /= g.ps[1];
-      const int p0 = r % g.ps[0]; r /= g.ps[0];
-      const int b2 = r % g.pn[2]; r /= g.pn[2];
-      const int b1 = r % g.pn[1];
-      const int b0 = r / g.pn[1];
-      const int e = b2 * g.R + off;
-      if (e + 3 < x.L) {
-        const long long g0 = min(b0 * g.ps[0] + p0, x.sz[0] - 1), g1 = min(b1 * g.ps[1] + p1, x.sz[1] - 1);
-        const long long o = g0 * g.as[0] + g1 * g.as[1] + e;
-        if (KIND == 0) {
-          const unsigned w = *reinterpret_cast<const unsigned*>(s8 + o);
-          v[0] = unit8(w & 0xffu); v[1] = unit8((w >> 8) & 0xffu); v[2] = unit8((w >> 16) & 0xffu); v[3] = unit8(w >> 24);
-        } else {
-          const uint4 q = *reinterpret_cast<const uint4*>(s32 + o);
-          v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-        }
-        done = true;
-      }
+      decode_run<PAD>(g, s0 / g.R, g0, g1, b2);
+      e = b2 * g.R + s0 % g.R;
     }
-    if (!done) {
+    unsigned v[4] = {0u, 0u, 0u, 0u};
+    if (VEC && (!PAD || e + 3 < g.L)) {                  // 4 consecutive source elements (the last axis is dense: its offset is e)
+      const long long o = g0 * x.as[0] + g1 * x.as[1] + e;
+      if (KIND == 0) {
+        const unsigned w = *reinterpret_cast<const unsigned*>(s8 + o);
+        v[0] = unit8(w & 0xffu); v[1] = unit8((w >> 8) & 0xffu); v[2] = unit8((w >> 16) & 0xffu); v[3] = unit8(w >> 24);
+      } else {
+        const uint4 q = *reinterpret_cast<const uint4*>(s32 + o);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+      }
+    } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (k < n) {
           const int s = s0 + k, off = s % g.R;
-          int r = s / g.R;
-          const int p1 = r % g.ps[1]; r /= g.ps[1];
-          const int p0 = r % g.ps[0]; r /= g.ps[0];
-          const int b2 = r % g.pn[2]; r /= g.pn[2];
-          const int b1 = r % g.pn[1];
-          const int b0 = r / g.pn[1];
-          const long long g0 = min(b0 * g.ps[0] + p0, x.sz[0] - 1), g1 = min(b1 * g.ps[1] + p1, x.sz[1] - 1);
-          const long long g2 = min(b2 * g.ps[2] + off / g.C, x.sz[2] - 1);
-          const long long o = g0 * g.as[0] + g1 * g.as[1] + g2 * g.as[2] + (long long)(off % g.C) * g.cs;
+          decode_run<PAD>(g, s / g.R, g0, g1, b2);
+          int g2 = b2 * g.ps[2] + off / g.C;
+          if (PAD) g2 = min(g2, g.sz[2] - 1);
+          const long long o = g0 * x.as[0] + g1 * x.as[1] + g2 * x.as[2] + (long long)(off % g.C) * x.cs;
           v[k] = KIND == 0 ? unit8(s8[o]) : s32[o];
         }
       }
@@ -167,8 +90,6 @@ __global__ void __launch_bounds__(kThreads) signal_patch_pad_kernel(const void* 
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 // both entries: `size` null is rcb_signal_patch (every axis has its G_i positions)
 int patch_entry(const char* who, const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,
                 const int32_t* patch_size, const int32_t* size, int32_t channels, int64_t data_stride, const int64_t* axis_stride,
@@ -178,64 +99,46 @@ int patch_entry(const char* who, const void* src, int32_t src_kind, int64_t n_da
   RCB_REQUIRE(patch_nums && patch_size && axis_stride, RCB_ERR_ARG, "%s: null patch geometry or strides", who);
   RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "%s: %d channels (1 .. 32)", who, channels);
   RCB_REQUIRE(n_data >= 0, RCB_ERR_SHAPE, "%s: %lld signals", who, (long long)n_data);
-  PadGeo x;
-  SignalGeo& g = x.g;
-  long long pix = 1;
-  for (int i = 0; i < 3; ++i) g.pn[i] = g.ps[i] = x.sz[i] = 1, g.as[i] = 0;
-  for (int i = 0; i < nd; ++i) {
-    RCB_REQUIRE(patch_nums[i] > 0 && patch_size[i] > 0, RCB_ERR_SHAPE, "%s: axis %d has %d patches of %d pixels", who, i,
-                patch_nums[i], patch_size[i]);
-    RCB_REQUIRE(axis_stride[i] >= 0, RCB_ERR_ARG, "%s: negative stride %lld of axis %d", who, (long long)axis_stride[i], i);
-    g.pn[3 - nd + i] = patch_nums[i];
-    g.ps[3 - nd + i] = patch_size[i];
-    g.as[3 - nd + i] = axis_stride[i];
-    const long long G = (long long)patch_nums[i] * patch_size[i];
-    RCB_REQUIRE(G <= 0x7fffffffLL && pix * G <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED,
-                "%s: more than 2^31 - 1 elements per signal", who);          // (pix, G < 2^31: the product fits 64 bits)
-    RCB_REQUIRE(!size || (size[i] >= 1 && size[i] <= G), RCB_ERR_SHAPE, "%s: axis %d of the signal has %d positions (1 .. %lld)", who,
-                i, size ? size[i] : 0, G);
-    x.sz[3 - nd + i] = size ? size[i] : (int)G;
-    pix *= G;
-  }
+  SignalGeo x;
+  PatchGeo& g = x.g;
+  long long per, P;
+  if (const int err = grid_axes(who, nd, patch_nums, patch_size, size, axis_stride, g, per, P)) return err;
   RCB_REQUIRE(data_stride >= 0 && channel_stride >= 0, RCB_ERR_ARG, "%s: negative stride (signal %lld, channel %lld)", who,
               (long long)data_stride, (long long)channel_stride);
-  const long long E = pix * channels;
+  const long long E = per * P * channels;
   RCB_REQUIRE(E <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED, "%s: %lld elements per signal (up to 2^31 - 1)", who, E);
   if (n_data == 0) return RCB_OK;
   RCB_REQUIRE(src && y, RCB_ERR_ARG, "%s: null src or y", who);
-  g.C = channels;
-  g.R = g.ps[2] * channels;
-  g.E = (int)E;
-  g.n_chunks = (int)((E + kChunk - 1) / kChunk);
-  g.ds = data_stride;
-  g.cs = channel_stride;
-  x.L = x.sz[2] * channels;
+  grid_elems(g, channels, E);
+  x.ds = data_stride;
+  x.cs = channel_stride;
+  for (int i = 0; i < 3; ++i) x.as[i] = i < 3 - nd ? 0 : axis_stride[i - (3 - nd)];
   RCB_REQUIRE(n_data <= 0x7fffffffLL / g.n_chunks, RCB_ERR_UNSUPPORTED,
               "%s: %lld signals of %lld elements need more than 2^31 - 1 workgroups", who, (long long)n_data, E);
   // the 16-byte path: channel-last, dense last axis, and every run start -- base, signal, outer positions; b2 * R by R % 4 -- a
   // multiple of 4 elements (a stride only counts where its index can be non-zero: an axis of more than one position)
-  bool vec = (channels == 1 || channel_stride == 1) && (x.sz[2] == 1 || g.as[2] == channels) && g.R % 4 == 0 &&
+  bool vec = (channels == 1 || channel_stride == 1) && (g.sz[2] == 1 || x.as[2] == channels) && g.R % 4 == 0 &&
              aligned(y, 16) && aligned(src, src_kind == 0 ? 4 : 16);
   vec = vec && (n_data == 1 || data_stride % 4 == 0);
-  for (int i = 0; i < 2; ++i) vec = vec && (x.sz[i] == 1 || g.as[i] % 4 == 0);
+  for (int i = 0; i < 2; ++i) vec = vec && (g.sz[i] == 1 || x.as[i] % 4 == 0);
   const unsigned blocks = (unsigned)(n_data * g.n_chunks);
   unsigned* yo = reinterpret_cast<unsigned*>(y);
   hipStream_t st = (hipStream_t)stream;
   if (!size) {
     if (src_kind == 0) {
-      if (vec) signal_patch_kernel<0, true><<<blocks, kThreads, 0, st>>>(src, yo, g);
-      else signal_patch_kernel<0, false><<<blocks, kThreads, 0, st>>>(src, yo, g);
+      if (vec) signal_patch_kernel<0, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
+      else signal_patch_kernel<0, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
     } else {
-      if (vec) signal_patch_kernel<1, true><<<blocks, kThreads, 0, st>>>(src, yo, g);
-      else signal_patch_kernel<1, false><<<blocks, kThreads, 0, st>>>(src, yo, g);
+      if (vec) signal_patch_kernel<1, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
+      else signal_patch_kernel<1, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
     }
   } else {
     if (src_kind == 0) {
-      if (vec) signal_patch_pad_kernel<0, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
-      else signal_patch_pad_kernel<0, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
+      if (vec) signal_patch_kernel<0, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
+      else signal_patch_kernel<0, false, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
     } else {
-      if (vec) signal_patch_pad_kernel<1, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
-      else signal_patch_pad_kernel<1, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
+      if (vec) signal_patch_kernel<1, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
+      else signal_patch_kernel<1, false, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
     }
   }
   RCB_LAUNCH_CHECK();

@@ -131,6 +131,16 @@ def _xf_bf16_cached(xf, precision=1):
     return copy
 
 
+def _grid_args(layout):
+    """What the entries that take a patch grid need of a PeLayout (None: no grid, the rows are datapoints) -> nd, patch_nums and
+    patch_size as int32 arrays right-padded with zeros to 3 entries, per = patches per signal, P = pixels per patch, and the
+    grid G_i = patch_nums[i] * patch_size[i]"""
+    pn, ps = ([], []) if layout is None else (list(layout.patch_nums), list(layout.patch_size))
+    arr = C.c_int32 * max(len(pn), len(ps), 3)
+    per, P = (int(np.prod(pn)), int(np.prod(ps))) if pn else (1, 1)
+    return len(pn), arr(*pn), arr(*ps), per, P, tuple(a * b for a, b in zip(pn, ps))
+
+
 class PeLayout:
     """pe / dpe given as the upsampling net's own channel-last output on the STITCHED grids of the patched presets
     (rcb_siren_desc.pe_grid_dims): [S * n_datapoints, *(patch_nums[i] * patch_size[i]), E] instead of [G, P, E]."""
@@ -140,9 +150,8 @@ class PeLayout:
         assert 1 <= len(self.patch_nums) == len(self.patch_size) <= 3
 
     def shape(self, G, meta):
-        n_inr = G // meta.samples
-        per = int(np.prod(self.patch_nums))
-        return (meta.samples * (n_inr // per),) + tuple(a * b for a, b in zip(self.patch_nums, self.patch_size)) + (meta.pe_dim,)
+        _, _, _, per, _, grid = _grid_args(self)
+        return (meta.samples * (G // meta.samples // per),) + grid + (meta.pe_dim,)
 
 
 def _siren_desc(meta: SirenMeta, wvec, xf, pe=None, dw_bf16=None, chunks=1, pe_layout=None, xf16=None, dw_planes=None):
@@ -1164,8 +1173,8 @@ def recon_whole_shape(shape, layout=None):
     N, P, Cc = shape
     if layout is None:
         return (N, P, Cc)
-    per = int(np.prod(layout.patch_nums))
-    return (N // per,) + tuple(a * b for a, b in zip(layout.patch_nums, layout.patch_size)) + (Cc,)
+    _, _, _, per, _, grid = _grid_args(layout)
+    return (N // per,) + grid + (Cc,)
 
 
 def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, want_whole=False, out=None, size=None):
@@ -1189,12 +1198,9 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
                                or target.device != y.device):
         raise RcbError(f"recon_finish: target must be a contiguous fp32 tensor {list(y.shape)} on the device of y")
     N, P, Cc = (int(v) for v in y.shape)
-    nd = 0 if layout is None else len(layout.patch_nums)
+    nd, pn, ps, per, _, _ = _grid_args(layout)
     if nd > 3 or (layout is not None and len(layout.patch_size) != nd):
         raise RcbError(f"recon_finish: {nd} grid dimensions (a PeLayout of 1 to 3 axes, or None)")
-    pn = (C.c_int32 * 3)(*(list(layout.patch_nums) + [0] * (3 - nd) if nd else [0] * 3))
-    ps = (C.c_int32 * 3)(*(list(layout.patch_size) + [0] * (3 - nd) if nd else [0] * 3))
-    per = int(np.prod(layout.patch_nums)) if nd else 1
     n_data = N // max(per, 1)
     n_ws = int(lib.rcb_recon_workspace_bytes(max(n_data, 1), per * P * Cc)) if N and P and Cc else -1
     dev = y.device
@@ -1256,15 +1262,12 @@ def _signal_patch(what, signals, layout, out, pad):
         raise RcbError(f"{what}: signals must be a GPU tensor (the HIP path has no CPU fallback)")
     if signals.dtype not in SIGNAL_KINDS:
         raise RcbError(f"{what}: signals must be uint8 or fp32, got {signals.dtype}")
-    pn, ps = list(layout.patch_nums), list(layout.patch_size)
-    nd = len(pn)
-    if len(ps) != nd or signals.dim() != nd + 2:
+    nd, pn, ps, per, P, grid = _grid_args(layout)
+    if len(layout.patch_size) != nd or signals.dim() != nd + 2:
         raise RcbError(f"{what}: signals of {signals.dim()} axes for a layout of {nd} ([n, *grid, C] expected)")
-    grid = tuple(a * b for a, b in zip(pn, ps))
     n, Cc = int(signals.shape[0]), int(signals.shape[-1])
     if not pad and tuple(signals.shape[1:-1]) != grid:       # (pad: the library holds the extent to [1, G])
         raise RcbError(f"{what}: signals on the grid {tuple(signals.shape[1:-1])}, the layout's is {grid}")
-    per, P = int(np.prod(pn)) if nd else 1, int(np.prod(ps)) if nd else 1
     shape = (n * per, P, Cc)
     fits = 0 <= per * P * Cc <= 0x7fffffff                   # (a refused shape gets no buffer: the library says why)
     if out is None:
@@ -1275,8 +1278,8 @@ def _signal_patch(what, signals, layout, out, pad):
     st = [int(v) for v in signals.stride()]
     arr = max(nd, 1)
     size = [(C.c_int32 * arr)(*signals.shape[1:-1])] if pad else []
-    _launch("rcb_" + what, C.c_void_p(signals.data_ptr()), SIGNAL_KINDS[signals.dtype], n, nd, (C.c_int32 * arr)(*pn),
-            (C.c_int32 * arr)(*ps), *size, Cc, st[0], (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
+    _launch("rcb_" + what, C.c_void_p(signals.data_ptr()), SIGNAL_KINDS[signals.dtype], n, nd, pn, ps, *size, Cc, st[0],
+            (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
     return out
 
 

@@ -73,9 +73,7 @@ class InrGeometry:
     def _pe_layout(self):
         # the patched presets in the 16-bit modes hand the SIREN kernel the upsampling net's output on the stitched grids
         # as it is (ops.PeLayout); None: pe is cut back into [N, S, P, 16]
-        if self.precision != 0 and self.patch and self.stitched_pe:
-            return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
-        return None
+        return self.recon_layout() if self.precision != 0 and self.stitched_pe else None
 
     def _pe(self, upsample_net, lpe, stitched=False, lpe16=None, weff_cache=None, weight_side_stream=None, fwd_fused=None):
         """lpe [S, N, *lat, C] -> pe [N, S, P, 16]: hand-written phase-conv kernels in the 16-bit modes
@@ -113,14 +111,13 @@ class InrGeometry:
 
     def recon_layout(self):
         """how the rows of a reconstruction [N, P, C] make up whole signals: ops.PeLayout of the patched presets, else None"""
-        if self.patch:
-            return ops.PeLayout(self.patch_nums[:self.data_dim], self.pixel_sizes[:self.data_dim])
-        return None
+        return self.signal_layout() if self.patch else None
 
     def signal_layout(self):
-        """recon_layout, with the unpatched presets as one patch per signal (what the signal entries take)"""
+        """the grid of a whole signal, the unpatched presets as one patch per signal (what the signal entries take): the one place
+        the models build their ops.PeLayout"""
         dd = self.data_dim
-        return self.recon_layout() or ops.PeLayout([1] * dd, self.pixel_sizes[:dd])
+        return ops.PeLayout(self.patch_nums[:dd] if self.patch else [1] * dd, self.pixel_sizes[:dd])
 
     def report(self, x, y, on_device=True, size=None):
         """TestBNNmodel (the model with `predict`, `dataset` and `_report`; it lives here because both models share this mixin):
