@@ -23,9 +23,10 @@ extern "C" {
 
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
  * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23;
- * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop).  A binding compares
- * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 411
+ * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop; 412: rcb_signal_patch_fmt,
+ * rcb_recon_finish_fmt).  A binding compares rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes()
+ * with the size of each of its mirrors. */
+#define RCB_VERSION 412
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -739,6 +740,41 @@ int rcb_signal_patch_pad(const void* src, int32_t src_kind, int64_t n_data, int3
 int rcb_recon_finish_crop(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
                           const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t mode, uint8_t* u8,
                           float* whole, double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (412): 16-bit sample formats -- PCM audio (the reference's data/audio.py:50-54 forms (q / 32768 + 1) / 2 on the host) and
+ * images / video of 9 to 16 bits.  The sample formats of both ends, defined once:
+ *   kind 0 (uint8) and kind 1 (fp32; on the way out: raw) are rcb_signal_patch's and rcb_recon_finish's modes 0 and 1, unchanged.
+ *   kind 2 (u16 at `depth` b, 9 <= b <= 16): samples stored in 16-bit unsigned words, M = 2^b - 1 (exact in fp32).
+ *     in:   y = (float)q / (float)M, one IEEE fp32 division.  A stored value above M is NOT clamped: y > 1.
+ *     out:  c = NaN ? 0 : fminf(fmaxf(x, 0), 1);  q = rintf(c * (float)M), an fp32 multiply rounded half to even;
+ *           v = (float)(int)q / (float)M.  v is formed from the integer, so q = 0 gives +0.0 whatever the sign of x (not mode 0's
+ *           -0.0).
+ *   kind 3 (s16: 16-bit two's-complement PCM on the audio preset's [0, 1) normalisation; depth 0):
+ *     in:   y = ((float)q + 32768.0f) / 65536.0f, every step exact: bit for bit the reference's (q / 32768 + 1) / 2 in fp32.
+ *     out:  c as above;  u = fminf(rintf(c * 65536.0f), 65535.0f);  q = (int)u - 32768 as int16;  v = u / 65536.0f, exact.
+ *   Round trip: out(in(q)) == q for every representable q -- 0 .. M at every depth, all of int16.
+ *   sse keeps its definition, over d = t - v in fp32, with the chunks, the order of additions and the n_bad / NaN rules of
+ *   rcb_recon_finish: the distortion of the signal the decoder delivers.
+ *
+ * rcb_signal_patch_fmt is rcb_signal_patch (`size` null) or rcb_signal_patch_pad (`size`: its HOST array) for src_kind 0 .. 3;
+ * strides are in elements of the source type.  A quad of 4 consecutive 16-bit source elements is one 8-byte load under the
+ * conditions of those entries, `src` and every run start 8-byte aligned; otherwise the quad moves element by element; both give
+ * the same bits.  Kinds 0 and 1 give every bit of y the older entries give.
+ * rcb_recon_finish_fmt is rcb_recon_finish (`size` null) or rcb_recon_finish_crop (`size`) for modes 0 .. 3, mode 2 = u16 at
+ * `depth`, mode 3 = s16.  `q_out` (nullable): q in the stitched / cropped layout of `u8` -- uint8 (mode 0), uint16 (mode 2) or
+ * int16 (mode 3).  A quad of 16-bit q is one 8-byte store when q_out is 8-byte aligned (the crop form: and size[nd-1] * channels is
+ * a multiple of 4); otherwise element by element, the same bits.  Modes 0 and 1 give every output bit of the older entries, the
+ * -0.0 of mode 0 included.
+ * Refused (RCB_ERR_*), nothing launched: what the older entries refuse, a kind or mode outside 0 .. 3, a depth outside 9 .. 16 for
+ * kind / mode 2, a non-zero depth for any other, q_out with mode 1.  The older entries keep refusing kind 2 and mode 2. */
+int rcb_signal_patch_fmt(const void* src, int32_t src_kind, int32_t depth, int64_t n_data, int32_t nd, const int32_t* patch_nums,
+                         const int32_t* patch_size, const int32_t* size, int32_t channels, int64_t data_stride,
+                         const int64_t* axis_stride, int64_t channel_stride, float* y, rcb_stream_t stream);
+int rcb_recon_finish_fmt(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
+                         const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t mode, int32_t depth,
+                         void* q_out, float* whole, double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes,
+                         rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

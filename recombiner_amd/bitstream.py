@@ -18,7 +18,13 @@ Version 2 (signals of any size, drivers.compress_signals_any): after the per-lev
 signals' own extent per spatial axis; the model's grid is utils.fit_config(config, size), the signals were edge-padded to it and
 `decode_signal_any` crops back -- and the CRC-32 covers that block and the payload, so a flipped size byte is rejected.  Rate of a
 version-2 stream: bpp = payload_bits / (n_signals * prod(size)), bits per REAL sample position (the padding costs bits, it is not
-counted as signal)."""
+counted as signal).
+
+Version 3 (16-bit and other non-implied sample formats, utils.SampleFormat): the version-2 extent block -- here nd may be 0: the
+signals fill the model's grid -- is followed by  u8 kind | u8 depth  (kind 0 u8, 1 f32, 2 u16 with depth 9 .. 16, 3 s16; depth 0
+for all but u16), inside the CRC-32 like the extent.  It is written only when a format other than the preset's implied one (u8
+for cifar / kodak / video, f32 for audio / protein) is given; versions 1 and 2 are byte for byte what they were.  The decoder
+rounds to the format's lattice and can return the integers in its dtype."""
 import struct
 import zlib
 
@@ -28,6 +34,7 @@ import torch
 MAGIC = b"RCB1"
 VERSION = 1
 VERSION_EXTENT = 2
+VERSION_FORMAT = 3
 
 
 def _extent_block(extent):
@@ -37,15 +44,27 @@ def _extent_block(extent):
     return struct.pack("<B", len(size)) + struct.pack("<%dI" % len(size), *size)
 
 
-def pack_indices(levels, bits=16, extent=None):
+def _format_block(sample_format):
+    from .utils import SampleFormat
+    if not isinstance(sample_format, SampleFormat):
+        raise ValueError("sample_format %r: a utils.SampleFormat expected" % (sample_format,))
+    return struct.pack("<BB", sample_format.kind, sample_format.depth)
+
+
+def pack_indices(levels, bits=16, extent=None, sample_format=None):
     """levels: list of integer arrays [rows, n_groups] with values < 2**bits  ->  bytes.  extent None: version 1; a tuple of the
-    signals' size per spatial axis: version 2, which carries it."""
+    signals' size per spatial axis: version 2, which carries it.  sample_format (utils.SampleFormat): version 3, which carries
+    the extent (or none: nd = 0) and the format."""
     if bits != 16:
         raise ValueError("only 16 bits per group are defined (K = 65536 candidates, test_model.py:441-444)")
     if not 1 <= len(levels) <= 3:
         raise ValueError("1 to 3 levels expected")
     ext = b"" if extent is None else _extent_block(extent)
-    head = MAGIC + struct.pack("<HBB", VERSION if extent is None else VERSION_EXTENT, len(levels), bits)
+    version = VERSION if extent is None else VERSION_EXTENT
+    if sample_format is not None:
+        ext = (ext or struct.pack("<B", 0)) + _format_block(sample_format)
+        version = VERSION_FORMAT
+    head = MAGIC + struct.pack("<HBB", version, len(levels), bits)
     body = b""
     for a in levels:
         a = np.asarray(a)
@@ -59,12 +78,25 @@ def pack_indices(levels, bits=16, extent=None):
 
 
 def unpack(blob):
-    """bytes (either version) -> (list of int64 arrays [rows, n_groups], extent: the tuple a version-2 stream carries, None
-    for version 1); raises ValueError on a malformed or corrupted stream."""
+    """bytes (any version) -> (list of int64 arrays [rows, n_groups], extent: the tuple a version-2 or -3 stream carries, None
+    for version 1 and for a version-3 stream without one); raises ValueError on a malformed or corrupted stream.  The sample
+    format of a version-3 stream: unpack_header."""
+    return _unpack(blob)[:2]
+
+
+def unpack_header(blob):
+    """bytes (any version) -> dict(version, extent, sample_format): extent as `unpack` gives it, sample_format the
+    utils.SampleFormat a version-3 stream carries (None for versions 1 and 2: the preset's implied format).  Validates the whole
+    stream as `unpack` does."""
+    _, extent, fmt, version = _unpack(blob)
+    return dict(version=version, extent=extent, sample_format=fmt)
+
+
+def _unpack(blob):
     if len(blob) < 12 or blob[:4] != MAGIC:
         raise ValueError("not an RCB1 bitstream")
     version, n_levels, bits = struct.unpack_from("<HBB", blob, 4)
-    if version not in (VERSION, VERSION_EXTENT) or bits != 16 or not 1 <= n_levels <= 3:
+    if version not in (VERSION, VERSION_EXTENT, VERSION_FORMAT) or bits != 16 or not 1 <= n_levels <= 3:
         raise ValueError("unsupported bitstream header (version %d, %d levels, %d bits)" % (version, n_levels, bits))
     off = 8
     shapes = []
@@ -73,19 +105,29 @@ def unpack(blob):
             raise ValueError("truncated header")
         shapes.append(struct.unpack_from("<II", blob, off))
         off += 8
-    start, extent = off, None
-    if version == VERSION_EXTENT:
+    start, extent, fmt = off, None, None
+    if version in (VERSION_EXTENT, VERSION_FORMAT):
         if off + 1 > len(blob):
             raise ValueError("truncated header")
         nd = blob[off]
-        if not 1 <= nd <= 3:
+        if not (0 if version == VERSION_FORMAT else 1) <= nd <= 3:
             raise ValueError("unsupported bitstream header (an extent of %d axes)" % nd)
         if off + 1 + 4 * nd > len(blob):
             raise ValueError("truncated header")
-        extent = tuple(int(v) for v in struct.unpack_from("<%dI" % nd, blob, off + 1))
-        if min(extent) < 1:
-            raise ValueError("bitstream extent %r has an empty axis" % (extent,))
+        if nd:
+            extent = tuple(int(v) for v in struct.unpack_from("<%dI" % nd, blob, off + 1))
+            if min(extent) < 1:
+                raise ValueError("bitstream extent %r has an empty axis" % (extent,))
         off += 1 + 4 * nd
+    if version == VERSION_FORMAT:
+        if off + 2 > len(blob):
+            raise ValueError("truncated header")
+        from .utils import SampleFormat
+        try:
+            fmt = SampleFormat(int(blob[off]), int(blob[off + 1]))
+        except ValueError as e:
+            raise ValueError("unsupported bitstream header (%s)" % e) from None
+        off += 2
     n_bytes = sum(r * g for r, g in shapes) * 2
     if len(blob) != off + n_bytes + 4:
         raise ValueError("bitstream length %d does not match its header (%d expected)" % (len(blob), off + n_bytes + 4))
@@ -97,7 +139,7 @@ def unpack(blob):
     for r, g in shapes:
         out.append(np.frombuffer(body, dtype="<u2", count=r * g, offset=p).reshape(r, g).astype(np.int64))
         p += r * g * 2
-    return out, extent
+    return out, extent, fmt, version
 
 
 def unpack_indices(blob):
@@ -114,14 +156,22 @@ def _levels_of(model):
     return [model._l1] + ([model._l2, model._l3] if model.patch else [])
 
 
-def encode(model, extent=None):
+def encode(model, extent=None, sample_format=None):
     """bitstream of a fully compressed TestBNNmodel (every group of every level encoded).  extent: the size of the signals
-    when they were edge-padded to the model's grid (a version-2 stream, decode_signal_any); None: version 1, as ever."""
+    when they were edge-padded to the model's grid (a version-2 stream, decode_signal_any); None: version 1, as ever.
+    sample_format (utils.SampleFormat): a format other than the one the model's dataset implies makes it a version-3 stream that
+    carries it; None or the implied format changes nothing."""
+    if sample_format is not None:
+        from .utils import SampleFormat
+        if not isinstance(sample_format, SampleFormat):
+            raise ValueError("sample_format %r: a utils.SampleFormat expected" % (sample_format,))
+        if sample_format == SampleFormat.implied(model.dataset):
+            sample_format = None
     lvls = _levels_of(model)
     for lv in lvls:
         if not lv.mask_groupwise.all():
             raise ValueError("level %r has %d groups that are not encoded yet" % (lv.pre, int((~lv.mask_groupwise).sum())))
-    return pack_indices([lv.idx_groupwise for lv in lvls], extent=extent)
+    return pack_indices([lv.idx_groupwise for lv in lvls], extent=extent, sample_format=sample_format)
 
 
 def apply_indices(model, levels):
@@ -165,7 +215,41 @@ def _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, 
         return model, model.predict(x.to(device))
 
 
-def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False):
+def _stream_format(blob, dataset, sample_format, as_int):
+    """the format the decoder rounds to: the one a version-3 stream carries, else `sample_format` (a version-1 / -2 stream whose
+    caller knows it), else None -- the preset's implied format, through the code paths of versions 1 and 2.  ValueError when the
+    two disagree, or when integers are asked of a format that has none."""
+    from .utils import METRIC_ROUNDS
+    if dataset not in METRIC_ROUNDS:
+        raise ValueError(dataset)
+    try:
+        fmt = unpack_header(blob)["sample_format"]
+    except ValueError:
+        if as_int and sample_format is None and not METRIC_ROUNDS[dataset]:
+            fmt = None                                       # (the older refusal below comes first, as it always did)
+        else:
+            raise
+    if fmt is not None and sample_format is not None and fmt != sample_format:
+        raise ValueError("the bitstream carries %r, sample_format says %r" % (fmt, sample_format))
+    fmt = fmt if fmt is not None else sample_format
+    if fmt is None and as_int and not METRIC_ROUNDS[dataset]:
+        raise ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+    if fmt is not None and as_int and not fmt.is_integer:
+        raise ValueError("%r has no integer form: decode it as fp32" % (fmt,))
+    return fmt
+
+
+def _finish(y, dataset, fmt, as_int, layout, size=None):
+    from . import ops
+    from .utils import METRIC_ROUNDS
+    mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
+    q, whole, _, _ = ops.recon_finish(y.to(torch.float32).contiguous(), layout=layout, size=size, mode=mode, want_u8=as_int,
+                                      want_whole=not as_int, sample_format=fmt)
+    return q if as_int else whole
+
+
+def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False,
+           sample_format=None, as_integer=False):
     """Standalone decoder: prior checkpoint (drivers.load_checkpoint) + bitstream -> reconstruction [N, P, C].
     x: the coordinate features the encoder used ([P, F] or [N, P, F]; None: the preset's own, utils.preset_inputs(config));
     n_datapoints: INRs (patches) in the stream.
@@ -173,57 +257,53 @@ def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", se
     patched presets stitched -- clip, x 255, round half to even, as the metric rounds (rcb_recon_finish).  audio / protein
     have no 8-bit form (their metric does not round): ValueError; `decode_signal` gives their fp32 whole signals.
     A version-2 stream is decoded like a version-1 stream: this is the patch level, `config` names the (fitted) grid and the
-    result covers all of it, padding included; `decode_signal_any` crops to the size the stream carries."""
-    if as_uint8:
-        return _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8=True)
+    result covers all of it, padding included; `decode_signal_any` crops to the size the stream carries.
+    A version-3 stream likewise: the reconstruction [N, P, C] is not rounded at all; as_uint8 (alias: as_integer) gives the
+    integers of the stream's format in its dtype (sample_format: the format of a version-1 / -2 stream, as decode_signal's)."""
+    if as_uint8 or as_integer:
+        return _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, True, sample_format)
     return _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision)[1]
 
 
-def _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8):
-    # the whole GRID of `config`, for either version: `decode` is the patch-level decoder -- its caller names the (fitted) config
+def _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8, sample_format=None):
+    # the whole GRID of `config`, for any version: `decode` is the patch-level decoder -- its caller names the (fitted) config
     # and the number of patches, and knows what the grid holds
-    from . import ops
-    from .utils import METRIC_ROUNDS
-    if dataset not in METRIC_ROUNDS:
-        raise ValueError(dataset)
-    if as_uint8 and not METRIC_ROUNDS[dataset]:
-        raise ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+    fmt = _stream_format(blob, dataset, sample_format, as_uint8)
     model, y = _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision)
-    mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
-    u8, whole, _, _ = ops.recon_finish(y.to(torch.float32).contiguous(), layout=model.recon_layout(), mode=mode,
-                                       want_u8=as_uint8, want_whole=not as_uint8)
-    return u8 if as_uint8 else whole
+    return _finish(y, dataset, fmt, as_uint8, model.recon_layout())
 
 
-def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False):
+def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False,
+                  sample_format=None, as_integer=False):
     """`decode`, finished on the device to WHOLE signals [n_signals, *grid, C] (n_signals = n_datapoints / patches per signal;
     [N, P, C] for the unpatched presets): fp32 -- on the 8-bit lattice k / 255 for the image / video presets, the raw values
     for audio / protein -- or, with as_uint8 (image / video only), the uint8 k themselves.
-    A version-2 stream is refused (ValueError): its signals are smaller than the grid, decode_signal_any crops them back."""
-    from .utils import METRIC_ROUNDS
-    if dataset not in METRIC_ROUNDS:
-        raise ValueError(dataset)
-    if as_uint8 and not METRIC_ROUNDS[dataset]:
-        raise ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+    A stream that carries an extent is refused (ValueError): its signals are smaller than the grid, decode_signal_any crops
+    them back.
+    sample_format (utils.SampleFormat): the format of a version-1 stream whose caller knows it (a version-3 stream carries its
+    own; ValueError when they disagree): fp32 on the format's lattice, or with as_uint8 (alias: as_integer) the integers in
+    the format's dtype -- uint16 for u16, int16 for s16."""
+    as_uint8 = as_uint8 or as_integer
+    fmt = _stream_format(blob, dataset, sample_format, as_uint8)
     extent = unpack(blob)[1]
     if extent is not None:
         raise ValueError("a version-2 bitstream: its signals of size %r were edge-padded to the model's grid -- decode them with "
                          "decode_signal_any, which crops back (this decoder would return the padding)" % (extent,))
-    return _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8)
+    return _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8, fmt)
 
 
-def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42, precision=0, as_uint8=False):
-    """The decoder of drivers.compress_signals_any: prior checkpoint + version-2 bitstream -> the signals [n, *size, C] at their
-    own size.  `config` is the PRESET: the stream's extent fits it (utils.fit_config), the number of signals follows from the
+def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42, precision=0, as_uint8=False, as_integer=False):
+    """The decoder of drivers.compress_signals_any: prior checkpoint + version-2 or -3 bitstream -> the signals [n, *size, C] at
+    their own size.  `config` is the PRESET: the stream's extent fits it (utils.fit_config), the number of signals follows from the
     level-1 rows (ValueError when they are no whole number of signals), the patches are decoded with the preset's own coordinate
     features, and rcb_recon_finish_crop stitches, rounds (image / video presets) and crops on the device.  fp32 -- on the 8-bit
-    lattice k / 255 for the image / video presets, raw for audio / protein -- or, with as_uint8 (image / video only), the k."""
+    lattice k / 255 for the image / video presets, raw for audio / protein -- or, with as_uint8 (image / video only), the k.
+    A version-3 stream carries its sample format (unpack_header): the lattice is the format's (rcb_recon_finish_fmt), and
+    as_integer (the clearer name of as_uint8) returns the integers in the format's dtype -- uint16 for u16, int16 for s16."""
     from . import ops
-    from .utils import METRIC_ROUNDS, fit_config, preset_grid
-    if dataset not in METRIC_ROUNDS:
-        raise ValueError(dataset)
-    if as_uint8 and not METRIC_ROUNDS[dataset]:
-        raise ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+    from .utils import fit_config, preset_grid
+    as_uint8 = as_uint8 or as_integer
+    fmt = _stream_format(blob, dataset, None, as_uint8)
     levels, extent = unpack(blob)
     if extent is None:
         raise ValueError("a version-1 bitstream carries no signal size: decode it with decode_signal")
@@ -236,7 +316,4 @@ def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42,
     if rows == 0 or rows % per:
         raise ValueError("bitstream holds %d rows, signals of size %r take %d patches each" % (rows, extent, per))
     _, y = _decode_patches(fitted, dataset, checkpoint, blob, None, rows, device, seed, precision)
-    mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
-    u8, whole, _, _ = ops.recon_finish(y.to(torch.float32).contiguous(), layout=ops.PeLayout(pn, ps), size=extent, mode=mode,
-                                       want_u8=as_uint8, want_whole=not as_uint8)
-    return u8 if as_uint8 else whole
+    return _finish(y, dataset, fmt, as_uint8, ops.PeLayout(pn, ps), size=extent)

@@ -8,6 +8,9 @@
 //   mode 0:  q = rintf(fminf(fmaxf(x, 0), 1) * 255.0f)      (fp32 multiply, round half to even: np.round)
 //            v = q / 255.0f                                  (IEEE fp32 division: numpy's)
 //   mode 1:  v = x
+//   mode 2:  (rcb_recon_finish_fmt; u16 at depth b, M = 2^b - 1)   q = rintf(c * (float)M),  v = (float)(int)q / (float)M
+//   mode 3:  (rcb_recon_finish_fmt; s16)   u = fminf(rintf(c * 65536.0f), 65535.0f),  q = (int)u - 32768,  v = u / 65536.0f
+//            c = NaN ? 0 : fminf(fmaxf(x, 0), 1); the integer output is 16-bit words, a quad of them one 8-byte store
 //   sse   =  sum of (double)d * (double)d,  d = t - v in fp32 (the difference numpy forms elementwise)
 //
 // Reduction (no floating-point atomics, no workgroup hand-off): a datapoint's E = rows * P * C elements are contiguous in y; they
@@ -39,8 +42,11 @@ namespace {
 struct ReconGeo {
   PatchGeo g;
   int mode;
-  int vec_out;            // crop: L % 4 == 0 and aligned outputs: a quad inside the extent is one 16-byte / 4-byte store
+  int vec_out;            // crop: L % 4 == 0 and aligned outputs: a quad inside the extent is one 16-byte / 4- or 8-byte store
   long long Ec;           // crop: elements of one cropped datapoint
+  // W16 (modes 2 and 3, rcb_recon_finish_fmt): u = fminf(rintf(c * scale), cap), the stored word (int)u - bias
+  float scale, cap;       // u16 at depth b: M = 2^b - 1 and M (the clamp never binds); s16: 65536 and 65535
+  int bias;               // u16: 0; s16: 32768
 };
 
 // offset of source element s (a multiple of R plus `off` < R) of a datapoint inside its stitched signal
@@ -80,6 +86,18 @@ __device__ __forceinline__ Elem finish(float x, int mode) {
   return e;
 }
 
+// modes 2 and 3: v is formed from the INTEGER (q = 0 gives +0.0 whatever the sign of x); for s16 (float)(int)u = u and the division
+// by 65536 is exact, for u16 it is the one IEEE fp32 division by M.  e.q: the 16-bit word to store.
+__device__ __forceinline__ Elem finish16(float x, const ReconGeo& r) {
+  Elem e;
+  e.bad = !(fabsf(x) < __builtin_inff());
+  const float c = (x != x) ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f);
+  const int u = (int)fminf(rintf(c * r.scale), r.cap);
+  e.q = (unsigned)(u - r.bias) & 0xffffu;
+  e.v = (float)u / r.scale;
+  return e;
+}
+
 // The workgroup's sum of (acc, bad), valid in thread 0 (-> true there): the 64 lanes of a wave by the xor butterfly, the waves in
 // wave order -- the same additions whatever the launch.
 __device__ __forceinline__ bool block_sum(double& acc, int& bad) {
@@ -103,9 +121,25 @@ __device__ __forceinline__ bool block_sum(double& acc, int& bad) {
   return true;
 }
 
+// the integer output at element offset o: bytes, or (W16) 16-bit words, a quad of which is one 8-byte store
+template <bool W16>
+__device__ __forceinline__ void store_quad(uint8_t* out, long long o, const Elem (&e)[4]) {
+  if (W16)
+    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(out) + o) = make_uint2(e[0].q | (e[1].q << 16), e[2].q | (e[3].q << 16));
+  else
+    *reinterpret_cast<unsigned*>(out + o) = e[0].q | (e[1].q << 8) | (e[2].q << 16) | (e[3].q << 24);
+}
+
+template <bool W16>
+__device__ __forceinline__ void store_one(uint8_t* out, long long o, unsigned q) {
+  if (W16) reinterpret_cast<uint16_t*>(out)[o] = (uint16_t)q;
+  else out[o] = (uint8_t)q;
+}
+
 // CROP: rcb_recon_finish_crop -- the same loads, the same additions in the same order; only what an element outside the extent
-// contributes (+0.0, no count) and where the outputs go differ
-template <bool VEC, bool CROP>
+// contributes (+0.0, no count) and where the outputs go differ.  W16 (rcb_recon_finish_fmt, modes 2 and 3): `u8` addresses 16-bit
+// words and an element is finish16's; W16 false is the code of the 8-bit and raw modes
+template <bool VEC, bool CROP, bool W16>
 __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict__ y, const float* __restrict__ target,
                                                          uint8_t* __restrict__ u8, float* __restrict__ whole,
                                                          double* __restrict__ part_sse, int* __restrict__ part_bad, ReconGeo x) {
@@ -162,7 +196,7 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
     Elem e[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      e[k] = finish(xs[k], x.mode);
+      e[k] = W16 ? finish16(xs[k], x) : finish(xs[k], x.mode);
       if (k < n) {
         const bool in = !CROP || co[k] >= 0;
         const bool b = e[k].bad || !(fabsf(t[k]) < __builtin_inff());
@@ -178,13 +212,13 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
         if (VEC && x.vec_out && co[0] >= 0 && co[3] >= 0) {
           const long long o = cbase + co[0];
           if (whole) *reinterpret_cast<float4*>(whole + o) = make_float4(e[0].v, e[1].v, e[2].v, e[3].v);
-          if (u8) *reinterpret_cast<unsigned*>(u8 + o) = e[0].q | (e[1].q << 8) | (e[2].q << 16) | (e[3].q << 24);
+          if (u8) store_quad<W16>(u8, o, e);
         } else {
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             if (k < n && co[k] >= 0) {
               if (whole) whole[cbase + co[k]] = e[k].v;
-              if (u8) u8[cbase + co[k]] = (uint8_t)e[k].q;
+              if (u8) store_one<W16>(u8, cbase + co[k], e[k].q);
             }
           }
         }
@@ -193,14 +227,14 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
       if (VEC) {
         const long long o = base + whole_offset(g, s0 / g.R, s0 % g.R);
         if (whole) *reinterpret_cast<float4*>(whole + o) = make_float4(e[0].v, e[1].v, e[2].v, e[3].v);
-        if (u8) *reinterpret_cast<unsigned*>(u8 + o) = e[0].q | (e[1].q << 8) | (e[2].q << 16) | (e[3].q << 24);
+        if (u8) store_quad<W16>(u8, o, e);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           if (k < n) {
             const long long o = base + whole_offset(g, (s0 + k) / g.R, (s0 + k) % g.R);
             if (whole) whole[o] = e[k].v;
-            if (u8) u8[o] = (uint8_t)e[k].q;
+            if (u8) store_one<W16>(u8, o, e[k].q);
           }
         }
       }
@@ -237,18 +271,37 @@ extern "C" int64_t rcb_recon_workspace_bytes(int64_t n_data, int64_t elems_per_d
   return n_data * n_chunks * (int64_t)(sizeof(double) + sizeof(int));
 }
 
-// both entries: `size` null is rcb_recon_finish (every datapoint fills its grid)
-static int finish_entry(const char* who, const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels,
-                        int32_t nd, const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t mode,
-                        uint8_t* u8, float* whole, double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes,
-                        rcb_stream_t stream) {
+template <bool W16>
+static void launch_finish(bool vec, bool crop, unsigned blocks, hipStream_t st, const float* y, const float* target, uint8_t* u8,
+                          float* whole, double* part_sse, int* part_bad, const ReconGeo& x) {
+  if (!crop) {
+    if (vec) recon_kernel<true, false, W16><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+    else recon_kernel<false, false, W16><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+  } else {
+    if (vec) recon_kernel<true, true, W16><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+    else recon_kernel<false, true, W16><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+  }
+}
+
+// all entries: `size` null is the uncropped form (every datapoint fills its grid); `fmt`: rcb_recon_finish_fmt, which alone takes
+// modes 2 (u16 at `depth`) and 3 (s16), `u8` then addressing 16-bit words
+static int finish_entry(const char* who, bool fmt, const float* y, const float* target, int64_t n_rows, int32_t n_pix,
+                        int32_t channels, int32_t nd, const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size,
+                        int32_t mode, int32_t depth, uint8_t* u8, float* whole, double* sse, int32_t* n_bad, void* workspace,
+                        int64_t workspace_bytes, rcb_stream_t stream) {
   RCB_REQUIRE(y && workspace, RCB_ERR_ARG, "%s: null y or workspace", who);
-  RCB_REQUIRE(mode == 0 || mode == 1, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw)", who, mode);
+  if (fmt) {
+    RCB_REQUIRE(mode >= 0 && mode <= 3, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw, 2 = u16, 3 = s16)", who, mode);
+    RCB_REQUIRE(mode == 2 ? (depth >= 9 && depth <= 16) : depth == 0, RCB_ERR_ARG,
+                "%s: depth %d for mode %d (9 .. 16 for u16, 0 for the others)", who, depth, mode);
+  } else {
+    RCB_REQUIRE(mode == 0 || mode == 1, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw)", who, mode);
+  }
   RCB_REQUIRE(nd >= (size ? 1 : 0) && nd <= 3, RCB_ERR_UNSUPPORTED, "%s: %d grid dimensions (%d .. 3)", who, nd, size ? 1 : 0);
   RCB_REQUIRE(nd == 0 || (patch_nums && patch_size), RCB_ERR_ARG, "%s: null patch geometry", who);
   RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "%s: %d channels (1 .. 32)", who, channels);
   RCB_REQUIRE(n_rows > 0 && n_pix > 0, RCB_ERR_SHAPE, "%s: %lld rows of %d pixels", who, (long long)n_rows, n_pix);
-  RCB_REQUIRE(!(u8 && mode == 1), RCB_ERR_ARG, "%s: the raw mode has no 8-bit output", who);
+  RCB_REQUIRE(!(u8 && mode == 1), RCB_ERR_ARG, "%s: the raw mode has no %s output", who, fmt ? "integer" : "8-bit");
   RCB_REQUIRE(!(sse && !target), RCB_ERR_ARG, "%s: sse needs a target", who);
   ReconGeo x;
   PatchGeo& g = x.g;
@@ -270,24 +323,28 @@ static int finish_entry(const char* who, const float* y, const float* target, in
               "%s: workspace of %lld bytes (8-byte aligned), %lld needed", who, (long long)workspace_bytes, (long long)need);
   grid_elems(g, channels, E);
   x.mode = mode;
+  const bool w16 = mode >= 2;
+  x.scale = mode == 2 ? (float)((1 << depth) - 1) : 65536.0f;
+  x.cap = mode == 2 ? x.scale : 65535.0f;
+  x.bias = mode == 3 ? 32768 : 0;
+  const uintptr_t q_align = w16 ? 8 : 4;                     // a quad of the integer output
   const long long blocks = n_data * g.n_chunks;
   double* part_sse = static_cast<double*>(workspace);
   int* part_bad = reinterpret_cast<int*>(part_sse + blocks);
   hipStream_t st = (hipStream_t)stream;
+  bool vec;
   if (!size) {
     x.vec_out = 0, x.Ec = 0;
-    const bool vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16)) && (!whole || aligned(whole, 16)) &&
-                     (!u8 || aligned(u8, 4));
-    if (vec) recon_kernel<true, false><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
-    else recon_kernel<false, false><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+    vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16)) && (!whole || aligned(whole, 16)) &&
+          (!u8 || aligned(u8, q_align));
   } else {
     // the 16-byte loads need only the inputs aligned; the stores go by quad (vec_out), the cropped rows seldom being multiples of 4
     x.Ec = (long long)g.sz[0] * g.sz[1] * g.L;               // (L <= E: the products fit)
-    const bool vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16));
-    x.vec_out = g.L % 4 == 0 && (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, 4));
-    if (vec) recon_kernel<true, true><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
-    else recon_kernel<false, true><<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+    vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16));
+    x.vec_out = g.L % 4 == 0 && (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, q_align));
   }
+  if (w16) launch_finish<true>(vec, size != nullptr, (unsigned)blocks, st, y, target, u8, whole, part_sse, part_bad, x);
+  else launch_finish<false>(vec, size != nullptr, (unsigned)blocks, st, y, target, u8, whole, part_sse, part_bad, x);
   RCB_LAUNCH_CHECK();
   if (sse || n_bad) {
     recon_reduce_kernel<<<(unsigned)n_data, kThreads, 0, st>>>(part_sse, part_bad, g.n_chunks, sse, n_bad);
@@ -299,8 +356,8 @@ static int finish_entry(const char* who, const float* y, const float* target, in
 extern "C" int rcb_recon_finish(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
                                 const int32_t* patch_nums, const int32_t* patch_size, int32_t mode, uint8_t* u8, float* whole,
                                 double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes, rcb_stream_t stream) {
-  return finish_entry("recon_finish", y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, nullptr, mode, u8, whole, sse,
-                      n_bad, workspace, workspace_bytes, stream);
+  return finish_entry("recon_finish", false, y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, nullptr, mode, 0, u8,
+                      whole, sse, n_bad, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rcb_recon_finish_crop(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels,
@@ -308,6 +365,14 @@ extern "C" int rcb_recon_finish_crop(const float* y, const float* target, int64_
                                      int32_t mode, uint8_t* u8, float* whole, double* sse, int32_t* n_bad, void* workspace,
                                      int64_t workspace_bytes, rcb_stream_t stream) {
   RCB_REQUIRE(size, RCB_ERR_ARG, "recon_finish_crop: null size");
-  return finish_entry("recon_finish_crop", y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, size, mode, u8, whole,
-                      sse, n_bad, workspace, workspace_bytes, stream);
+  return finish_entry("recon_finish_crop", false, y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, size, mode, 0, u8,
+                      whole, sse, n_bad, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rcb_recon_finish_fmt(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
+                                    const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t mode,
+                                    int32_t depth, void* q_out, float* whole, double* sse, int32_t* n_bad, void* workspace,
+                                    int64_t workspace_bytes, rcb_stream_t stream) {
+  return finish_entry("recon_finish_fmt", true, y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, size, mode, depth,
+                      static_cast<uint8_t*>(q_out), whole, sse, n_bad, workspace, workspace_bytes, stream);
 }

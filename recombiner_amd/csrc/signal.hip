@@ -9,12 +9,15 @@
 //
 //   src_kind 0 (uint8):  y = (float)q / 255.0f         (one IEEE fp32 division: ToTensor's and numpy's)
 //   src_kind 1 (fp32):   the 32 bits of the source, unchanged (moved as integers: NaN payloads, -0, denormals keep their bits)
+//   src_kind 2 (u16 at depth b, rcb_signal_patch_fmt only):  y = (float)q / (float)(2^b - 1), one IEEE fp32 division; a stored
+//                        value above 2^b - 1 is not clamped (y > 1)
+//   src_kind 3 (s16, rcb_signal_patch_fmt only):  y = ((float)q + 32768.0f) / 65536.0f, every step exact
 //
 // Memory: a quad is 4 consecutive DESTINATION elements of one signal.  When the source is channel-last and dense along the last axis
 // (channel_stride = 1, axis_stride[last] = channels), the run R = patch_size[last] * channels is a multiple of 4 and every run starts
 // on a 4-element boundary of an aligned base, a quad is 4 consecutive source elements too and never straddles a run: one 4-byte
-// (uint8) or 16-byte (fp32) load and one 16-byte store.  Otherwise the same quads are moved element by element.  The host entry
-// decides; both paths give the same bits.  Pure data movement: bytes = src + y.  No LDS, no atomics.
+// (uint8), 8-byte (u16, s16) or 16-byte (fp32) load and one 16-byte store.  Otherwise the same quads are moved element by element.
+// The host entry decides; both paths give the same bits.  Pure data movement: bytes = src + y.  No LDS, no atomics.
 //
 // rcb_signal_patch_pad (template parameter PAD) is the same cut of a signal that holds only size[i] <= G_i positions per axis:
 // grid position g_i reads source position min(g_i, size[i] - 1), the edge sample replicated on the far side of every axis.  Of a
@@ -33,9 +36,17 @@ namespace {
 struct SignalGeo {
   PatchGeo g;
   long long ds, as[3], cs;    // source strides in elements: signal, axes (right-aligned, leading 0), channel
+  float m;                    // KIND 2: 2^depth - 1
 };
 
 __device__ __forceinline__ unsigned unit8(unsigned q) { return __float_as_uint((float)q / 255.0f); }
+
+// a 16-bit word of the source -> the bits of y: KIND 2 unsigned over m, KIND 3 two's complement on [0, 1)
+template <int KIND>
+__device__ __forceinline__ unsigned unit16(unsigned w, float m) {
+  if (KIND == 2) return __float_as_uint((float)w / m);
+  return __float_as_uint(((float)(int)(short)w + 32768.0f) / 65536.0f);
+}
 
 // PAD false never reads the extent (g.sz, g.L)
 template <int KIND, bool VEC, bool PAD>
@@ -46,6 +57,7 @@ __global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __re
   const int chunk = (int)(blk % g.n_chunks);
   const uint8_t* s8 = static_cast<const uint8_t*>(src) + d * x.ds;
   const unsigned* s32 = static_cast<const unsigned*>(src) + d * x.ds;
+  const uint16_t* s16 = static_cast<const uint16_t*>(src) + d * x.ds;
   unsigned* yd = y + d * (long long)g.E;
   for (int it = 0; it < kQuadsPerThread; ++it) {
     const long long s0l = (long long)chunk * kChunk + ((long long)it * kThreads + threadIdx.x) * 4;
@@ -63,9 +75,13 @@ __global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __re
       if (KIND == 0) {
         const unsigned w = *reinterpret_cast<const unsigned*>(s8 + o);
         v[0] = unit8(w & 0xffu); v[1] = unit8((w >> 8) & 0xffu); v[2] = unit8((w >> 16) & 0xffu); v[3] = unit8(w >> 24);
-      } else {
+      } else if (KIND == 1) {
         const uint4 q = *reinterpret_cast<const uint4*>(s32 + o);
         v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+      } else {
+        const uint2 q = *reinterpret_cast<const uint2*>(s16 + o);
+        v[0] = unit16<KIND>(q.x & 0xffffu, x.m); v[1] = unit16<KIND>(q.x >> 16, x.m);
+        v[2] = unit16<KIND>(q.y & 0xffffu, x.m); v[3] = unit16<KIND>(q.y >> 16, x.m);
       }
     } else {
 #pragma unroll
@@ -76,7 +92,7 @@ __global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __re
           int g2 = b2 * g.ps[2] + off / g.C;
           if (PAD) g2 = min(g2, g.sz[2] - 1);
           const long long o = g0 * x.as[0] + g1 * x.as[1] + g2 * x.as[2] + (long long)(off % g.C) * x.cs;
-          v[k] = KIND == 0 ? unit8(s8[o]) : s32[o];
+          v[k] = KIND == 0 ? unit8(s8[o]) : KIND == 1 ? s32[o] : unit16<KIND>(s16[o], x.m);
         }
       }
     }
@@ -90,11 +106,30 @@ __global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __re
   }
 }
 
-// both entries: `size` null is rcb_signal_patch (every axis has its G_i positions)
-int patch_entry(const char* who, const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,
-                const int32_t* patch_size, const int32_t* size, int32_t channels, int64_t data_stride, const int64_t* axis_stride,
-                int64_t channel_stride, float* y, rcb_stream_t stream) {
-  RCB_REQUIRE(src_kind == 0 || src_kind == 1, RCB_ERR_ARG, "%s: source kind %d (0 = uint8, 1 = fp32)", who, src_kind);
+template <int KIND>
+void launch_patch(bool vec, bool pad, unsigned blocks, hipStream_t st, const void* src, unsigned* yo, const SignalGeo& x) {
+  if (!pad) {
+    if (vec) signal_patch_kernel<KIND, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
+    else signal_patch_kernel<KIND, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
+  } else {
+    if (vec) signal_patch_kernel<KIND, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
+    else signal_patch_kernel<KIND, false, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
+  }
+}
+
+// all entries: `size` null is the uncropped form (every axis has its G_i positions); `fmt`: rcb_signal_patch_fmt, which alone takes
+// the 16-bit kinds and a depth
+int patch_entry(const char* who, bool fmt, const void* src, int32_t src_kind, int32_t depth, int64_t n_data, int32_t nd,
+                const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t channels, int64_t data_stride,
+                const int64_t* axis_stride, int64_t channel_stride, float* y, rcb_stream_t stream) {
+  if (fmt) {
+    RCB_REQUIRE(src_kind >= 0 && src_kind <= 3, RCB_ERR_ARG, "%s: source kind %d (0 = uint8, 1 = fp32, 2 = u16, 3 = s16)", who,
+                src_kind);
+    RCB_REQUIRE(src_kind == 2 ? (depth >= 9 && depth <= 16) : depth == 0, RCB_ERR_ARG,
+                "%s: depth %d for source kind %d (9 .. 16 for u16, 0 for the others)", who, depth, src_kind);
+  } else {
+    RCB_REQUIRE(src_kind == 0 || src_kind == 1, RCB_ERR_ARG, "%s: source kind %d (0 = uint8, 1 = fp32)", who, src_kind);
+  }
   RCB_REQUIRE(nd >= 1 && nd <= 3, RCB_ERR_UNSUPPORTED, "%s: %d grid dimensions (1 .. 3)", who, nd);
   RCB_REQUIRE(patch_nums && patch_size && axis_stride, RCB_ERR_ARG, "%s: null patch geometry or strides", who);
   RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "%s: %d channels (1 .. 32)", who, channels);
@@ -112,34 +147,25 @@ int patch_entry(const char* who, const void* src, int32_t src_kind, int64_t n_da
   grid_elems(g, channels, E);
   x.ds = data_stride;
   x.cs = channel_stride;
+  x.m = src_kind == 2 ? (float)((1 << depth) - 1) : 0.0f;
   for (int i = 0; i < 3; ++i) x.as[i] = i < 3 - nd ? 0 : axis_stride[i - (3 - nd)];
   RCB_REQUIRE(n_data <= 0x7fffffffLL / g.n_chunks, RCB_ERR_UNSUPPORTED,
               "%s: %lld signals of %lld elements need more than 2^31 - 1 workgroups", who, (long long)n_data, E);
-  // the 16-byte path: channel-last, dense last axis, and every run start -- base, signal, outer positions; b2 * R by R % 4 -- a
-  // multiple of 4 elements (a stride only counts where its index can be non-zero: an axis of more than one position)
+  // the 16-byte path (of y; the source quad is 4, 8 or 16 bytes): channel-last, dense last axis, and every run start -- base,
+  // signal, outer positions; b2 * R by R % 4 -- a multiple of 4 elements (a stride only counts where its index can be non-zero: an
+  // axis of more than one position)
   bool vec = (channels == 1 || channel_stride == 1) && (g.sz[2] == 1 || x.as[2] == channels) && g.R % 4 == 0 &&
-             aligned(y, 16) && aligned(src, src_kind == 0 ? 4 : 16);
+             aligned(y, 16) && aligned(src, src_kind == 0 ? 4 : src_kind == 1 ? 16 : 8);
   vec = vec && (n_data == 1 || data_stride % 4 == 0);
   for (int i = 0; i < 2; ++i) vec = vec && (g.sz[i] == 1 || x.as[i] % 4 == 0);
   const unsigned blocks = (unsigned)(n_data * g.n_chunks);
   unsigned* yo = reinterpret_cast<unsigned*>(y);
   hipStream_t st = (hipStream_t)stream;
-  if (!size) {
-    if (src_kind == 0) {
-      if (vec) signal_patch_kernel<0, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
-      else signal_patch_kernel<0, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
-    } else {
-      if (vec) signal_patch_kernel<1, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
-      else signal_patch_kernel<1, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
-    }
-  } else {
-    if (src_kind == 0) {
-      if (vec) signal_patch_kernel<0, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
-      else signal_patch_kernel<0, false, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
-    } else {
-      if (vec) signal_patch_kernel<1, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
-      else signal_patch_kernel<1, false, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
-    }
+  switch (src_kind) {
+    case 0: launch_patch<0>(vec, size != nullptr, blocks, st, src, yo, x); break;
+    case 1: launch_patch<1>(vec, size != nullptr, blocks, st, src, yo, x); break;
+    case 2: launch_patch<2>(vec, size != nullptr, blocks, st, src, yo, x); break;
+    default: launch_patch<3>(vec, size != nullptr, blocks, st, src, yo, x); break;
   }
   RCB_LAUNCH_CHECK();
   return RCB_OK;
@@ -150,14 +176,22 @@ int patch_entry(const char* who, const void* src, int32_t src_kind, int64_t n_da
 extern "C" int rcb_signal_patch(const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,
                                 const int32_t* patch_size, int32_t channels, int64_t data_stride, const int64_t* axis_stride,
                                 int64_t channel_stride, float* y, rcb_stream_t stream) {
-  return patch_entry("signal_patch", src, src_kind, n_data, nd, patch_nums, patch_size, nullptr, channels, data_stride, axis_stride,
-                     channel_stride, y, stream);
+  return patch_entry("signal_patch", false, src, src_kind, 0, n_data, nd, patch_nums, patch_size, nullptr, channels, data_stride,
+                     axis_stride, channel_stride, y, stream);
 }
 
 extern "C" int rcb_signal_patch_pad(const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,
                                     const int32_t* patch_size, const int32_t* size, int32_t channels, int64_t data_stride,
                                     const int64_t* axis_stride, int64_t channel_stride, float* y, rcb_stream_t stream) {
   RCB_REQUIRE(size, RCB_ERR_ARG, "signal_patch_pad: null size");
-  return patch_entry("signal_patch_pad", src, src_kind, n_data, nd, patch_nums, patch_size, size, channels, data_stride, axis_stride,
-                     channel_stride, y, stream);
+  return patch_entry("signal_patch_pad", false, src, src_kind, 0, n_data, nd, patch_nums, patch_size, size, channels, data_stride,
+                     axis_stride, channel_stride, y, stream);
+}
+
+extern "C" int rcb_signal_patch_fmt(const void* src, int32_t src_kind, int32_t depth, int64_t n_data, int32_t nd,
+                                    const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t channels,
+                                    int64_t data_stride, const int64_t* axis_stride, int64_t channel_stride, float* y,
+                                    rcb_stream_t stream) {
+  return patch_entry("signal_patch_fmt", true, src, src_kind, depth, n_data, nd, patch_nums, patch_size, size, channels, data_stride,
+                     axis_stride, channel_stride, y, stream);
 }

@@ -242,9 +242,11 @@ def build_test_model(config, dataset, checkpoint, n_datapoints, device="cuda", s
 
 
 def compress(config, dataset, checkpoint, x, y, device="cuda", seed=42, n_epochs=30000, lr=2e-4, precision=0,
-             verbose=0, finetune_epochs=None, bitstream_path=None):
+             verbose=0, finetune_epochs=None, bitstream_path=None, sample_format=None):
     """main_compression.py:47-178 on an in-memory checkpoint (list from load_checkpoint / build_checkpoint).
-    Returns (distortion, model); with `bitstream_path` the packed A* indices are written there (bitstream.py)."""
+    Returns (distortion, model); with `bitstream_path` the packed A* indices are written there (bitstream.py).
+    sample_format (utils.SampleFormat): only written into the stream (version 3 when it is not the preset's implied format); the
+    distortion returned here is the reference's figure on the patch targets."""
     tuning.enable_tuned_gemms()
     g1, _, g2, _, g3, _, _, _ = checkpoint
     n_groups = g1[5]
@@ -264,26 +266,40 @@ def compress(config, dataset, checkpoint, x, y, device="cuda", seed=42, n_epochs
     if bitstream_path is not None:
         from . import bitstream
         with open(bitstream_path, "wb") as f:
-            f.write(bitstream.encode(model))
+            f.write(bitstream.encode(model, sample_format=sample_format))
     return distortion, model
 
 
-def compress_signals(config, dataset, checkpoint, signals, x=None, channels_first=False, origin=None, landscape=True, **kw):
+def _signal_format(what, signals, sample_format):
+    # a 16-bit tensor does not say how deep its samples are (nor, for int16, whether they are PCM or reinterpreted u16)
+    if sample_format is None and signals.dtype in (torch.uint16, torch.int16):
+        raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.u16(depth) or .s16()): the depth is not in the "
+                         "dtype" % (what, signals.dtype))
+    if sample_format is not None and not sample_format.accepts(signals.dtype):
+        raise ValueError("%s: sample_format %r reads %s signals, got %s" % (what, sample_format, sample_format.dtype, signals.dtype))
+
+
+def compress_signals(config, dataset, checkpoint, signals, x=None, channels_first=False, origin=None, landscape=True,
+                     sample_format=None, **kw):
     """`compress` on whole signals in memory -- uint8 (q / 255, as ToTensor and `video / 255`) or fp32, [n, *spatial, C] or
     [n, C, *spatial] with channels_first -- instead of patch targets: the preset's window of each signal (utils.signal_view,
     which also documents origin / landscape) is cut into y [N, P, C] on the device (rcb_signal_patch), where the reference's
     loaders slice on the host (data/image.py:30-46, data/video.py:54-73, data/audio.py:125-140).  x None: the preset's own
-    coordinate features (utils.preset_inputs) shared by all rows.  Every other argument, and the result, is `compress`'s."""
+    coordinate features (utils.preset_inputs) shared by all rows.  Every other argument, and the result, is `compress`'s.
+    sample_format (utils.SampleFormat): how the samples are stored; required for uint16 / int16 signals (ValueError without it),
+    and written into the stream as `compress` documents."""
     from . import utils
+    _signal_format("compress_signals", signals, sample_format)
     device = kw.get("device", "cuda")
     view = utils.signal_view(config, signals.to(device), channels_first=channels_first, origin=origin, landscape=landscape)
-    y = ops.signal_patch(view, utils.signal_layout(config))
+    y = ops.signal_patch(view, utils.signal_layout(config), sample_format=sample_format)
     if x is None:
         x = utils.preset_inputs(config, device)[None].expand(y.shape[0], -1, -1)
-    return compress(config, dataset, checkpoint, x, y, **kw)
+    return compress(config, dataset, checkpoint, x, y, sample_format=sample_format, **kw)
 
 
-def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_first=False, bitstream_path=None, **kw):
+def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_first=False, bitstream_path=None,
+                         sample_format=None, **kw):
     """`compress_signals` for signals of ANY size that the preset can be fitted to: `signals` is [n, *size, C] (or [n, C, *size]
     with channels_first), uint8 or fp32, one size per call.  The config is fitted (utils.fit_config: patched presets get the
     next whole patch grid that level 2 divides; unpatched presets keep theirs and take signals up to it), the signals'
@@ -294,8 +310,13 @@ def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_
     The bitstream (bitstream_path) is version 2 and carries `size`; bitstream.decode_signal_any decodes and crops it.
     Rate: bpp = bitstream.payload_bits(blob) / (n * prod(size)), bits per real sample position.
     There is no landscape swap and no origin: the signals are coded in the orientation they are passed in -- a portrait photograph
-    on a landscape-trained prior is the caller's to transpose.  Every other argument is `compress`'s."""
+    on a landscape-trained prior is the caller's to transpose.  Every other argument is `compress`'s.
+    sample_format (utils.SampleFormat; required for uint16 / int16 signals, ValueError without it): how the samples are stored.
+    `distortion` is then formed on the format's lattice -- the figure of the signal decode_signal_any delivers.  For s16 audio
+    that is the distortion of the delivered PCM, NOT the reference's figure, which scores the unrounded reconstruction
+    (utils.metric, round=False).  A format other than the preset's implied one makes the stream version 3, which carries it."""
     from . import bitstream, utils
+    _signal_format("compress_signals_any", signals, sample_format)
     device = kw.get("device", "cuda")
     dd = config["data_dim"]
     if signals.dim() != dd + 2:
@@ -307,14 +328,14 @@ def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_
         raise ValueError("compress_signals_any: %d channels, the preset has %d" % (view.shape[-1], config["output_dim"]))
     size = tuple(int(v) for v in view.shape[1:-1])
     fitted = utils.fit_config(config, size)
-    y = ops.signal_patch_pad(view, utils.signal_layout(fitted))
+    y = ops.signal_patch_pad(view, utils.signal_layout(fitted), sample_format=sample_format)
     if x is None:
         x = utils.preset_inputs(fitted, device)[None].expand(y.shape[0], -1, -1)
     _, model = compress(fitted, dataset, checkpoint, x, y, **kw)
-    distortion = model.report(x, y, size=size)
+    distortion = model.report(x, y, size=size, sample_format=sample_format)
     if bitstream_path is not None:
         with open(bitstream_path, "wb") as f:
-            f.write(bitstream.encode(model, extent=size))
+            f.write(bitstream.encode(model, extent=size, sample_format=sample_format))
     return distortion, model, fitted
 
 

@@ -1164,7 +1164,7 @@ def tile_fold(tiles, n, H, W, Ty, Tx, off):
 # ---------------------------------------------------------------------------------------------------
 # N4: the decoder's last step and the distortion figure (rcb_recon_finish)
 # ---------------------------------------------------------------------------------------------------
-RECON_8BIT, RECON_RAW = 0, 1
+RECON_8BIT, RECON_RAW, RECON_U16, RECON_S16 = 0, 1, 2, 3
 
 
 def recon_whole_shape(shape, layout=None):
@@ -1177,7 +1177,8 @@ def recon_whole_shape(shape, layout=None):
     return (N // per,) + grid + (Cc,)
 
 
-def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, want_whole=False, out=None, size=None):
+def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, want_whole=False, out=None, size=None,
+                 sample_format=None, want_int=False):
     """The last step of a reconstruction y [N, P, C] (fp32; the rows are datapoints, or with `layout` = PeLayout(patch_nums,
     patch_size) the patches of stitched signals) and its score against `target` (same layout), in one pass (rcb_recon_finish):
     mode RECON_8BIT rounds to the 8-bit lattice as the reference's metric does (clip, x 255, round half to even, / 255),
@@ -1190,8 +1191,17 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
     size (needs a layout; patch_nums of ones for an unpatched preset): only the leading size[i] <= G_i positions per axis of
     every signal are real, the rest what signal_patch_pad replicated (rcb_recon_finish_crop): u8 / whole are [n_data, *size, C],
     and an element outside that extent adds +0.0 to sse and is never counted in n_bad.  The additions and their order are
-    those without a size, and with size = G so is every output bit."""
+    those without a size, and with size = G so is every output bit.
+    sample_format (utils.SampleFormat; None: everything above, through the same entries as ever): the format's lattice instead of
+    `mode`, which it overrides (rcb_recon_finish_fmt) -- u8 and f32 are RECON_8BIT and RECON_RAW bit for bit, u16(b) rounds to
+    k / (2^b - 1) (RECON_U16), s16 to k / 65536 (RECON_S16), and want_u8 (alias: want_int) then asks for the integer output in the
+    format's dtype: uint8, uint16 or int16 in the first slot of the result (and of `out`); f32 has none."""
     lib = _lib.load()
+    want_u8 = want_u8 or want_int
+    depth, qdt = 0, torch.uint8
+    if sample_format is not None:
+        mode, depth = sample_format.kind, sample_format.depth
+        qdt = sample_format.dtype if sample_format.is_integer else torch.uint8
     if y.dim() != 3 or y.dtype != f32 or not y.is_cuda or not y.is_contiguous():
         raise RcbError("recon_finish: y must be a contiguous fp32 GPU tensor [N, P, C]")
     if target is not None and (tuple(target.shape) != tuple(y.shape) or target.dtype != f32 or not target.is_contiguous()
@@ -1215,18 +1225,23 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
         crop = [(C.c_int32 * 3)(*(size + [0] * (3 - nd)))]
     u8, whole, sse, n_bad = out if out is not None else (None,) * 4
     if want_u8 and u8 is None:
-        u8 = torch.empty(shape, device=dev, dtype=torch.uint8)
+        u8 = torch.empty(shape, device=dev, dtype=qdt)
     if want_whole and whole is None:
         whole = torch.empty(shape, device=dev, dtype=f32)
     if target is not None and sse is None:
         sse = torch.empty(n_data, device=dev, dtype=f64)
     if n_bad is None:
         n_bad = torch.empty(n_data, device=dev, dtype=i32)
-    for t_, want, dt in ((u8, shape, torch.uint8), (whole, shape, f32), (sse, (n_data,), f64), (n_bad, (n_data,), i32)):
+    for t_, want, dt in ((u8, shape, qdt), (whole, shape, f32), (sse, (n_data,), f64), (n_bad, (n_data,), i32)):
         if t_ is not None and (tuple(t_.shape) != tuple(want) or t_.dtype != dt or t_.device != dev or not t_.is_contiguous()):
             raise RcbError(f"recon_finish: output of shape {tuple(t_.shape)} {t_.dtype}, expected contiguous {tuple(want)} {dt} "
                            "on the device of y")
     ws = torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8)       # (a refused shape: the library says why)
+    if sample_format is not None:
+        _launch("rcb_recon_finish_fmt", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps, crop[0] if crop else None,
+                int(mode), depth, ptr(u8, qdt, True), ptr(whole, f32, True), ptr(sse, f64, True), ptr(n_bad, i32), ptr(ws),
+                max(n_ws, 8))
+        return u8, whole, sse, n_bad
     _launch("rcb_recon_finish_crop" if crop else "rcb_recon_finish", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps,
             *crop, int(mode), ptr(u8, torch.uint8, True), ptr(whole, f32, True), ptr(sse, f64, True), ptr(n_bad, i32), ptr(ws),
             max(n_ws, 8))
@@ -1239,28 +1254,36 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
 SIGNAL_KINDS = {torch.uint8: 0, f32: 1}
 
 
-def signal_patch(signals, layout, out=None):
+def signal_patch(signals, layout, out=None, sample_format=None):
     """Whole signals -> the targets y [N, P, C] (fp32) of the INRs, in the row order recon_finish reads (rcb_signal_patch):
     `signals` is a GPU tensor viewed as [n, *G, C], G_i = patch_nums[i] * patch_size[i] of `layout` = PeLayout(patch_nums,
     patch_size) (all ones for an unpatched preset), uint8 (y = q / 255 as one IEEE fp32 division) or fp32 (the bits are kept),
     with ANY strides and storage offset -- channel-first storage, transposed axes, a window of a larger signal, an expanded
     channel: the strides go to the kernel as they are and nothing is copied.  recon_finish(y, layout=layout) stitches y back.
-    out: optional preallocated contiguous fp32 [N, P, C].  No host sync."""
-    return _signal_patch("signal_patch", signals, layout, out, pad=False)
+    out: optional preallocated contiguous fp32 [N, P, C].  No host sync.
+    sample_format (utils.SampleFormat; None: the dtype decides between uint8 and fp32, through the same entry as ever): how the
+    samples are stored (rcb_signal_patch_fmt) -- u8 / f32 as above bit for bit, u16(b): y = q / (2^b - 1) from a uint16 tensor (or
+    int16, its bits reinterpreted; a value above 2^b - 1 is not clamped), s16: y = (q + 32768) / 65536 from an int16 tensor.  A
+    tensor of another dtype than the format's is an RcbError."""
+    return _signal_patch("signal_patch", signals, layout, out, pad=False, fmt=sample_format)
 
 
-def signal_patch_pad(signals, layout, out=None):
+def signal_patch_pad(signals, layout, out=None, sample_format=None):
     """`signal_patch` for signals SMALLER than the layout's grid G: `signals` is [n, *size, C] with 1 <= size[i] <= G_i (read from
     its shape; any strides, uint8 or fp32) and grid position g_i takes the sample at min(g_i, size[i] - 1) -- the edge samples
     replicated on the far side of every axis (rcb_signal_patch_pad).  With size = G the result is signal_patch's bit for bit.
-    recon_finish(y, layout=layout, size=size) gives the signals back.  out: optional contiguous fp32 [N, P, C].  No host sync."""
-    return _signal_patch("signal_patch_pad", signals, layout, out, pad=True)
+    recon_finish(y, layout=layout, size=size) gives the signals back.  out: optional contiguous fp32 [N, P, C].  No host sync.
+    sample_format: as signal_patch's."""
+    return _signal_patch("signal_patch_pad", signals, layout, out, pad=True, fmt=sample_format)
 
 
-def _signal_patch(what, signals, layout, out, pad):
+def _signal_patch(what, signals, layout, out, pad, fmt=None):
     if not isinstance(signals, torch.Tensor) or not signals.is_cuda:
         raise RcbError(f"{what}: signals must be a GPU tensor (the HIP path has no CPU fallback)")
-    if signals.dtype not in SIGNAL_KINDS:
+    if fmt is not None:
+        if not fmt.accepts(signals.dtype):
+            raise RcbError(f"{what}: {fmt!r} reads {fmt.dtype} signals, got {signals.dtype}")
+    elif signals.dtype not in SIGNAL_KINDS:
         raise RcbError(f"{what}: signals must be uint8 or fp32, got {signals.dtype}")
     nd, pn, ps, per, P, grid = _grid_args(layout)
     if len(layout.patch_size) != nd or signals.dim() != nd + 2:
@@ -1278,6 +1301,10 @@ def _signal_patch(what, signals, layout, out, pad):
     st = [int(v) for v in signals.stride()]
     arr = max(nd, 1)
     size = [(C.c_int32 * arr)(*signals.shape[1:-1])] if pad else []
+    if fmt is not None:
+        _launch("rcb_signal_patch_fmt", C.c_void_p(signals.data_ptr()), fmt.kind, fmt.depth, n, nd, pn, ps, size[0] if pad else None,
+                Cc, st[0], (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
+        return out
     _launch("rcb_" + what, C.c_void_p(signals.data_ptr()), SIGNAL_KINDS[signals.dtype], n, nd, pn, ps, *size, Cc, st[0],
             (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
     return out

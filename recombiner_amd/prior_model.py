@@ -119,38 +119,42 @@ class InrGeometry:
         dd = self.data_dim
         return ops.PeLayout(self.patch_nums[:dd] if self.patch else [1] * dd, self.pixel_sizes[:dd])
 
-    def report(self, x, y, on_device=True, size=None):
+    def report(self, x, y, on_device=True, size=None, sample_format=None):
         """TestBNNmodel (the model with `predict`, `dataset` and `_report`; it lives here because both models share this mixin):
         the distortion figure of `_report` -- an array per datapoint (cifar, protein) or one float -- without the host copy of the
         reconstruction: rounding and squared error run in rcb_recon_finish and only the per-datapoint fp64 sums come back
         (utils.metric_device).  Agrees with `_report` to the rounding of its float32 evaluation; on_device=False is `_report`.
         size: the signals' own extent inside this model's grid (y = patch_signals(signals, size)): the figure counts the real
-        samples only, not the edge padding (rcb_recon_finish_crop); on the device only."""
+        samples only, not the edge padding (rcb_recon_finish_crop); on the device only.
+        sample_format (utils.SampleFormat): the lattice the reconstruction is rounded to instead of the dataset's own choice
+        (utils.metric_device); on the device only."""
         if not on_device:
-            if size is not None:
-                raise ValueError("report: the figure over a cropped extent is formed on the device only")
+            if size is not None or sample_format is not None:
+                raise ValueError("report: the figure over a cropped extent or on a sample format's lattice is formed on the "
+                                 "device only")
             return self._report(x, y)
         with torch.no_grad():
             y_pred = self.predict(x.to(self.loc.device))
         if size is not None:
-            return metric_device(y, y_pred, self.dataset, self.signal_layout(), size=size)
-        return metric_device(y, y_pred, self.dataset, self.recon_layout())
+            return metric_device(y, y_pred, self.dataset, self.signal_layout(), size=size, sample_format=sample_format)
+        return metric_device(y, y_pred, self.dataset, self.recon_layout(), sample_format=sample_format)
 
-    def patch_signals(self, signals, size=None):
+    def patch_signals(self, signals, size=None, sample_format=None):
         """whole signals [n, *grid, C] on the GPU (uint8 or fp32, any strides: utils.signal_view) -> the targets y [N, P, C] of
         this model's INRs, cut on the device in the row order of recon_layout (rcb_signal_patch); the inverse of the stitching
         in ops.recon_finish.  The unpatched presets are one patch per signal.
         size: the signals are [n, *size, C] with size[i] <= grid[i] and are edge-padded to the grid on the way
-        (rcb_signal_patch_pad)."""
+        (rcb_signal_patch_pad).
+        sample_format (utils.SampleFormat): how the samples are stored -- needed for 16-bit signals (ops.signal_patch)."""
         if size is not None:
             if tuple(int(v) for v in size) != tuple(signals.shape[1:-1]):
                 raise ValueError("patch_signals: signals of extent %r, size %r" % (tuple(signals.shape[1:-1]), tuple(size)))
-            return ops.signal_patch_pad(signals, self.signal_layout())
-        return ops.signal_patch(signals, self.signal_layout())
+            return ops.signal_patch_pad(signals, self.signal_layout(), sample_format=sample_format)
+        return ops.signal_patch(signals, self.signal_layout(), sample_format=sample_format)
 
-    def report_signals(self, x, signals, size=None):
+    def report_signals(self, x, signals, size=None, sample_format=None):
         """`report` against whole signals instead of patch targets"""
-        return self.report(x, self.patch_signals(signals, size), size=size)
+        return self.report(x, self.patch_signals(signals, size, sample_format), size=size, sample_format=sample_format)
 
 
 class PriorBNNmodel(nn.Module, InrGeometry):

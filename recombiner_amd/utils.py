@@ -186,6 +186,73 @@ def preset_inputs(config, device=None):
 # ---------------------------------------------------------------------------------------------
 # whole signals in memory -> what rcb_signal_patch reads (data/image.py:17-46, data/video.py:40-73, data/audio.py:112-140)
 # ---------------------------------------------------------------------------------------------
+class SampleFormat:
+    """How the samples of a whole signal are stored (include/rcb.h, N4 412): a kind and, for u16, a depth.
+      u8()     uint8, y = q / 255                                   -- what the image / video presets imply
+      f32()    fp32, the bits unchanged; raw on the way out          -- what the audio / protein presets imply
+      u16(b)   b-bit samples (9 <= b <= 16) in 16-bit unsigned words, y = q / (2^b - 1); a stored value above 2^b - 1 is not
+               clamped.  torch.uint16, or an int16 tensor whose bits are reinterpreted
+      s16()    16-bit PCM, y = (q + 32768) / 65536: the audio preset's (q / 32768 + 1) / 2 of data/audio.py:50-54, bit for bit
+    `kind` is the library's src_kind and, on the way out, its mode (ops.RECON_8BIT / RECON_RAW / RECON_U16 / RECON_S16)."""
+    U8, F32, U16, S16 = 0, 1, 2, 3
+    _NAMES = {0: "u8", 1: "f32", 2: "u16", 3: "s16"}
+
+    def __init__(self, kind, depth=0):
+        if isinstance(kind, bool) or isinstance(depth, bool) or not isinstance(kind, (int, np.integer)) \
+                or not isinstance(depth, (int, np.integer)):
+            raise ValueError("SampleFormat: kind %r and depth %r must be integers" % (kind, depth))
+        if kind not in self._NAMES:
+            raise ValueError("SampleFormat: kind %r (0 = u8, 1 = f32, 2 = u16, 3 = s16)" % (kind,))
+        if kind == self.U16 and not 9 <= depth <= 16:
+            raise ValueError("SampleFormat: a u16 depth of %r (9 .. 16; 8-bit samples are u8)" % (depth,))
+        if kind != self.U16 and depth != 0:
+            raise ValueError("SampleFormat: %s has no depth (got %r)" % (self._NAMES[kind], depth))
+        self.kind, self.depth = int(kind), int(depth)
+
+    @classmethod
+    def u8(cls):
+        return cls(cls.U8)
+
+    @classmethod
+    def f32(cls):
+        return cls(cls.F32)
+
+    @classmethod
+    def u16(cls, depth):
+        return cls(cls.U16, depth)
+
+    @classmethod
+    def s16(cls):
+        return cls(cls.S16)
+
+    @classmethod
+    def implied(cls, dataset):
+        """the format a preset implies, which a bitstream need not carry: u8 where the metric rounds, else f32"""
+        return cls.u8() if METRIC_ROUNDS[dataset] else cls.f32()
+
+    @property
+    def dtype(self):
+        """the torch dtype of the samples (and of the integer output of ops.recon_finish)"""
+        return (torch.uint8, torch.float32, torch.uint16, torch.int16)[self.kind]
+
+    @property
+    def is_integer(self):
+        return self.kind != self.F32
+
+    def accepts(self, dtype):
+        """whether a source tensor of `dtype` can be read in this format: its own dtype; u16 also takes int16 (the bits)"""
+        return dtype == self.dtype or (self.kind == self.U16 and dtype == torch.int16)
+
+    def __eq__(self, other):
+        return isinstance(other, SampleFormat) and (self.kind, self.depth) == (other.kind, other.depth)
+
+    def __hash__(self):
+        return hash((self.kind, self.depth))
+
+    def __repr__(self):
+        return "SampleFormat.%s(%s)" % (self._NAMES[self.kind], self.depth if self.kind == self.U16 else "")
+
+
 def preset_grid(config):
     """(patch_nums, patch_size) of a preset's whole signal: its patch grid, or one patch for the unpatched presets"""
     dd = config["data_dim"]
@@ -317,7 +384,7 @@ def metric_from_sse(sse, n_elems, dataset):
     return (-10.0 * np.log10(sse.sum() / (n * sse.size))).item()
 
 
-def metric_device(y_true, y_pred, dataset, layout=None, size=None):
+def metric_device(y_true, y_pred, dataset, layout=None, size=None, sample_format=None):
     """`metric(y_true, y_pred, dataset)` for GPU tensors [N, P, C] without copying them to the host: one pass of
     rcb_recon_finish (rounding to 8 bits where the dataset's metric does), then only the per-datapoint sums -- and the counts
     of non-finite elements, which make a datapoint's figure NaN as numpy's would be -- are read back.  layout: ops.PeLayout
@@ -325,13 +392,15 @@ def metric_device(y_true, y_pred, dataset, layout=None, size=None):
     depend on it.
     size (needs a layout; patch_nums of ones for an unpatched preset): only the leading size[i] positions per axis of every
     signal are real, the rest edge padding (ops.signal_patch_pad) -- the figure is over the real samples alone
-    (rcb_recon_finish_crop), the mean over prod(size) * C elements per signal."""
+    (rcb_recon_finish_crop), the mean over prod(size) * C elements per signal.
+    sample_format (SampleFormat): the lattice the reconstruction is rounded to -- it overrides the dataset's choice, so the figure is
+    the distortion of the signal a decoder delivers in that format (rcb_recon_finish_fmt); the formula stays the dataset's."""
     from . import ops
     if dataset not in METRIC_ROUNDS:
         raise ValueError(dataset)
     mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
     y_pred = y_pred.detach().to(torch.float32).contiguous()
     y_true = y_true.detach().to(device=y_pred.device, dtype=torch.float32).contiguous()
-    _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode, size=size)
+    _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode, size=size, sample_format=sample_format)
     n_elems = y_pred.numel() // sse.numel() if size is None else int(np.prod([int(v) for v in size])) * y_pred.shape[-1]
     return metric_from_sse(sse.cpu().numpy(), n_elems, dataset)
