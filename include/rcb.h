@@ -6,7 +6,8 @@
  * point below replaces a sequence of torch ops on the reference's hot path and cites it
  * (file:line relative to the reference root).  Conventions:
  *   - plain device pointers + explicit sizes; the caller (PyTorch, or any HIP host) allocates
- *     every buffer including outputs; nothing is allocated, freed or synchronised inside;
+ *     every buffer including outputs; nothing is allocated, freed or synchronised inside (but for the one table upload of the
+ *     two per-signal entries of 413, which says so);
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it;
  *   - return value: 0 = ok, < 0 = argument/shape error (RCB_ERR_*), > 0 = hipError_t;
  *   - no global mutable state besides the thread-local last-error string; re-entrant per stream;
@@ -24,9 +25,9 @@ extern "C" {
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
  * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23;
  * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop; 412: rcb_signal_patch_fmt,
- * rcb_recon_finish_fmt).  A binding compares rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes()
- * with the size of each of its mirrors. */
-#define RCB_VERSION 412
+ * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged).  A binding compares
+ * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
+#define RCB_VERSION 413
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -775,6 +776,50 @@ int rcb_recon_finish_fmt(const float* y, const float* target, int64_t n_rows, in
                          const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t mode, int32_t depth,
                          void* q_out, float* whole, double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes,
                          rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (413): batches of signals of mixed sizes and memory layouts -- the per-signal ("ragged") forms of rcb_signal_patch_fmt and
+ * rcb_recon_finish_fmt.  All signals of a call share the patch grid G_i = patch_nums[i] * patch_size[i], the channels and the
+ * sample format; each keeps its own extent and its own place and strides in one source / output buffer:
+ *   sizes  HOST int32 [n_data][3]: the first nd entries of row d are signal d's extent along the grid axes, 1 <= size <= G_i
+ *          (the others are ignored).
+ *   spans  HOST int64 [n_data][4]: {offset, axis_stride[0 .. 2]} (the first nd strides count), in elements of the source / output
+ *          type, all >= 0.  Element (g, c) of signal d lies at base + offset + sum g_i * axis_stride[i] + c * channel_stride; a
+ *          transposed signal is only a matter of strides.
+ *   table  device buffer of rcb_ragged_table_bytes(n_data) bytes (-1 for n_data < 0), 8-byte aligned, the caller's to allocate:
+ *          the entry validates the host tables, writes their device copy (with a per-signal flag for the memory path) there on
+ *          `stream` and synchronises the stream ONCE for that upload; on return the host arrays are the caller's again.  Because
+ *          of that synchronisation these two entries are NOT for graph capture: they are the I/O ends, not part of the step.
+ *
+ * rcb_signal_patch_ragged: per signal exactly rcb_signal_patch_fmt with that signal's `size` and strides -- grid position g_i reads
+ * min(g_i, size_i - 1), the four sample kinds of 412, rows d * prod(patch_nums) + patch of y as ever.  A signal whose strides and
+ * alignment meet the vector-path conditions of rcb_signal_patch_pad takes the 4- / 8- / 16-byte loads, any other moves element by
+ * element, in the same call, with the same bits.  `src_elems`: elements of the source buffer from `src`; a signal whose farthest
+ * element offset + sum (size_i - 1) * axis_stride[i] + (channels - 1) * channel_stride is >= src_elems is refused, so every read
+ * lies inside [src, src + src_elems).
+ *
+ * rcb_recon_finish_ragged: per signal exactly rcb_recon_finish_fmt with that signal's `size`; the channel stride is 1.  q_out /
+ * whole (each nullable) are ONE buffer of out_elems elements each, signal d's values at its span.  Every signal must be dense with
+ * its axes in some order: sorted by stride the innermost stride is `channels` and each next one the previous times that axis's
+ * size (axes of size 1 are ignored); the ranges [offset, offset + channels * prod(size)) must be pairwise disjoint and lie inside
+ * [0, out_elems) -- so every write lies inside the buffers and no two signals meet.  Elements of the buffers outside the spans are
+ * not touched.  sse[d] / n_bad[d] keep the chunks and the order of additions over the PADDED datapoint (workspace:
+ * rcb_recon_workspace_bytes(n_data, padded elements)); an element outside a signal's extent adds +0.0 and is never counted, and
+ * sse[d] is bitwise rcb_recon_finish_fmt(size = sizes[d])'s for that signal alone -- in any batch, in any batch order, from run to
+ * run.
+ * Refused (RCB_ERR_*), nothing launched and nothing uploaded: what the _fmt entries refuse, null sizes / spans / table, table_bytes
+ * below rcb_ragged_table_bytes(n_data) or a misaligned table, a size outside [1, G_i], a negative offset or stride, a reach past
+ * src_elems, output strides that are not dense, overlapping spans, a span past out_elems.  n_data = 0 (n_rows = 0) succeeds and
+ * launches nothing. */
+int64_t rcb_ragged_table_bytes(int64_t n_data);
+int rcb_signal_patch_ragged(const void* src, int64_t src_elems, int32_t src_kind, int32_t depth, int64_t n_data, int32_t nd,
+                            const int32_t* patch_nums, const int32_t* patch_size, const int32_t* sizes, const int64_t* spans,
+                            int32_t channels, int64_t channel_stride, float* y, void* table, int64_t table_bytes,
+                            rcb_stream_t stream);
+int rcb_recon_finish_ragged(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
+                            const int32_t* patch_nums, const int32_t* patch_size, const int32_t* sizes, const int64_t* spans,
+                            int64_t out_elems, int32_t mode, int32_t depth, void* q_out, float* whole, double* sse, int32_t* n_bad,
+                            void* workspace, int64_t workspace_bytes, void* table, int64_t table_bytes, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

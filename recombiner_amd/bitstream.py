@@ -24,7 +24,15 @@ Version 3 (16-bit and other non-implied sample formats, utils.SampleFormat): the
 signals fill the model's grid -- is followed by  u8 kind | u8 depth  (kind 0 u8, 1 f32, 2 u16 with depth 9 .. 16, 3 s16; depth 0
 for all but u16), inside the CRC-32 like the extent.  It is written only when a format other than the preset's implied one (u8
 for cifar / kodak / video, f32 for audio / protein) is given; versions 1 and 2 are byte for byte what they were.  The decoder
-rounds to the format's lattice and can return the integers in its dtype."""
+rounds to the format's lattice and can return the integers in its dtype.
+
+Version 4 (signals of mixed sizes and orientations sharing one model, drivers.compress_signal_list): after the per-level shapes comes
+u8 nd | u32 n_signals | n_signals x (nd x u32 size, u8 flags)  -- each signal's own extent along the MODEL's axes and its flags: bit
+0 = "deliver with axes 0 and 1 exchanged" (2-D only: the signal was portrait and coded landscape), every other bit reserved and
+rejected -- then  u8 kind | u8 depth, always present (the implied format is written out).  All sizes fit one grid
+(utils.fit_config), and the level-1 rows are n_signals x the patches of that grid.  The CRC-32 of a version-4 stream covers the WHOLE
+stream from the magic on, so a relabelled version number is caught as well; versions 1 to 3 stay byte for byte what they are.
+`decode_signal_list` is its decoder.  Rate: bpp = payload_bits / sum of prod(size) over the signals."""
 import struct
 import zlib
 
@@ -35,6 +43,7 @@ MAGIC = b"RCB1"
 VERSION = 1
 VERSION_EXTENT = 2
 VERSION_FORMAT = 3
+VERSION_LIST = 4
 
 
 def _extent_block(extent):
@@ -51,14 +60,46 @@ def _format_block(sample_format):
     return struct.pack("<BB", sample_format.kind, sample_format.depth)
 
 
-def pack_indices(levels, bits=16, extent=None, sample_format=None):
+def _list_block(extents, swaps, sample_format):
+    extents = [[int(v) for v in e] for e in extents]
+    swaps = [False] * len(extents) if swaps is None else [bool(v) for v in swaps]
+    nd = len(extents[0]) if extents else 0
+    if not 1 <= len(extents) <= 0xFFFFFFFF or not 1 <= nd <= 3 or len(swaps) != len(extents):
+        raise ValueError("extents: a list of 1 to 2^32 - 1 sizes of 1 to 3 axes expected, and one swap flag for each")
+    out = struct.pack("<BI", nd, len(extents))
+    for size, sw in zip(extents, swaps):
+        if len(size) != nd or any(not 1 <= v <= 0xFFFFFFFF for v in size):
+            raise ValueError("extent %r: %d sizes in [1, 2^32) expected" % (tuple(size), nd))
+        if sw and nd != 2:
+            raise ValueError("only 2-D signals can be delivered with their axes exchanged")
+        out += struct.pack("<%dIB" % nd, *size, 1 if sw else 0)
+    return out + _format_block(sample_format)
+
+
+def pack_indices(levels, bits=16, extent=None, sample_format=None, extents=None, swaps=None):
     """levels: list of integer arrays [rows, n_groups] with values < 2**bits  ->  bytes.  extent None: version 1; a tuple of the
     signals' size per spatial axis: version 2, which carries it.  sample_format (utils.SampleFormat): version 3, which carries
-    the extent (or none: nd = 0) and the format."""
+    the extent (or none: nd = 0) and the format.  extents (a list of sizes, one per signal; swaps: a flag for each, default
+    none; sample_format required): version 4."""
     if bits != 16:
         raise ValueError("only 16 bits per group are defined (K = 65536 candidates, test_model.py:441-444)")
     if not 1 <= len(levels) <= 3:
         raise ValueError("1 to 3 levels expected")
+    if extents is not None:
+        if extent is not None:
+            raise ValueError("extent and extents exclude each other")
+        head = MAGIC + struct.pack("<HBB", VERSION_LIST, len(levels), bits)
+        body = b""
+        for a in levels:
+            a = np.asarray(a)
+            if a.ndim != 2:
+                raise ValueError("index arrays must be [rows, n_groups]")
+            if a.size and (a.min() < 0 or a.max() >= (1 << bits) or np.any(a != np.floor(a))):
+                raise ValueError("index out of range for %d bits" % bits)
+            head += struct.pack("<II", a.shape[0], a.shape[1])
+            body += np.ascontiguousarray(a.astype("<u2")).tobytes()
+        whole = head + _list_block(extents, swaps, sample_format) + body
+        return whole + struct.pack("<I", zlib.crc32(whole) & 0xFFFFFFFF)
     ext = b"" if extent is None else _extent_block(extent)
     version = VERSION if extent is None else VERSION_EXTENT
     if sample_format is not None:
@@ -85,18 +126,22 @@ def unpack(blob):
 
 
 def unpack_header(blob):
-    """bytes (any version) -> dict(version, extent, sample_format): extent as `unpack` gives it, sample_format the
-    utils.SampleFormat a version-3 stream carries (None for versions 1 and 2: the preset's implied format).  Validates the whole
-    stream as `unpack` does."""
-    _, extent, fmt, version = _unpack(blob)
-    return dict(version=version, extent=extent, sample_format=fmt)
+    """bytes (any version) -> dict(version, extent, sample_format, extents, swaps): extent as `unpack` gives it, sample_format the
+    utils.SampleFormat a version-3 or -4 stream carries (None for versions 1 and 2: the preset's implied format); a version-4
+    stream adds extents / swaps, its per-signal sizes (tuples, along the model's axes) and exchange flags.
+    Validates the whole stream as `unpack` does."""
+    _, extent, fmt, version, extents, swaps = _unpack(blob)
+    hdr = dict(version=version, extent=extent, sample_format=fmt)
+    if version == VERSION_LIST:
+        hdr.update(extents=extents, swaps=swaps)
+    return hdr
 
 
 def _unpack(blob):
     if len(blob) < 12 or blob[:4] != MAGIC:
         raise ValueError("not an RCB1 bitstream")
     version, n_levels, bits = struct.unpack_from("<HBB", blob, 4)
-    if version not in (VERSION, VERSION_EXTENT, VERSION_FORMAT) or bits != 16 or not 1 <= n_levels <= 3:
+    if version not in (VERSION, VERSION_EXTENT, VERSION_FORMAT, VERSION_LIST) or bits != 16 or not 1 <= n_levels <= 3:
         raise ValueError("unsupported bitstream header (version %d, %d levels, %d bits)" % (version, n_levels, bits))
     off = 8
     shapes = []
@@ -105,7 +150,28 @@ def _unpack(blob):
             raise ValueError("truncated header")
         shapes.append(struct.unpack_from("<II", blob, off))
         off += 8
-    start, extent, fmt = off, None, None
+    start, extent, fmt, extents, swaps = off, None, None, None, None
+    if version == VERSION_LIST:
+        if off + 5 > len(blob):
+            raise ValueError("truncated header")
+        nd, n_sig = struct.unpack_from("<BI", blob, off)
+        if not 1 <= nd <= 3 or n_sig < 1:
+            raise ValueError("unsupported bitstream header (%d signals of %d axes)" % (n_sig, nd))
+        off += 5
+        if off + n_sig * (4 * nd + 1) > len(blob):
+            raise ValueError("truncated header")
+        extents, swaps = [], []
+        for _ in range(n_sig):
+            size = tuple(int(v) for v in struct.unpack_from("<%dI" % nd, blob, off))
+            flags = blob[off + 4 * nd]
+            if min(size) < 1:
+                raise ValueError("bitstream extent %r has an empty axis" % (size,))
+            if flags & ~1 or (flags and nd != 2):
+                raise ValueError("unsupported bitstream header (signal flags 0x%02x for %d axes)" % (flags, nd))
+            extents.append(size)
+            swaps.append(bool(flags & 1))
+            off += 4 * nd + 1
+        start = 0                                            # the checksum covers the whole stream
     if version in (VERSION_EXTENT, VERSION_FORMAT):
         if off + 1 > len(blob):
             raise ValueError("truncated header")
@@ -119,7 +185,7 @@ def _unpack(blob):
             if min(extent) < 1:
                 raise ValueError("bitstream extent %r has an empty axis" % (extent,))
         off += 1 + 4 * nd
-    if version == VERSION_FORMAT:
+    if version in (VERSION_FORMAT, VERSION_LIST):
         if off + 2 > len(blob):
             raise ValueError("truncated header")
         from .utils import SampleFormat
@@ -139,7 +205,7 @@ def _unpack(blob):
     for r, g in shapes:
         out.append(np.frombuffer(body, dtype="<u2", count=r * g, offset=p).reshape(r, g).astype(np.int64))
         p += r * g * 2
-    return out, extent, fmt, version
+    return out, extent, fmt, version, extents, swaps
 
 
 def unpack_indices(blob):
@@ -156,11 +222,22 @@ def _levels_of(model):
     return [model._l1] + ([model._l2, model._l3] if model.patch else [])
 
 
-def encode(model, extent=None, sample_format=None):
+def encode(model, extent=None, sample_format=None, extents=None, swaps=None):
     """bitstream of a fully compressed TestBNNmodel (every group of every level encoded).  extent: the size of the signals
     when they were edge-padded to the model's grid (a version-2 stream, decode_signal_any); None: version 1, as ever.
     sample_format (utils.SampleFormat): a format other than the one the model's dataset implies makes it a version-3 stream that
-    carries it; None or the implied format changes nothing."""
+    carries it; None or the implied format changes nothing.
+    extents (one size per signal, along the model's axes; swaps: one flag per signal, default none): a version-4 stream, which
+    always carries a format -- sample_format, or the implied one written out (decode_signal_list)."""
+    if extents is not None:
+        from .utils import SampleFormat
+        if sample_format is None:
+            sample_format = SampleFormat.implied(model.dataset)
+        lvls = _levels_of(model)
+        for lv in lvls:
+            if not lv.mask_groupwise.all():
+                raise ValueError("level %r has %d groups that are not encoded yet" % (lv.pre, int((~lv.mask_groupwise).sum())))
+        return pack_indices([lv.idx_groupwise for lv in lvls], extents=extents, swaps=swaps, sample_format=sample_format)
     if sample_format is not None:
         from .utils import SampleFormat
         if not isinstance(sample_format, SampleFormat):
@@ -273,6 +350,12 @@ def _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, see
     return _finish(y, dataset, fmt, as_uint8, model.recon_layout())
 
 
+def _refuse_list(blob, who):
+    if len(blob) >= 6 and blob[:4] == MAGIC and struct.unpack_from("<H", blob, 4)[0] == VERSION_LIST:
+        raise ValueError("%s: a version-4 bitstream holds signals of their own sizes and orientations -- decode it with "
+                         "decode_signal_list" % who)
+
+
 def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", seed=42, precision=0, as_uint8=False,
                   sample_format=None, as_integer=False):
     """`decode`, finished on the device to WHOLE signals [n_signals, *grid, C] (n_signals = n_datapoints / patches per signal;
@@ -284,6 +367,7 @@ def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cu
     own; ValueError when they disagree): fp32 on the format's lattice, or with as_uint8 (alias: as_integer) the integers in
     the format's dtype -- uint16 for u16, int16 for s16."""
     as_uint8 = as_uint8 or as_integer
+    _refuse_list(blob, "decode_signal")
     fmt = _stream_format(blob, dataset, sample_format, as_uint8)
     extent = unpack(blob)[1]
     if extent is not None:
@@ -303,6 +387,7 @@ def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42,
     from . import ops
     from .utils import fit_config, preset_grid
     as_uint8 = as_uint8 or as_integer
+    _refuse_list(blob, "decode_signal_any")
     fmt = _stream_format(blob, dataset, None, as_uint8)
     levels, extent = unpack(blob)
     if extent is None:
@@ -317,3 +402,37 @@ def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42,
         raise ValueError("bitstream holds %d rows, signals of size %r take %d patches each" % (rows, extent, per))
     _, y = _decode_patches(fitted, dataset, checkpoint, blob, None, rows, device, seed, precision)
     return _finish(y, dataset, fmt, as_uint8, ops.PeLayout(pn, ps), size=extent)
+
+
+def decode_signal_list(config, dataset, checkpoint, blob, device="cuda", seed=42, precision=0, as_integer=False):
+    """The decoder of drivers.compress_signal_list: prior checkpoint + version-4 bitstream -> the LIST of signals, each at its own
+    size [*size_k, C] and in its own orientation (a signal flagged as exchanged comes back [size_k[1], size_k[0], C]: a portrait
+    one portrait).  `config` is the PRESET: all sizes of the stream must fit one grid of it (utils.fit_config; ValueError
+    otherwise, as when the level-1 rows are not n_signals x the patches of that grid), the patches are decoded with the preset's
+    own coordinate features, and ONE rcb_recon_finish_ragged call stitches, rounds to the stream's sample format and crops every
+    signal into its place.  fp32 on the format's lattice, or with as_integer the integers in the format's dtype (ValueError
+    for f32, which has none)."""
+    from . import ops
+    from .utils import fit_config, preset_grid
+    hdr = unpack_header(blob)
+    if hdr["version"] != VERSION_LIST:
+        raise ValueError("decode_signal_list: a version-%d bitstream -- decode it with decode_signal / decode_signal_any"
+                         % hdr["version"])
+    fmt = _stream_format(blob, dataset, None, as_integer)
+    extents, swaps = hdr["extents"], hdr["swaps"]
+    dd = config["data_dim"]
+    if len(extents[0]) != dd:
+        raise ValueError("bitstream extents of %d axes for a %d-D preset" % (len(extents[0]), dd))
+    fitted = fit_config(config, extents[0])
+    pn, ps = preset_grid(fitted)
+    for size in extents[1:]:
+        if preset_grid(fit_config(config, size))[0] != pn:
+            raise ValueError("bitstream extents %r and %r do not fit one grid of the preset" % (extents[0], size))
+    per = int(np.prod(pn))
+    rows = int(unpack_indices(blob)[0].shape[0])
+    if rows != len(extents) * per:
+        raise ValueError("bitstream holds %d rows, %d signals take %d patches each" % (rows, len(extents), per))
+    _, y = _decode_patches(fitted, dataset, checkpoint, blob, None, rows, device, seed, precision)
+    q, whole, _, _ = ops.recon_finish_ragged(y.to(torch.float32).contiguous(), layout=ops.PeLayout(pn, ps), sizes=extents,
+                                             swap=swaps, sample_format=fmt, want_int=as_integer, want_whole=not as_integer)
+    return q if as_integer else whole

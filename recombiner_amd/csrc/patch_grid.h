@@ -1,5 +1,5 @@
-// N4: the one index rule of the whole-signal entries (recon.hip: rcb_recon_finish, rcb_recon_finish_crop; signal.hip:
-// rcb_signal_patch, rcb_signal_patch_pad).  A signal lies on the grid G_i = pn[i] * ps[i]; its y [per][P][C] holds patch after patch
+// N4: the one index rule of the whole-signal entries (recon.hip: rcb_recon_finish and its _crop / _fmt / _ragged forms; signal.hip:
+// rcb_signal_patch and its _pad / _fmt / _ragged forms).  A signal lies on the grid G_i = pn[i] * ps[i]; its y [per][P][C] holds patch after patch
 // (b0 b1 b2 row-major), each patch pixel after pixel (p0 p1 p2 row-major), so the R = ps[2] * C elements of a patch row are
 // contiguous: a run.  Run number r of a signal counts (b0, b1, b2, p0, p1) row-major and lies at grid position g_i = b_i * ps_i + p_i,
 // its element `off` at e = b2 * R + off of the grid row (g0, g1).  Both files cut a signal into chunks of kChunk elements, one
@@ -80,6 +80,64 @@ inline void grid_elems(PatchGeo& g, int channels, long long E) {
   g.E = (int)E;
   g.n_chunks = (int)((E + kChunk - 1) / kChunk);
   g.L = g.sz[2] * channels;
+}
+
+// ---- the per-signal ("ragged") entries (rcb_signal_patch_ragged, rcb_recon_finish_ragged) ---------------------------------
+// One row of the device table per signal: where the by-value geometry of the other entries holds one extent (sz, L) and one set of
+// strides for the whole launch, a workgroup of these entries takes them from the row of its signal.
+struct RaggedRow {
+  long long off;          // the signal's first element, from the base pointer of the call
+  long long as[3];        // strides of the axes in elements, right-aligned (leading 0)
+  int sz[3];              // positions per axis, right-aligned (leading 1)
+  int flags;              // kRagged*: the memory path of this signal, decided by the host entry
+};
+constexpr int kRaggedQuad = 1;    // a quad inside the extent is 4 consecutive, aligned elements on the signal's side: one load / store
+constexpr int kRaggedDense = 2;   // (recon) the last axis is the innermost one: element e of a grid row lies e elements on
+
+// the geometry of one signal: g with the row's extent
+__device__ __forceinline__ PatchGeo ragged_geo(const PatchGeo& g, const RaggedRow& r) {
+  PatchGeo o = g;
+  o.sz[0] = r.sz[0]; o.sz[1] = r.sz[1]; o.sz[2] = r.sz[2];
+  o.L = r.sz[2] * g.C;
+  return o;
+}
+
+// The host tables -> rows (no flags yet), validated: `sizes` [n_data][3] against the grid of g, `spans` [n_data][4] non-negative.
+// reach[d]: offset of the farthest element of signal d with channel stride cs.
+inline int ragged_rows(const char* who, long long n_data, int nd, const PatchGeo& g, int channels, long long cs, const int32_t* sizes,
+                       const int64_t* spans, RaggedRow* rows, long long* reach) {
+  for (long long d = 0; d < n_data; ++d) {
+    RaggedRow& r = rows[d];
+    r.off = spans[4 * d];
+    r.flags = 0;
+    RCB_REQUIRE(r.off >= 0, RCB_ERR_ARG, "%s: signal %lld has the negative offset %lld", who, d, r.off);
+    long long far = r.off;
+    bool fits = true;
+    for (int i = 0; i < 3; ++i) {
+      const int a = i - (3 - nd);                            // the caller's axis, or < 0: a leading axis of one position
+      r.sz[i] = a < 0 ? 1 : sizes[3 * d + a];
+      r.as[i] = a < 0 ? 0 : spans[4 * d + 1 + a];
+      const long long G = (long long)g.pn[i] * g.ps[i];
+      RCB_REQUIRE(r.sz[i] >= 1 && r.sz[i] <= G, RCB_ERR_SHAPE, "%s: axis %d of signal %lld has %d positions (1 .. %lld)", who, a, d,
+                  r.sz[i], G);
+      RCB_REQUIRE(r.as[i] >= 0, RCB_ERR_ARG, "%s: negative stride %lld of axis %d of signal %lld", who, r.as[i], a, d);
+      // (sz - 1) * stride + far without overflow: a reach beyond 2^62 fits no buffer
+      if (r.sz[i] > 1 && r.as[i] > ((1LL << 62) - far) / (r.sz[i] - 1)) fits = false;
+      else far += (r.sz[i] - 1) * r.as[i];
+    }
+    if (channels > 1 && cs > ((1LL << 62) - far) / (channels - 1)) fits = false;
+    else far += (channels - 1) * cs;
+    reach[d] = fits ? far : (1LL << 62);
+  }
+  return RCB_OK;
+}
+
+// the rows -> the device table, on `st`, which is synchronised: the host rows may be freed on return
+inline int ragged_upload(const char* who, const RaggedRow* rows, long long n_data, void* table, hipStream_t st) {
+  hipError_t e = hipMemcpyAsync(table, rows, (size_t)n_data * sizeof(RaggedRow), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail((int)e, "%s: table upload failed: %s", who, hipGetErrorString(e));
+  return RCB_OK;
 }
 
 }  // namespace rcb

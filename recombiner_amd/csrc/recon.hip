@@ -28,6 +28,14 @@
 // rcb_recon_finish_crop is the same kernel (template parameter CROP) for datapoints of which only a leading extent is real.
 // Where a run lies in the stitched signal, the chunking and the validation of the patch grid are patch_grid.h's, shared with
 // signal.hip, which cuts the signals the other way.
+//
+// rcb_recon_finish_ragged (template parameter RAG) is the crop form with one extent and one
+// output span PER SIGNAL, read from row d of a device table the host entry writes (patch_grid.h: RaggedRow): each signal's outputs
+// go to its own offset of one buffer, along its own strides (a transposed delivery is only that).  The loads, the terms and the
+// order of the additions do not know about it: sse[d] stays the crop entry's for that signal alone, bit for bit.
+#include <algorithm>
+#include <vector>
+
 #include "patch_grid.h"
 
 #pragma clang fp contract(off)
@@ -63,6 +71,19 @@ __device__ __forceinline__ int crop_row(const PatchGeo& g, int run, int& e0) {
   decode_run<false>(g, run, g0, g1, b2);
   e0 = b2 * g.R;
   return (g0 < g.sz[0] && g1 < g.sz[1]) ? (g0 * g.sz[1] + g1) * g.L : -1;
+}
+
+// rcb_recon_finish_ragged: the same row inside signal `r`'s own span -> offset of its element 0 from the span's start, or -1
+__device__ __forceinline__ long long ragged_row(const PatchGeo& g, const RaggedRow& r, int run, int& e0) {
+  int g0, g1, b2;
+  decode_run<false>(g, run, g0, g1, b2);
+  e0 = b2 * g.R;
+  return (g0 < g.sz[0] && g1 < g.sz[1]) ? g0 * r.as[0] + g1 * r.as[1] : -1;
+}
+
+// element e = pos * C + c of a grid row inside the span: e itself where the last axis is the innermost (kRaggedDense)
+__device__ __forceinline__ long long ragged_elem(const PatchGeo& g, const RaggedRow& r, int e) {
+  return (r.flags & kRaggedDense) ? (long long)e : (e / g.C) * r.as[2] + e % g.C;
 }
 
 struct Elem {
@@ -139,14 +160,25 @@ __device__ __forceinline__ void store_one(uint8_t* out, long long o, unsigned q)
 // CROP: rcb_recon_finish_crop -- the same loads, the same additions in the same order; only what an element outside the extent
 // contributes (+0.0, no count) and where the outputs go differ.  W16 (rcb_recon_finish_fmt, modes 2 and 3): `u8` addresses 16-bit
 // words and an element is finish16's; W16 false is the code of the 8-bit and raw modes
-template <bool VEC, bool CROP, bool W16>
+// RAG (rcb_recon_finish_ragged; CROP): the extent and the place of the signal's outputs come from row d of `table` -- the span's
+// offset and strides instead of d * Ec and the contiguous cropped rows (x.Ec is not read, and x.vec_out says only that the output
+// POINTERS take quads: the rest is the row's kRaggedQuad); what is loaded, what an element contributes and the order of the
+// additions are CROP's.  RAG false is the code of the by-value entries and never reads `table`.
+template <bool VEC, bool CROP, bool W16, bool RAG>
 __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict__ y, const float* __restrict__ target,
                                                          uint8_t* __restrict__ u8, float* __restrict__ whole,
-                                                         double* __restrict__ part_sse, int* __restrict__ part_bad, ReconGeo x) {
-  const PatchGeo& g = x.g;
+                                                         double* __restrict__ part_sse, int* __restrict__ part_bad, ReconGeo x,
+                                                         const RaggedRow* __restrict__ table) {
   const long long blk = blockIdx.x;
-  const long long d = blk / g.n_chunks;
-  const int chunk = (int)(blk % g.n_chunks);
+  const long long d = blk / x.g.n_chunks;
+  const int chunk = (int)(blk % x.g.n_chunks);
+  PatchGeo gr;
+  RaggedRow rrow;
+  if (RAG) {
+    rrow = table[d];
+    gr = ragged_geo(x.g, rrow);
+  }
+  const PatchGeo& g = RAG ? gr : x.g;
   const long long base = d * (long long)g.E;
   const float* yd = y + base;
   const float* td = target ? target + base : nullptr;
@@ -175,7 +207,23 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
     }
     long long co[4] = {-1, -1, -1, -1};                  // CROP: offset inside the cropped datapoint, -1 outside the extent
     if (CROP) {
-      if (VEC) {
+      if (RAG && VEC) {                                  // the quad lies inside one run: one row
+        int e0;
+        const long long rb = ragged_row(g, rrow, s0 / g.R, e0);
+        e0 += s0 % g.R;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) co[k] = (rb >= 0 && e0 + k < g.L) ? rb + ragged_elem(g, rrow, e0 + k) : -1;
+      } else if (RAG) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (k < n) {
+            int e0;
+            const long long rb = ragged_row(g, rrow, (s0 + k) / g.R, e0);
+            e0 += (s0 + k) % g.R;
+            co[k] = (rb >= 0 && e0 < g.L) ? rb + ragged_elem(g, rrow, e0) : -1;
+          }
+        }
+      } else if (VEC) {
         int e0;
         const int row = crop_row(g, s0 / g.R, e0);
         e0 += s0 % g.R;
@@ -208,8 +256,8 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
     }
     if (CROP) {
       if (u8 || whole) {
-        const long long cbase = d * x.Ec;
-        if (VEC && x.vec_out && co[0] >= 0 && co[3] >= 0) {
+        const long long cbase = RAG ? rrow.off : d * x.Ec;
+        if (VEC && x.vec_out && (!RAG || (rrow.flags & kRaggedQuad) != 0) && co[0] >= 0 && co[3] >= 0) {
           const long long o = cbase + co[0];
           if (whole) *reinterpret_cast<float4*>(whole + o) = make_float4(e[0].v, e[1].v, e[2].v, e[3].v);
           if (u8) store_quad<W16>(u8, o, e);
@@ -275,20 +323,75 @@ template <bool W16>
 static void launch_finish(bool vec, bool crop, unsigned blocks, hipStream_t st, const float* y, const float* target, uint8_t* u8,
                           float* whole, double* part_sse, int* part_bad, const ReconGeo& x) {
   if (!crop) {
-    if (vec) recon_kernel<true, false, W16><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
-    else recon_kernel<false, false, W16><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+    if (vec) recon_kernel<true, false, W16, false><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, nullptr);
+    else recon_kernel<false, false, W16, false><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, nullptr);
   } else {
-    if (vec) recon_kernel<true, true, W16><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
-    else recon_kernel<false, true, W16><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x);
+    if (vec) recon_kernel<true, true, W16, false><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, nullptr);
+    else recon_kernel<false, true, W16, false><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, nullptr);
   }
 }
 
+template <bool W16>
+static void launch_ragged(bool vec, unsigned blocks, hipStream_t st, const float* y, const float* target, uint8_t* u8, float* whole,
+                          double* part_sse, int* part_bad, const ReconGeo& x, const RaggedRow* table) {
+  if (vec) recon_kernel<true, true, W16, true><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, table);
+  else recon_kernel<false, true, W16, true><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, table);
+}
+
+// rcb_recon_finish_ragged: the caller's tables and the device buffer their copy goes to (null `sizes` .. for the other entries)
+struct RaggedArgs {
+  const int32_t* sizes;
+  const int64_t* spans;
+  int64_t out_elems;
+  void* table;
+  int64_t table_bytes;
+};
+
+// The output spans of the rows: every signal dense with its axes in some order, the spans pairwise disjoint and inside
+// [0, out_elems); sets the rows' flags (kRaggedQuad on the offsets and strides alone: the pointers' alignment is x.vec_out).
+static int ragged_spans(const char* who, std::vector<RaggedRow>& rows, int channels, long long out_elems) {
+  std::vector<std::pair<long long, long long>> ranges;
+  ranges.reserve(rows.size());
+  for (size_t d = 0; d < rows.size(); ++d) {
+    RaggedRow& r = rows[d];
+    int ax[3] = {0, 1, 2};
+    std::sort(ax, ax + 3, [&](int a, int b) { return r.as[a] != r.as[b] ? r.as[a] < r.as[b] : a > b; });
+    long long want = channels;
+    for (int i = 0; i < 3; ++i) {
+      const int a = ax[i];
+      if (r.sz[a] == 1) continue;
+      RCB_REQUIRE(r.as[a] == want, RCB_ERR_SHAPE,
+                  "%s: signal %lld is not dense (a stride of %lld where %lld would continue the axes below it)", who, (long long)d,
+                  r.as[a], want);
+      want *= r.sz[a];                                       // (<= E * channels < 2^36)
+    }
+    RCB_REQUIRE(r.off <= out_elems && want <= out_elems - r.off, RCB_ERR_SHAPE,
+                "%s: signal %lld spans [%lld, %lld) of an output of %lld elements", who, (long long)d, r.off, r.off + want, out_elems);
+    ranges.emplace_back(r.off, r.off + want);
+    const long long L = (long long)r.sz[2] * channels;
+    const bool dense = r.sz[2] == 1 || r.as[2] == channels;
+    bool quad = dense && L % 4 == 0 && r.off % 4 == 0;
+    for (int i = 0; i < 2; ++i) quad = quad && (r.sz[i] == 1 || r.as[i] % 4 == 0);
+    r.flags = (dense ? kRaggedDense : 0) | (quad ? kRaggedQuad : 0);
+  }
+  std::sort(ranges.begin(), ranges.end());
+  for (size_t i = 1; i < ranges.size(); ++i)
+    RCB_REQUIRE(ranges[i].first >= ranges[i - 1].second, RCB_ERR_SHAPE, "%s: the spans [%lld, %lld) and [%lld, %lld) overlap", who,
+                ranges[i - 1].first, ranges[i - 1].second, ranges[i].first, ranges[i].second);
+  return RCB_OK;
+}
+
 // all entries: `size` null is the uncropped form (every datapoint fills its grid); `fmt`: rcb_recon_finish_fmt, which alone takes
-// modes 2 (u16 at `depth`) and 3 (s16), `u8` then addressing 16-bit words
+// modes 2 (u16 at `depth`) and 3 (s16), `u8` then addressing 16-bit words; `rag`: rcb_recon_finish_ragged (fmt, size null: the
+// extents are per signal)
 static int finish_entry(const char* who, bool fmt, const float* y, const float* target, int64_t n_rows, int32_t n_pix,
                         int32_t channels, int32_t nd, const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size,
                         int32_t mode, int32_t depth, uint8_t* u8, float* whole, double* sse, int32_t* n_bad, void* workspace,
-                        int64_t workspace_bytes, rcb_stream_t stream) {
+                        int64_t workspace_bytes, rcb_stream_t stream, const RaggedArgs* rag = nullptr) {
+  if (rag && n_rows == 0) {                                  // no signals: nothing to validate against, nothing launched
+    RCB_REQUIRE(mode >= 0 && mode <= 3, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw, 2 = u16, 3 = s16)", who, mode);
+    return RCB_OK;
+  }
   RCB_REQUIRE(y && workspace, RCB_ERR_ARG, "%s: null y or workspace", who);
   if (fmt) {
     RCB_REQUIRE(mode >= 0 && mode <= 3, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw, 2 = u16, 3 = s16)", who, mode);
@@ -297,7 +400,8 @@ static int finish_entry(const char* who, bool fmt, const float* y, const float* 
   } else {
     RCB_REQUIRE(mode == 0 || mode == 1, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw)", who, mode);
   }
-  RCB_REQUIRE(nd >= (size ? 1 : 0) && nd <= 3, RCB_ERR_UNSUPPORTED, "%s: %d grid dimensions (%d .. 3)", who, nd, size ? 1 : 0);
+  RCB_REQUIRE(nd >= (size || rag ? 1 : 0) && nd <= 3, RCB_ERR_UNSUPPORTED, "%s: %d grid dimensions (%d .. 3)", who, nd,
+              size || rag ? 1 : 0);
   RCB_REQUIRE(nd == 0 || (patch_nums && patch_size), RCB_ERR_ARG, "%s: null patch geometry", who);
   RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "%s: %d channels (1 .. 32)", who, channels);
   RCB_REQUIRE(n_rows > 0 && n_pix > 0, RCB_ERR_SHAPE, "%s: %lld rows of %d pixels", who, (long long)n_rows, n_pix);
@@ -333,6 +437,30 @@ static int finish_entry(const char* who, bool fmt, const float* y, const float* 
   int* part_bad = reinterpret_cast<int*>(part_sse + blocks);
   hipStream_t st = (hipStream_t)stream;
   bool vec;
+  if (rag) {
+    RCB_REQUIRE(rag->sizes && rag->spans && rag->table, RCB_ERR_ARG, "%s: null sizes, spans or table", who);
+    const int64_t tb = rcb_ragged_table_bytes(n_data);
+    RCB_REQUIRE(tb > 0 && rag->table_bytes >= tb && aligned(rag->table, 8), RCB_ERR_SHAPE,
+                "%s: table of %lld bytes (8-byte aligned), %lld needed", who, (long long)rag->table_bytes, (long long)tb);
+    RCB_REQUIRE(rag->out_elems >= 0, RCB_ERR_SHAPE, "%s: an output of %lld elements", who, (long long)rag->out_elems);
+    std::vector<RaggedRow> rows((size_t)n_data);
+    std::vector<long long> reach((size_t)n_data);
+    if (const int err = ragged_rows(who, n_data, nd, g, channels, 1, rag->sizes, rag->spans, rows.data(), reach.data())) return err;
+    if (const int err = ragged_spans(who, rows, channels, rag->out_elems)) return err;
+    if (const int err = ragged_upload(who, rows.data(), n_data, rag->table, st)) return err;
+    x.Ec = 0;
+    vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16));
+    x.vec_out = (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, q_align));
+    const RaggedRow* table = static_cast<const RaggedRow*>(rag->table);
+    if (w16) launch_ragged<true>(vec, (unsigned)blocks, st, y, target, u8, whole, part_sse, part_bad, x, table);
+    else launch_ragged<false>(vec, (unsigned)blocks, st, y, target, u8, whole, part_sse, part_bad, x, table);
+    RCB_LAUNCH_CHECK();
+    if (sse || n_bad) {
+      recon_reduce_kernel<<<(unsigned)n_data, kThreads, 0, st>>>(part_sse, part_bad, g.n_chunks, sse, n_bad);
+      RCB_LAUNCH_CHECK();
+    }
+    return RCB_OK;
+  }
   if (!size) {
     x.vec_out = 0, x.Ec = 0;
     vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16)) && (!whole || aligned(whole, 16)) &&
@@ -375,4 +503,14 @@ extern "C" int rcb_recon_finish_fmt(const float* y, const float* target, int64_t
                                     int64_t workspace_bytes, rcb_stream_t stream) {
   return finish_entry("recon_finish_fmt", true, y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, size, mode, depth,
                       static_cast<uint8_t*>(q_out), whole, sse, n_bad, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rcb_recon_finish_ragged(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels,
+                                       int32_t nd, const int32_t* patch_nums, const int32_t* patch_size, const int32_t* sizes,
+                                       const int64_t* spans, int64_t out_elems, int32_t mode, int32_t depth, void* q_out,
+                                       float* whole, double* sse, int32_t* n_bad, void* workspace, int64_t workspace_bytes,
+                                       void* table, int64_t table_bytes, rcb_stream_t stream) {
+  const RaggedArgs rag = {sizes, spans, out_elems, table, table_bytes};
+  return finish_entry("recon_finish_ragged", true, y, target, n_rows, n_pix, channels, nd, patch_nums, patch_size, nullptr, mode,
+                      depth, static_cast<uint8_t*>(q_out), whole, sse, n_bad, workspace, workspace_bytes, stream, &rag);
 }

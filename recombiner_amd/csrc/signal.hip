@@ -25,6 +25,13 @@
 // strides of the axes that still have more than one position) a quad whose 4 elements lie below L is 4 consecutive source elements
 // on a 4-element boundary; any other quad moves element by element through the clipped index.  Every read is at a clipped
 // position: inside the source.
+//
+// rcb_signal_patch_ragged (template parameter RAG) is the _pad cut with one extent, one offset
+// and one stride set PER SIGNAL, read from row d of a device table the host entry writes (patch_grid.h: RaggedRow): signals of mixed
+// sizes and orientations in one launch.  Whether a signal's quads are single loads is decided per signal on the host, by the same
+// conditions, and travels in the row; the host entry also holds every signal's farthest element inside the source buffer.
+#include <vector>
+
 #include "patch_grid.h"
 
 #pragma clang fp contract(off)
@@ -48,16 +55,31 @@ __device__ __forceinline__ unsigned unit16(unsigned w, float m) {
   return __float_as_uint(((float)(int)(short)w + 32768.0f) / 65536.0f);
 }
 
-// PAD false never reads the extent (g.sz, g.L)
-template <int KIND, bool VEC, bool PAD>
-__global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __restrict__ src, unsigned* __restrict__ y, SignalGeo x) {
-  const PatchGeo& g = x.g;
+// PAD false never reads the extent (g.sz, g.L).  RAG (rcb_signal_patch_ragged; PAD): the extent, the strides
+// and the place of the signal come from row d of `table` where the other entries take them from x, and VEC then says only that y
+// takes whole quads (R % 4 == 0, y aligned) -- whether a quad of the SOURCE is one load is the row's kRaggedQuad, uniform over the
+// workgroup.  RAG false is the code of the by-value entries and never reads `table`.
+template <int KIND, bool VEC, bool PAD, bool RAG>
+__global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __restrict__ src, unsigned* __restrict__ y, SignalGeo xv,
+                                                                const RaggedRow* __restrict__ table) {
   const long long blk = blockIdx.x;
-  const long long d = blk / g.n_chunks;
-  const int chunk = (int)(blk % g.n_chunks);
-  const uint8_t* s8 = static_cast<const uint8_t*>(src) + d * x.ds;
-  const unsigned* s32 = static_cast<const unsigned*>(src) + d * x.ds;
-  const uint16_t* s16 = static_cast<const uint16_t*>(src) + d * x.ds;
+  const long long d = blk / xv.g.n_chunks;
+  const int chunk = (int)(blk % xv.g.n_chunks);
+  SignalGeo xr;
+  bool quad = true;                                          // (RAG) a quad of this signal's source is one load
+  if (RAG) {
+    const RaggedRow row = table[d];
+    xr = xv;
+    xr.g = ragged_geo(xv.g, row);
+    xr.as[0] = row.as[0]; xr.as[1] = row.as[1]; xr.as[2] = row.as[2];
+    xr.ds = row.off;                                         // (the signal's own offset: not a multiple of d)
+    quad = (row.flags & kRaggedQuad) != 0;
+  }
+  const SignalGeo& x = RAG ? xr : xv;
+  const PatchGeo& g = x.g;
+  const uint8_t* s8 = static_cast<const uint8_t*>(src) + (RAG ? x.ds : d * x.ds);
+  const unsigned* s32 = static_cast<const unsigned*>(src) + (RAG ? x.ds : d * x.ds);
+  const uint16_t* s16 = static_cast<const uint16_t*>(src) + (RAG ? x.ds : d * x.ds);
   unsigned* yd = y + d * (long long)g.E;
   for (int it = 0; it < kQuadsPerThread; ++it) {
     const long long s0l = (long long)chunk * kChunk + ((long long)it * kThreads + threadIdx.x) * 4;
@@ -65,12 +87,12 @@ __global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __re
     const int s0 = (int)s0l;
     const int n = g.E - s0 < 4 ? g.E - s0 : 4;
     int g0, g1, b2, e = 0;
-    if (VEC) {                                           // R % 4 == 0: the quad lies inside one run
+    if (VEC && (!RAG || quad)) {                         // R % 4 == 0: the quad lies inside one run
       decode_run<PAD>(g, s0 / g.R, g0, g1, b2);
       e = b2 * g.R + s0 % g.R;
     }
     unsigned v[4] = {0u, 0u, 0u, 0u};
-    if (VEC && (!PAD || e + 3 < g.L)) {                  // 4 consecutive source elements (the last axis is dense: its offset is e)
+    if (VEC && (!RAG || quad) && (!PAD || e + 3 < g.L)) {  // 4 consecutive source elements (the last axis is dense: offset e)
       const long long o = g0 * x.as[0] + g1 * x.as[1] + e;
       if (KIND == 0) {
         const unsigned w = *reinterpret_cast<const unsigned*>(s8 + o);
@@ -109,11 +131,11 @@ __global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __re
 template <int KIND>
 void launch_patch(bool vec, bool pad, unsigned blocks, hipStream_t st, const void* src, unsigned* yo, const SignalGeo& x) {
   if (!pad) {
-    if (vec) signal_patch_kernel<KIND, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
-    else signal_patch_kernel<KIND, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x);
+    if (vec) signal_patch_kernel<KIND, true, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x, nullptr);
+    else signal_patch_kernel<KIND, false, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x, nullptr);
   } else {
-    if (vec) signal_patch_kernel<KIND, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
-    else signal_patch_kernel<KIND, false, true><<<blocks, kThreads, 0, st>>>(src, yo, x);
+    if (vec) signal_patch_kernel<KIND, true, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x, nullptr);
+    else signal_patch_kernel<KIND, false, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x, nullptr);
   }
 }
 
@@ -171,7 +193,82 @@ int patch_entry(const char* who, bool fmt, const void* src, int32_t src_kind, in
   return RCB_OK;
 }
 
+template <int KIND>
+void launch_ragged(bool vec, unsigned blocks, hipStream_t st, const void* src, unsigned* yo, const SignalGeo& x,
+                   const RaggedRow* table) {
+  if (vec) signal_patch_kernel<KIND, true, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x, table);
+  else signal_patch_kernel<KIND, false, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x, table);
+}
+
 }  // namespace
+
+extern "C" int64_t rcb_ragged_table_bytes(int64_t n_data) {
+  if (n_data < 0 || n_data > 0x7fffffffLL) return -1;
+  return n_data * (int64_t)sizeof(RaggedRow);
+}
+
+extern "C" int rcb_signal_patch_ragged(const void* src, int64_t src_elems, int32_t src_kind, int32_t depth, int64_t n_data,
+                                       int32_t nd, const int32_t* patch_nums, const int32_t* patch_size, const int32_t* sizes,
+                                       const int64_t* spans, int32_t channels, int64_t channel_stride, float* y, void* table,
+                                       int64_t table_bytes, rcb_stream_t stream) {
+  const char* who = "signal_patch_ragged";
+  RCB_REQUIRE(src_kind >= 0 && src_kind <= 3, RCB_ERR_ARG, "%s: source kind %d (0 = uint8, 1 = fp32, 2 = u16, 3 = s16)", who, src_kind);
+  RCB_REQUIRE(src_kind == 2 ? (depth >= 9 && depth <= 16) : depth == 0, RCB_ERR_ARG,
+              "%s: depth %d for source kind %d (9 .. 16 for u16, 0 for the others)", who, depth, src_kind);
+  RCB_REQUIRE(nd >= 1 && nd <= 3, RCB_ERR_UNSUPPORTED, "%s: %d grid dimensions (1 .. 3)", who, nd);
+  RCB_REQUIRE(patch_nums && patch_size, RCB_ERR_ARG, "%s: null patch geometry", who);
+  RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "%s: %d channels (1 .. 32)", who, channels);
+  RCB_REQUIRE(n_data >= 0, RCB_ERR_SHAPE, "%s: %lld signals", who, (long long)n_data);
+  SignalGeo x;
+  PatchGeo& g = x.g;
+  long long per, P;
+  const int64_t no_stride[3] = {0, 0, 0};                    // (selects the per-signal wording of the 2^31 limit)
+  if (const int err = grid_axes(who, nd, patch_nums, patch_size, nullptr, no_stride, g, per, P)) return err;
+  RCB_REQUIRE(channel_stride >= 0, RCB_ERR_ARG, "%s: negative channel stride %lld", who, (long long)channel_stride);
+  const long long E = per * P * channels;
+  RCB_REQUIRE(E <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED, "%s: %lld elements per signal (up to 2^31 - 1)", who, E);
+  if (n_data == 0) return RCB_OK;
+  RCB_REQUIRE(src && y, RCB_ERR_ARG, "%s: null src or y", who);
+  RCB_REQUIRE(sizes && spans && table, RCB_ERR_ARG, "%s: null sizes, spans or table", who);
+  const int64_t need = rcb_ragged_table_bytes(n_data);
+  RCB_REQUIRE(need > 0 && table_bytes >= need && aligned(table, 8), RCB_ERR_SHAPE,
+              "%s: table of %lld bytes (8-byte aligned), %lld needed", who, (long long)table_bytes, (long long)need);
+  grid_elems(g, channels, E);
+  RCB_REQUIRE(n_data <= 0x7fffffffLL / g.n_chunks, RCB_ERR_UNSUPPORTED,
+              "%s: %lld signals of %lld elements need more than 2^31 - 1 workgroups", who, (long long)n_data, E);
+  std::vector<RaggedRow> rows((size_t)n_data);
+  std::vector<long long> reach((size_t)n_data);
+  if (const int err = ragged_rows(who, n_data, nd, g, channels, channel_stride, sizes, spans, rows.data(), reach.data())) return err;
+  const uintptr_t esize = src_kind == 0 ? 1 : src_kind == 1 ? 4 : 2;
+  for (long long d = 0; d < n_data; ++d) {
+    RaggedRow& r = rows[(size_t)d];
+    RCB_REQUIRE(reach[(size_t)d] < src_elems, RCB_ERR_SHAPE, "%s: signal %lld reaches element %lld of a source of %lld", who, d,
+                reach[(size_t)d], (long long)src_elems);
+    // the vector-path conditions of patch_entry, on this signal's strides and on the address of its first element
+    bool quad = (channels == 1 || channel_stride == 1) && (r.sz[2] == 1 || r.as[2] == channels) &&
+                ((uintptr_t)src + (uintptr_t)r.off * esize) % (4 * esize) == 0;
+    for (int i = 0; i < 2; ++i) quad = quad && (r.sz[i] == 1 || r.as[i] % 4 == 0);
+    r.flags = quad ? kRaggedQuad : 0;
+  }
+  x.ds = 0;
+  x.cs = channel_stride;
+  x.m = src_kind == 2 ? (float)((1 << depth) - 1) : 0.0f;
+  for (int i = 0; i < 3; ++i) x.as[i] = 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (const int err = ragged_upload(who, rows.data(), n_data, table, st)) return err;
+  const bool vec = g.R % 4 == 0 && aligned(y, 16);           // y takes whole quads (E % 4 == 0 by R % 4 == 0)
+  const unsigned blocks = (unsigned)(n_data * g.n_chunks);
+  unsigned* yo = reinterpret_cast<unsigned*>(y);
+  const RaggedRow* tb = static_cast<const RaggedRow*>(table);
+  switch (src_kind) {
+    case 0: launch_ragged<0>(vec, blocks, st, src, yo, x, tb); break;
+    case 1: launch_ragged<1>(vec, blocks, st, src, yo, x, tb); break;
+    case 2: launch_ragged<2>(vec, blocks, st, src, yo, x, tb); break;
+    default: launch_ragged<3>(vec, blocks, st, src, yo, x, tb); break;
+  }
+  RCB_LAUNCH_CHECK();
+  return RCB_OK;
+}
 
 extern "C" int rcb_signal_patch(const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,
                                 const int32_t* patch_size, int32_t channels, int64_t data_stride, const int64_t* axis_stride,

@@ -301,7 +301,8 @@ def compress_signals(config, dataset, checkpoint, signals, x=None, channels_firs
 def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_first=False, bitstream_path=None,
                          sample_format=None, **kw):
     """`compress_signals` for signals of ANY size that the preset can be fitted to: `signals` is [n, *size, C] (or [n, C, *size]
-    with channels_first), uint8 or fp32, one size per call.  The config is fitted (utils.fit_config: patched presets get the
+    with channels_first), uint8 or fp32, one size per call (a list of signals of mixed sizes: compress_signal_list).
+    The config is fitted (utils.fit_config: patched presets get the
     next whole patch grid that level 2 divides; unpatched presets keep theirs and take signals up to it), the signals'
     edge samples are replicated out to that grid while they are cut into y on the device (rcb_signal_patch_pad), and `compress`
     runs with the fitted config -- a checkpoint trained at the preset's patch_nums drives it, its priors being per parameter.
@@ -309,8 +310,10 @@ def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_
     loss does not: padded samples are fitted at full weight and cost rate, and a wholly padded patch still costs its groups.
     The bitstream (bitstream_path) is version 2 and carries `size`; bitstream.decode_signal_any decodes and crops it.
     Rate: bpp = bitstream.payload_bits(blob) / (n * prod(size)), bits per real sample position.
-    There is no landscape swap and no origin: the signals are coded in the orientation they are passed in -- a portrait photograph
-    on a landscape-trained prior is the caller's to transpose.  Every other argument is `compress`'s.
+    There is no landscape swap and no origin here: the signals are coded in the orientation they are passed in.  Signals of mixed
+    sizes and orientations -- a photo set with portraits in it, clips of different lengths -- go through compress_signal_list, which
+    swaps a portrait signal through its strides, buckets the sizes by the grid they fit and writes version-4 streams.  Every other
+    argument is `compress`'s.
     sample_format (utils.SampleFormat; required for uint16 / int16 signals, ValueError without it): how the samples are stored.
     `distortion` is then formed on the format's lattice -- the figure of the signal decode_signal_any delivers.  For s16 audio
     that is the distortion of the delivered PCM, NOT the reference's figure, which scores the unrounded reconstruction
@@ -337,6 +340,73 @@ def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_
         with open(bitstream_path, "wb") as f:
             f.write(bitstream.encode(model, extent=size, sample_format=sample_format))
     return distortion, model, fitted
+
+
+def compress_signal_list(config, dataset, checkpoint, signals, channels_first=False, landscape=True, sample_format=None,
+                         bitstream_dir=None, **kw):
+    """`compress_signals_any` for a LIST of signals of mixed sizes and orientations: signals[k] is [*size_k, C] (or [C, *size_k]
+    with channels_first), all of one dtype.  utils.ragged_plan decides per signal whether its two axes are exchanged (2-D presets
+    with `landscape`: a portrait signal is coded landscape, read through transposed strides, nothing copied) and groups the
+    signals into buckets by the patch grid their size fits (utils.fit_config).  Per bucket: all its signals are cut into y in ONE
+    rcb_signal_patch_ragged call, each edge-padded to the grid from its own extent; `compress` runs once with the fitted config;
+    the distortion counts each signal's real samples (report(sizes=), rcb_recon_finish_ragged); the stream is version 4 and
+    carries every size and swap flag (bitstream.decode_signal_list gives the signals back, a portrait one portrait).
+    -> (distortion, records, bpp): distortion is an array of per-signal figures in input order (cifar, protein) or the one figure
+    pooled over the real samples of the whole list (kodak, video, audio); records holds one dict per bucket -- indices (input
+    positions of its signals), sizes (along the model's axes), swaps, model, config (fitted) and stream (the version-4 bytes; also
+    written to bitstream_dir/bucket_<i>.rcb when a directory is given); bpp = sum of payload bits / sum of prod(size_k).
+    As with compress_signals_any the padded samples are trained on at full weight and cost rate; there is one model per grid, and the
+    swap exists for 2-D presets only.  sample_format: compress_signals_any's.  Every other argument is `compress`'s."""
+    import os
+    from . import bitstream, utils
+    signals = list(signals)
+    if not signals:
+        raise ValueError("compress_signal_list: an empty list of signals")
+    if "bitstream_path" in kw:
+        raise ValueError("compress_signal_list: one stream per bucket is written, to bitstream_dir")
+    device = kw.get("device", "cuda")
+    dd = config["data_dim"]
+    views = []
+    for k, t in enumerate(signals):
+        _signal_format("compress_signal_list", t, sample_format)
+        if t.dim() != dd + 1 or t.dtype != signals[0].dtype:
+            raise ValueError("compress_signal_list: signal %d is %s with %d axes; [*size, C] of %s expected for a %d-D preset"
+                             % (k, t.dtype, t.dim(), signals[0].dtype, dd))
+        v = t.to(device)
+        if channels_first:
+            v = v.movedim(0, -1)
+        if v.shape[-1] != config["output_dim"]:
+            raise ValueError("compress_signal_list: signal %d has %d channels, the preset %d" % (k, v.shape[-1], config["output_dim"]))
+        views.append(v)
+    swaps, buckets = utils.ragged_plan(config, [tuple(v.shape[:-1]) for v in views], landscape=landscape)
+    per_signal = dataset in ("cifar", "protein")
+    figures = np.zeros(len(views), dtype=np.float64)
+    pooled_err = pooled_n = 0.0
+    records, bits, positions = [], 0, 0
+    for b, bucket in enumerate(buckets):
+        fitted, idx, sizes = bucket["config"], bucket["indices"], bucket["sizes"]
+        cut = [views[k].transpose(0, 1) if swaps[k] else views[k] for k in idx]
+        y = ops.signal_patch_ragged(cut, utils.signal_layout(fitted), sample_format=sample_format)
+        x = utils.preset_inputs(fitted, device)[None].expand(y.shape[0], -1, -1)
+        _, model = compress(fitted, dataset, checkpoint, x, y, **kw)
+        d = model.report(x, y, sizes=sizes, sample_format=sample_format)
+        count = float(sum(int(np.prod(s)) for s in sizes) * y.shape[-1])
+        if per_signal:
+            figures[idx] = d
+        else:                                                # a PSNR over the bucket's real samples -> its share of the summed error
+            pooled_err += 10.0 ** (-d / 10.0) * count
+            pooled_n += count
+        blob = bitstream.encode(model, extents=sizes, swaps=[swaps[k] for k in idx], sample_format=sample_format)
+        if bitstream_dir is not None:
+            os.makedirs(bitstream_dir, exist_ok=True)
+            with open(os.path.join(bitstream_dir, "bucket_%d.rcb" % b), "wb") as f:
+                f.write(blob)
+        bits += bitstream.payload_bits(blob)
+        positions += sum(int(np.prod(s)) for s in sizes)
+        records.append(dict(indices=list(idx), sizes=list(sizes), swaps=[swaps[k] for k in idx], model=model, config=fitted,
+                            stream=blob))
+    distortion = figures if per_signal else float(-10.0 * np.log10(pooled_err / pooled_n))
+    return distortion, records, bits / positions
 
 
 def rd_point(config, dataset, X, Y_train, Y_test, max_bitrate, device="cuda", seed=42, n_em_iter=550, first_epochs=200, epochs=100,

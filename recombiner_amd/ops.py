@@ -1310,6 +1310,180 @@ def _signal_patch(what, signals, layout, out, pad, fmt=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------
+# N4 (413): batches of signals of mixed sizes and memory layouts (rcb_signal_patch_ragged, rcb_recon_finish_ragged)
+# ---------------------------------------------------------------------------------------------------
+def _ragged_tables(sizes, spans, nd):
+    """the host tables of the ragged entries: sizes int32 [n, 3], spans int64 [n, 4] = (offset, axis strides), zero-filled past nd"""
+    n = len(sizes)
+    sz, sp = np.zeros((n, 3), dtype=np.int32), np.zeros((n, 4), dtype=np.int64)
+    for k in range(n):
+        if len(sizes[k]) != nd or len(spans[k]) != nd + 1:
+            raise RcbError(f"signal {k}: a size of {len(sizes[k])} axes for a layout of {nd}")
+        sz[k, :nd] = sizes[k]
+        sp[k, :nd + 1] = spans[k]
+    return sz, sp
+
+
+def _ragged_table(n, device):
+    n_bytes = int(_lib.load().rcb_ragged_table_bytes(n))
+    return torch.empty(max(n_bytes, 8), device=device, dtype=torch.uint8), max(n_bytes, 8)
+
+
+def _np_ptr(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def signal_patch_ragged(signals, layout, out=None, sample_format=None):
+    """`signal_patch_pad` for a LIST of signals of mixed sizes and memory layouts in one call (rcb_signal_patch_ragged): signals[k] is
+    a GPU tensor [*size_k, C] with 1 <= size_k[i] <= G_i of `layout`; all share one dtype, C and device, and each has ANY strides,
+    storage offset and allocation -- a transposed or channel-first view, an expanded channel, a window of a larger signal.
+    Nothing is copied: the lowest address among them is the base, every signal goes to the kernel as its offset from it and its
+    own strides (an offset that is no whole number of elements is an RcbError), and per signal the result is signal_patch_pad's
+    bit for bit.  -> y [n * per, P, C] fp32, signal k's patches in rows k * per .. (k + 1) * per.
+    The C entry takes one channel stride per call: consecutive signals that share theirs go in one launch (all of them, usually),
+    a list that mixes channel-last and channel-first signals in as many launches as it has runs.
+    out: optional contiguous fp32 [n * per, P, C].  sample_format: as signal_patch's.  The only host sync is the table upload."""
+    what = "signal_patch_ragged"
+    signals = list(signals)
+    nd, pn, ps, per, P, grid = _grid_args(layout)
+    if not signals:
+        raise RcbError(f"{what}: an empty list of signals")
+    first = signals[0]
+    for k, t in enumerate(signals):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RcbError(f"{what}: signals must be GPU tensors (the HIP path has no CPU fallback)")
+        if t.dtype != first.dtype or t.device != first.device or t.dim() != nd + 1 or t.shape[-1] != first.shape[-1]:
+            raise RcbError(f"{what}: signal {k} is {t.dtype} {tuple(t.shape)} on {t.device}; all signals are [*size, C] of one "
+                           f"dtype, channel count and device, with {nd} axes of size")
+    if sample_format is not None:
+        if not sample_format.accepts(first.dtype):
+            raise RcbError(f"{what}: {sample_format!r} reads {sample_format.dtype} signals, got {first.dtype}")
+        kind, depth = sample_format.kind, sample_format.depth
+    elif first.dtype in SIGNAL_KINDS:
+        kind, depth = SIGNAL_KINDS[first.dtype], 0
+    else:
+        raise RcbError(f"{what}: signals must be uint8 or fp32, got {first.dtype}")
+    n, Cc, dev, item = len(signals), int(first.shape[-1]), first.device, first.element_size()
+    shape = (n * per, P, Cc)
+    fits = 0 <= per * P * Cc <= 0x7fffffff
+    if out is None:
+        out = torch.empty(shape if fits else (1,), device=dev, dtype=f32)
+    elif tuple(out.shape) != shape or out.dtype != f32 or out.device != dev or not out.is_contiguous():
+        raise RcbError(f"{what}: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {f32} on the "
+                       "device of the signals")
+    base = min(t.data_ptr() for t in signals)
+    end = max(t.untyped_storage().data_ptr() + t.untyped_storage().nbytes() for t in signals)
+    sizes, spans, cstride = [], [], []
+    for k, t in enumerate(signals):
+        if (t.data_ptr() - base) % item:
+            raise RcbError(f"{what}: signal {k} lies {t.data_ptr() - base} bytes above the lowest one: no whole number of "
+                           f"{item}-byte elements")
+        sizes.append([int(v) for v in t.shape[:-1]])
+        spans.append([(t.data_ptr() - base) // item] + [int(v) for v in t.stride()[:-1]])
+        cstride.append(int(t.stride(-1)) if Cc > 1 else 1)
+    sz, sp = _ragged_tables(sizes, spans, nd)
+    k0 = 0
+    while k0 < n:                                            # runs of one channel stride
+        k1 = k0 + 1
+        while k1 < n and cstride[k1] == cstride[k0]:
+            k1 += 1
+        table, n_bytes = _ragged_table(k1 - k0, dev)
+        y_ptr = out.data_ptr() + k0 * per * P * Cc * 4 if fits else out.data_ptr()
+        _launch("rcb_signal_patch_ragged", C.c_void_p(base), (end - base) // item, kind, depth, k1 - k0, nd, pn, ps,
+                _np_ptr(sz[k0:k1]), _np_ptr(sp[k0:k1]), Cc, cstride[k0], C.c_void_p(y_ptr), ptr(table), n_bytes)
+        k0 = k1
+    return out
+
+
+def _ragged_spans(sizes, swap, Cc):
+    """the spans of a ragged output buffer: signal k dense at an offset that is a multiple of 4 elements (so that a quad of it can
+    be one store), its axes 0 and 1 exchanged in memory where swap[k] -> (spans [(offset, *strides)], shapes as delivered, elements)"""
+    spans, shapes, off = [], [], 0
+    for size, sw in zip(sizes, swap):
+        order = list(range(len(size)))
+        if sw:
+            order[0], order[1] = 1, 0                        # the memory order of the model's axes
+        stride, st = Cc, [0] * len(size)
+        for a in reversed(order):
+            st[a] = stride
+            stride *= size[a]
+        spans.append([off] + st)
+        shapes.append(tuple(size[a] for a in order) + (Cc,))
+        off += -(-stride // 4) * 4
+    return spans, shapes, off
+
+
+def recon_finish_ragged_into(y, target, layout, sizes, spans, out_elems, mode=RECON_8BIT, depth=0, q_buf=None, whole_buf=None,
+                             sse=None, n_bad=None):
+    """rcb_recon_finish_ragged on the caller's own output buffers and spans (what recon_finish_ragged lays out for itself):
+    q_buf / whole_buf are 1-D GPU tensors of at least out_elems elements (or None), spans[k] = (offset, *axis strides) in elements.
+    -> (sse fp64 [n] or None without target, n_bad int32 [n])."""
+    lib = _lib.load()
+    if y.dim() != 3 or y.dtype != f32 or not y.is_cuda or not y.is_contiguous():
+        raise RcbError("recon_finish_ragged: y must be a contiguous fp32 GPU tensor [N, P, C]")
+    if target is not None and (tuple(target.shape) != tuple(y.shape) or target.dtype != f32 or not target.is_contiguous()
+                               or target.device != y.device):
+        raise RcbError(f"recon_finish_ragged: target must be a contiguous fp32 tensor {list(y.shape)} on the device of y")
+    N, P, Cc = (int(v) for v in y.shape)
+    nd, pn, ps, per, _, _ = _grid_args(layout)
+    n = len(sizes)
+    if nd == 0 or n * per != N:
+        raise RcbError(f"recon_finish_ragged: {n} sizes for {N} rows of a layout of {per} patches per signal")
+    sz, sp = _ragged_tables(sizes, spans, nd)
+    dev = y.device
+    qdt = {RECON_8BIT: torch.uint8, RECON_U16: torch.uint16, RECON_S16: torch.int16}.get(int(mode))
+    for b, dt in ((q_buf, qdt), (whole_buf, f32)):
+        if b is not None and (dt is None or b.dtype != dt or b.dim() != 1 or b.numel() < out_elems or b.device != dev
+                              or not b.is_contiguous()):
+            raise RcbError(f"recon_finish_ragged: an output buffer {b.dtype} {tuple(b.shape)}, expected 1-D {dt} of at least "
+                           f"{out_elems} elements on the device of y")
+    if target is not None and sse is None:
+        sse = torch.empty(n, device=dev, dtype=f64)
+    if n_bad is None:
+        n_bad = torch.empty(n, device=dev, dtype=i32)
+    n_ws = int(lib.rcb_recon_workspace_bytes(max(n, 1), per * P * Cc)) if N and P and Cc else -1
+    ws = torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8)
+    table, n_bytes = _ragged_table(n, dev)
+    _launch("rcb_recon_finish_ragged", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps, _np_ptr(sz), _np_ptr(sp),
+            int(out_elems), int(mode), int(depth), ptr(q_buf, None, True), ptr(whole_buf, f32, True), ptr(sse, f64, True),
+            ptr(n_bad, i32), ptr(ws), max(n_ws, 8), ptr(table), n_bytes)
+    return sse, n_bad
+
+
+def recon_finish_ragged(y, target=None, layout=None, sizes=None, swap=None, mode=RECON_8BIT, sample_format=None, want_int=False,
+                        want_whole=False):
+    """`recon_finish(size=)` with one size PER SIGNAL, in one call (rcb_recon_finish_ragged): y [n * per, P, C] holds n signals on
+    the grid of `layout`, sizes[k] (1 <= sizes[k][i] <= G_i) is signal k's own extent along the model's axes.
+    -> (q: list of the integer signals or None, whole: list of the fp32 signals or None, sse fp64 [n], n_bad int32 [n]).
+    Entry k of a list is a contiguous [*sizes[k], C] view into one buffer that holds all signals one after the other; with
+    swap[k] (2-D layouts only) it is delivered with axes 0 and 1 exchanged, contiguous [sizes[k][1], sizes[k][0], C]: the
+    kernel writes it along transposed strides -- a portrait signal that was coded landscape comes back portrait.
+    sse[k] / n_bad[k] count signal k's real samples only and are bitwise recon_finish(size=sizes[k])'s of that signal alone.
+    mode / sample_format / want_int / want_whole: recon_finish's.  The only host sync is the table upload."""
+    if layout is None or sizes is None:
+        raise RcbError("recon_finish_ragged: a layout and one size per signal are needed")
+    depth, qdt = 0, torch.uint8
+    if sample_format is not None:
+        mode, depth = sample_format.kind, sample_format.depth
+        qdt = sample_format.dtype if sample_format.is_integer else torch.uint8
+    sizes = [[int(v) for v in s] for s in sizes]
+    swap = [False] * len(sizes) if swap is None else [bool(v) for v in swap]
+    if len(swap) != len(sizes) or (any(swap) and len(layout.patch_nums) != 2):
+        raise RcbError("recon_finish_ragged: one swap flag per signal, and only 2-D signals can be swapped")
+    Cc = int(y.shape[-1]) if y.dim() == 3 else 1
+    spans, shapes, total = _ragged_spans(sizes, swap, Cc)
+    q_buf = torch.empty(max(total, 1), device=y.device, dtype=qdt) if want_int else None
+    whole_buf = torch.empty(max(total, 1), device=y.device, dtype=f32) if want_whole else None
+    sse, n_bad = recon_finish_ragged_into(y, target, layout, sizes, spans, total, mode, depth, q_buf, whole_buf)
+
+    def views(buf):
+        if buf is None:
+            return None
+        return [buf[sp[0]:sp[0] + int(np.prod(shp))].view(shp) for sp, shp in zip(spans, shapes)]
+    return views(q_buf), views(whole_buf), sse, n_bad
+
+
 def _win_geo(shape):
     nd = len(shape) - 2
     if nd < 1 or nd > 3 or shape[-1] % 8:

@@ -119,7 +119,7 @@ class InrGeometry:
         dd = self.data_dim
         return ops.PeLayout(self.patch_nums[:dd] if self.patch else [1] * dd, self.pixel_sizes[:dd])
 
-    def report(self, x, y, on_device=True, size=None, sample_format=None):
+    def report(self, x, y, on_device=True, size=None, sample_format=None, sizes=None):
         """TestBNNmodel (the model with `predict`, `dataset` and `_report`; it lives here because both models share this mixin):
         the distortion figure of `_report` -- an array per datapoint (cifar, protein) or one float -- without the host copy of the
         reconstruction: rounding and squared error run in rcb_recon_finish and only the per-datapoint fp64 sums come back
@@ -127,34 +127,48 @@ class InrGeometry:
         size: the signals' own extent inside this model's grid (y = patch_signals(signals, size)): the figure counts the real
         samples only, not the edge padding (rcb_recon_finish_crop); on the device only.
         sample_format (utils.SampleFormat): the lattice the reconstruction is rounded to instead of the dataset's own choice
-        (utils.metric_device); on the device only."""
+        (utils.metric_device); on the device only.
+        sizes (instead of size): one extent per signal (y = patch_signals(list, sizes=)); the figure counts each signal's real
+        samples (rcb_recon_finish_ragged); on the device only."""
         if not on_device:
-            if size is not None or sample_format is not None:
+            if size is not None or sample_format is not None or sizes is not None:
                 raise ValueError("report: the figure over a cropped extent or on a sample format's lattice is formed on the "
                                  "device only")
             return self._report(x, y)
         with torch.no_grad():
             y_pred = self.predict(x.to(self.loc.device))
+        if sizes is not None:
+            return metric_device(y, y_pred, self.dataset, self.signal_layout(), sample_format=sample_format, sizes=sizes)
         if size is not None:
             return metric_device(y, y_pred, self.dataset, self.signal_layout(), size=size, sample_format=sample_format)
         return metric_device(y, y_pred, self.dataset, self.recon_layout(), sample_format=sample_format)
 
-    def patch_signals(self, signals, size=None, sample_format=None):
+    def patch_signals(self, signals, size=None, sample_format=None, sizes=None):
         """whole signals [n, *grid, C] on the GPU (uint8 or fp32, any strides: utils.signal_view) -> the targets y [N, P, C] of
         this model's INRs, cut on the device in the row order of recon_layout (rcb_signal_patch); the inverse of the stitching
         in ops.recon_finish.  The unpatched presets are one patch per signal.
         size: the signals are [n, *size, C] with size[i] <= grid[i] and are edge-padded to the grid on the way
         (rcb_signal_patch_pad).
-        sample_format (utils.SampleFormat): how the samples are stored -- needed for 16-bit signals (ops.signal_patch)."""
+        sample_format (utils.SampleFormat): how the samples are stored -- needed for 16-bit signals (ops.signal_patch).
+        sizes (instead of size): `signals` is a LIST of tensors [*sizes[k], C] of mixed sizes and memory layouts, each edge-padded
+        to the grid in one call (ops.signal_patch_ragged)."""
+        if sizes is not None:
+            if size is not None:
+                raise ValueError("patch_signals: size and sizes exclude each other")
+            got = [tuple(int(v) for v in t.shape[:-1]) for t in signals]
+            if got != [tuple(int(v) for v in s) for s in sizes]:
+                raise ValueError("patch_signals: signals of extents %r, sizes %r" % (got, [tuple(s) for s in sizes]))
+            return ops.signal_patch_ragged(signals, self.signal_layout(), sample_format=sample_format)
         if size is not None:
             if tuple(int(v) for v in size) != tuple(signals.shape[1:-1]):
                 raise ValueError("patch_signals: signals of extent %r, size %r" % (tuple(signals.shape[1:-1]), tuple(size)))
             return ops.signal_patch_pad(signals, self.signal_layout(), sample_format=sample_format)
         return ops.signal_patch(signals, self.signal_layout(), sample_format=sample_format)
 
-    def report_signals(self, x, signals, size=None, sample_format=None):
-        """`report` against whole signals instead of patch targets"""
-        return self.report(x, self.patch_signals(signals, size, sample_format), size=size, sample_format=sample_format)
+    def report_signals(self, x, signals, size=None, sample_format=None, sizes=None):
+        """`report` against whole signals instead of patch targets (sizes: a list of signals, as patch_signals takes it)"""
+        return self.report(x, self.patch_signals(signals, size, sample_format, sizes=sizes), size=size, sample_format=sample_format,
+                           sizes=sizes)
 
 
 class PriorBNNmodel(nn.Module, InrGeometry):

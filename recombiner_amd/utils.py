@@ -322,6 +322,37 @@ def fit_config(config, size):
     return out
 
 
+def ragged_plan(config, sizes, landscape=True):
+    """How a list of signals of mixed sizes and orientations is coded (drivers.compress_signal_list): pure host arithmetic.
+    sizes[k]: signal k's extent per spatial axis, as it lies in memory.  Per signal the swap is decided -- 2-D presets with
+    `landscape`, when the first axis is longer than the second, as signal_view rotates a portrait image -- and the signals are
+    grouped into buckets by the grid that fit_config gives the (possibly swapped) size: signals share a model when they fit the
+    same patch grid.  -> (swaps: a bool per signal, buckets: a list of dicts
+        patch_nums  the fitted grid's patches per axis (ones for the unpatched presets, which have one bucket),
+        config      the fitted config,
+        indices     the signals of the bucket, in input order,
+        sizes       their extents along the model's axes (after the swap)),
+    buckets in the order of their first signal.  ValueError where fit_config raises it (an unpatched preset and a larger signal)."""
+    dd = config["data_dim"]
+    swaps, buckets, by_grid = [], [], {}
+    for k, size in enumerate(sizes):
+        size = [int(v) for v in size]
+        if len(size) != dd:
+            raise ValueError("ragged_plan: signal %d has %d axes, the preset %d" % (k, len(size), dd))
+        sw = bool(dd == 2 and landscape and size[0] > size[1])
+        if sw:
+            size = [size[1], size[0]]
+        fitted = fit_config(config, size)
+        key = tuple(preset_grid(fitted)[0])
+        if key not in by_grid:
+            by_grid[key] = dict(patch_nums=list(key), config=fitted, indices=[], sizes=[])
+            buckets.append(by_grid[key])
+        by_grid[key]["indices"].append(k)
+        by_grid[key]["sizes"].append(tuple(size))
+        swaps.append(sw)
+    return swaps, buckets
+
+
 # ---------------------------------------------------------------------------------------------
 # metrics (utils.py:200-260) -- host numpy, as in the reference
 # ---------------------------------------------------------------------------------------------
@@ -372,10 +403,21 @@ def metric_from_sse(sse, n_elems, dataset):
     kodak / video, raw mode for audio / protein) and the element count of one datapoint, all in fp64:
     cifar -> PSNR per datapoint [n_data]; kodak / video / audio -> one PSNR over the whole batch (a float); protein ->
     RMSD per datapoint, 25 * sqrt(3 * sse / n).  Where `metric` takes a float32 mean in numpy's pairwise order, this divides
-    an fp64 sum once."""
+    an fp64 sum once.
+    n_elems may be an array [n_data] of per-datapoint element counts (signals of mixed sizes, ops.recon_finish_ragged): the
+    per-datapoint figures use sse_d / n_d, the batch-wide one sum(sse) / sum(n)."""
     if dataset not in METRIC_ROUNDS:
         raise ValueError(dataset)
     sse = np.asarray(sse, dtype=np.float64).reshape(-1)
+    if np.ndim(n_elems) != 0:
+        counts = np.asarray(n_elems, dtype=np.float64).reshape(-1)
+        if counts.size != sse.size:
+            raise ValueError("metric_from_sse: %d element counts for %d datapoints" % (counts.size, sse.size))
+        if dataset == "cifar":
+            return -10.0 * np.log10(sse / counts)
+        if dataset == "protein":
+            return 25.0 * np.sqrt(3.0 * sse / counts)
+        return (-10.0 * np.log10(sse.sum() / counts.sum())).item()
     n = float(n_elems)
     if dataset == "cifar":
         return -10.0 * np.log10(sse / n)
@@ -384,7 +426,7 @@ def metric_from_sse(sse, n_elems, dataset):
     return (-10.0 * np.log10(sse.sum() / (n * sse.size))).item()
 
 
-def metric_device(y_true, y_pred, dataset, layout=None, size=None, sample_format=None):
+def metric_device(y_true, y_pred, dataset, layout=None, size=None, sample_format=None, sizes=None):
     """`metric(y_true, y_pred, dataset)` for GPU tensors [N, P, C] without copying them to the host: one pass of
     rcb_recon_finish (rounding to 8 bits where the dataset's metric does), then only the per-datapoint sums -- and the counts
     of non-finite elements, which make a datapoint's figure NaN as numpy's would be -- are read back.  layout: ops.PeLayout
@@ -394,13 +436,21 @@ def metric_device(y_true, y_pred, dataset, layout=None, size=None, sample_format
     signal are real, the rest edge padding (ops.signal_patch_pad) -- the figure is over the real samples alone
     (rcb_recon_finish_crop), the mean over prod(size) * C elements per signal.
     sample_format (SampleFormat): the lattice the reconstruction is rounded to -- it overrides the dataset's choice, so the figure is
-    the distortion of the signal a decoder delivers in that format (rcb_recon_finish_fmt); the formula stays the dataset's."""
+    the distortion of the signal a decoder delivers in that format (rcb_recon_finish_fmt); the formula stays the dataset's.
+    sizes (instead of size; needs a layout): one extent PER SIGNAL (rcb_recon_finish_ragged) -- per-datapoint figures over each
+    signal's own prod(size) * C elements, the batch-wide figure over all real samples of the batch."""
     from . import ops
     if dataset not in METRIC_ROUNDS:
         raise ValueError(dataset)
     mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
     y_pred = y_pred.detach().to(torch.float32).contiguous()
     y_true = y_true.detach().to(device=y_pred.device, dtype=torch.float32).contiguous()
+    if sizes is not None:
+        if size is not None:
+            raise ValueError("metric_device: size and sizes exclude each other")
+        _, _, sse, _n_bad = ops.recon_finish_ragged(y_pred, y_true, layout=layout, sizes=sizes, mode=mode, sample_format=sample_format)
+        counts = [int(np.prod([int(v) for v in s])) * y_pred.shape[-1] for s in sizes]
+        return metric_from_sse(sse.cpu().numpy(), np.asarray(counts), dataset)
     _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode, size=size, sample_format=sample_format)
     n_elems = y_pred.numel() // sse.numel() if size is None else int(np.prod([int(v) for v in size])) * y_pred.shape[-1]
     return metric_from_sse(sse.cpu().numpy(), n_elems, dataset)
