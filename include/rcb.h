@@ -458,7 +458,9 @@ int rcb_col_moments(const float* loc, const float* log_scale, int32_t rows, int3
  * data in an fp64 container, so it is held as fp32, TRANSPOSED: tables_t[g] -> [g][K] (candidate index contiguous).
  * tables_t and table_absmax are DEVICE arrays of max_glen + 1 entries (NULL / 0 for unused lengths); the job arrays are
  * DEVICE arrays too, so an encode round needs no host round trip.  Jobs outside the matrix, with an unknown group
- * length or a missing table are rejected on the device: idx = -1, nothing committed.
+ * length or a missing table are rejected on the device: idx = -1, nothing committed.  A job all of whose scores are NaN
+ * (a NaN in its posterior or prior row) has no arg-max: idx = -1 in both modes as well, best = (-inf, -inf), nothing
+ * committed -- the caller sees the group as not coded; the reference's torch.argmax would code it at index 0.
  *
  * mode RCB_REC_EXACT: the reference arithmetic op for op (one workgroup per job).
  * mode RCB_REC_FAST : logw as a quadratic in xi (two fp64 FMAs per candidate and element, eight jobs share every table

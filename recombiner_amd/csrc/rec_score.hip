@@ -8,6 +8,8 @@
 // Two scorers share one job description:
 //   * rec_exact_kernel -- the reference arithmetic op for op in fp64 (separate mul / add / true division), one workgroup
 //     per job.  It produces the published log-weights and is the arbiter for every job the fast scorer cannot certify.
+//     (The two sums over j run in ascending order; torch's own reduction takes another order from g = 5 on, so beyond g = 4
+//     the log-weights equal the reference's up to the roundings of that sum, not bit for bit.)
 //   * rec_fast_kernel  -- the same log-weight as a quadratic in xi,  c0 + sum_j (c1_j xi_j + c2_j xi_j^2) + gumbel,  two
 //     fp64 FMAs per (candidate, element) instead of two divisions and a dozen dependent operations; eight jobs of one group
 //     length share every table element a workgroup loads (coefficients arrive through scalar loads), 1024 candidates per
@@ -406,7 +408,7 @@ __global__ void __launch_bounds__(256) rec_exact_kernel(RecArgs a, int only_flag
       top2_load(o, &s_top[w]);
       r = top2_merge(r, o);
     }
-    idx[b] = r.i1;
+    idx[b] = (r.i1 == 0x7fffffff) ? -1 : r.i1;      // nothing was ever pushed: every score of the job is NaN
     if (best) {
       best[2 * b] = r.v1;
       best[2 * b + 1] = r.v2;
