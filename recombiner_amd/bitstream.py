@@ -34,6 +34,7 @@ rejected -- then  u8 kind | u8 depth, always present (the implied format is writ
 stream from the magic on, so a relabelled version number is caught as well; versions 1 to 3 stay byte for byte what they are.
 `decode_signal_list` is its decoder.  Rate: bpp = payload_bits / sum of prod(size) over the signals."""
 import struct
+import typing
 import zlib
 
 import numpy as np
@@ -85,44 +86,52 @@ def pack_indices(levels, bits=16, extent=None, sample_format=None, extents=None,
         raise ValueError("only 16 bits per group are defined (K = 65536 candidates, test_model.py:441-444)")
     if not 1 <= len(levels) <= 3:
         raise ValueError("1 to 3 levels expected")
-    if extents is not None:
-        if extent is not None:
-            raise ValueError("extent and extents exclude each other")
-        head = MAGIC + struct.pack("<HBB", VERSION_LIST, len(levels), bits)
-        body = b""
-        for a in levels:
-            a = np.asarray(a)
-            if a.ndim != 2:
-                raise ValueError("index arrays must be [rows, n_groups]")
-            if a.size and (a.min() < 0 or a.max() >= (1 << bits) or np.any(a != np.floor(a))):
-                raise ValueError("index out of range for %d bits" % bits)
-            head += struct.pack("<II", a.shape[0], a.shape[1])
-            body += np.ascontiguousarray(a.astype("<u2")).tobytes()
-        whole = head + _list_block(extents, swaps, sample_format) + body
-        return whole + struct.pack("<I", zlib.crc32(whole) & 0xFFFFFFFF)
-    ext = b"" if extent is None else _extent_block(extent)
-    version = VERSION if extent is None else VERSION_EXTENT
-    if sample_format is not None:
-        ext = (ext or struct.pack("<B", 0)) + _format_block(sample_format)
-        version = VERSION_FORMAT
-    head = MAGIC + struct.pack("<HBB", version, len(levels), bits)
-    body = b""
+    listed = extents is not None
+    if listed and extent is not None:
+        raise ValueError("extent and extents exclude each other")
+    if not listed:                                           # (versions 1 to 3 refuse a bad extent before a bad index array)
+        mid = b"" if extent is None else _extent_block(extent)
+        version = VERSION if extent is None else VERSION_EXTENT
+        if sample_format is not None:
+            mid = (mid or struct.pack("<B", 0)) + _format_block(sample_format)
+            version = VERSION_FORMAT
+    shapes = body = b""
     for a in levels:
         a = np.asarray(a)
         if a.ndim != 2:
             raise ValueError("index arrays must be [rows, n_groups]")
         if a.size and (a.min() < 0 or a.max() >= (1 << bits) or np.any(a != np.floor(a))):
             raise ValueError("index out of range for %d bits" % bits)
-        head += struct.pack("<II", a.shape[0], a.shape[1])
+        shapes += struct.pack("<II", a.shape[0], a.shape[1])
         body += np.ascontiguousarray(a.astype("<u2")).tobytes()
-    return head + ext + body + struct.pack("<I", zlib.crc32(ext + body) & 0xFFFFFFFF)
+    if listed:                                               # (version 4 after it)
+        mid, version = _list_block(extents, swaps, sample_format), VERSION_LIST
+    head = MAGIC + struct.pack("<HBB", version, len(levels), bits) + shapes
+    covered = head + mid + body if listed else mid + body    # version 4: the checksum covers the whole stream
+    return head + mid + body + struct.pack("<I", zlib.crc32(covered) & 0xFFFFFFFF)
+
+
+class Stream(typing.NamedTuple):
+    """A parsed and verified stream (_parse).  levels: the index arrays [rows, n_groups] as they lie in the stream (uint16 views,
+    nothing converted); extent: the tuple a version-2 or -3 stream carries, else None; sample_format: the utils.SampleFormat a
+    version-3 or -4 stream carries, else None; extents / swaps: a version-4 stream's per-signal sizes and exchange flags, else None."""
+    version: int
+    levels: list
+    extent: typing.Optional[tuple]
+    sample_format: object
+    extents: typing.Optional[list]
+    swaps: typing.Optional[list]
+
+    def indices(self):
+        return [a.astype(np.int64) for a in self.levels]
 
 
 def unpack(blob):
     """bytes (any version) -> (list of int64 arrays [rows, n_groups], extent: the tuple a version-2 or -3 stream carries, None
     for version 1 and for a version-3 stream without one); raises ValueError on a malformed or corrupted stream.  The sample
     format of a version-3 stream: unpack_header."""
-    return _unpack(blob)[:2]
+    s = _parse(blob)
+    return s.indices(), s.extent
 
 
 def unpack_header(blob):
@@ -130,70 +139,69 @@ def unpack_header(blob):
     utils.SampleFormat a version-3 or -4 stream carries (None for versions 1 and 2: the preset's implied format); a version-4
     stream adds extents / swaps, its per-signal sizes (tuples, along the model's axes) and exchange flags.
     Validates the whole stream as `unpack` does."""
-    _, extent, fmt, version, extents, swaps = _unpack(blob)
-    hdr = dict(version=version, extent=extent, sample_format=fmt)
-    if version == VERSION_LIST:
-        hdr.update(extents=extents, swaps=swaps)
-    return hdr
+    s = _parse(blob)
+    names = ("version", "extent", "sample_format") + (("extents", "swaps") if s.version == VERSION_LIST else ())
+    return {k: getattr(s, k) for k in names}
 
 
-def _unpack(blob):
+class _Cursor:
+    """reads the header's fields in order; a field that the stream is too short for is a truncated header"""
+
+    def __init__(self, blob, off):
+        self.blob, self.off = blob, off
+
+    def need(self, n_bytes):
+        if self.off + n_bytes > len(self.blob):
+            raise ValueError("truncated header")
+
+    def take(self, fmt):
+        self.need(struct.calcsize(fmt))
+        out = struct.unpack_from(fmt, self.blob, self.off)
+        self.off += struct.calcsize(fmt)
+        return out
+
+
+def _parse(blob):
+    """bytes (any version) -> Stream; ValueError on a malformed or corrupted stream.  Every public function parses its stream once."""
     if len(blob) < 12 or blob[:4] != MAGIC:
         raise ValueError("not an RCB1 bitstream")
     version, n_levels, bits = struct.unpack_from("<HBB", blob, 4)
     if version not in (VERSION, VERSION_EXTENT, VERSION_FORMAT, VERSION_LIST) or bits != 16 or not 1 <= n_levels <= 3:
         raise ValueError("unsupported bitstream header (version %d, %d levels, %d bits)" % (version, n_levels, bits))
-    off = 8
-    shapes = []
-    for _ in range(n_levels):
-        if off + 8 > len(blob):
-            raise ValueError("truncated header")
-        shapes.append(struct.unpack_from("<II", blob, off))
-        off += 8
-    start, extent, fmt, extents, swaps = off, None, None, None, None
+    cur = _Cursor(blob, 8)
+    shapes = [cur.take("<II") for _ in range(n_levels)]
+    start, extent, fmt, extents, swaps = cur.off, None, None, None, None
     if version == VERSION_LIST:
-        if off + 5 > len(blob):
-            raise ValueError("truncated header")
-        nd, n_sig = struct.unpack_from("<BI", blob, off)
+        nd, n_sig = cur.take("<BI")
         if not 1 <= nd <= 3 or n_sig < 1:
             raise ValueError("unsupported bitstream header (%d signals of %d axes)" % (n_sig, nd))
-        off += 5
-        if off + n_sig * (4 * nd + 1) > len(blob):
-            raise ValueError("truncated header")
+        cur.need(n_sig * (4 * nd + 1))
         extents, swaps = [], []
         for _ in range(n_sig):
-            size = tuple(int(v) for v in struct.unpack_from("<%dI" % nd, blob, off))
-            flags = blob[off + 4 * nd]
+            *size, flags = (int(v) for v in cur.take("<%dIB" % nd))
             if min(size) < 1:
-                raise ValueError("bitstream extent %r has an empty axis" % (size,))
+                raise ValueError("bitstream extent %r has an empty axis" % (tuple(size),))
             if flags & ~1 or (flags and nd != 2):
                 raise ValueError("unsupported bitstream header (signal flags 0x%02x for %d axes)" % (flags, nd))
-            extents.append(size)
+            extents.append(tuple(size))
             swaps.append(bool(flags & 1))
-            off += 4 * nd + 1
         start = 0                                            # the checksum covers the whole stream
     if version in (VERSION_EXTENT, VERSION_FORMAT):
-        if off + 1 > len(blob):
-            raise ValueError("truncated header")
-        nd = blob[off]
+        (nd,) = cur.take("<B")
         if not (0 if version == VERSION_FORMAT else 1) <= nd <= 3:
             raise ValueError("unsupported bitstream header (an extent of %d axes)" % nd)
-        if off + 1 + 4 * nd > len(blob):
-            raise ValueError("truncated header")
         if nd:
-            extent = tuple(int(v) for v in struct.unpack_from("<%dI" % nd, blob, off + 1))
+            extent = tuple(int(v) for v in cur.take("<%dI" % nd))
             if min(extent) < 1:
                 raise ValueError("bitstream extent %r has an empty axis" % (extent,))
-        off += 1 + 4 * nd
     if version in (VERSION_FORMAT, VERSION_LIST):
-        if off + 2 > len(blob):
-            raise ValueError("truncated header")
         from .utils import SampleFormat
+        kind, depth = cur.take("<BB")
         try:
-            fmt = SampleFormat(int(blob[off]), int(blob[off + 1]))
+            fmt = SampleFormat(kind, depth)
         except ValueError as e:
             raise ValueError("unsupported bitstream header (%s)" % e) from None
-        off += 2
+    off = cur.off
     n_bytes = sum(r * g for r, g in shapes) * 2
     if len(blob) != off + n_bytes + 4:
         raise ValueError("bitstream length %d does not match its header (%d expected)" % (len(blob), off + n_bytes + 4))
@@ -201,21 +209,21 @@ def _unpack(blob):
     (crc,) = struct.unpack_from("<I", blob, off + n_bytes)
     if zlib.crc32(blob[start:off + n_bytes]) & 0xFFFFFFFF != crc:
         raise ValueError("bitstream checksum mismatch")
-    out, p = [], 0
+    levels, p = [], 0
     for r, g in shapes:
-        out.append(np.frombuffer(body, dtype="<u2", count=r * g, offset=p).reshape(r, g).astype(np.int64))
+        levels.append(np.frombuffer(body, dtype="<u2", count=r * g, offset=p).reshape(r, g))
         p += r * g * 2
-    return out, extent, fmt, version, extents, swaps
+    return Stream(version, levels, extent, fmt, extents, swaps)
 
 
 def unpack_indices(blob):
-    """bytes (either version) -> list of int64 arrays [rows, n_groups]; raises ValueError on a malformed or corrupted stream."""
-    return unpack(blob)[0]
+    """bytes (any version) -> list of int64 arrays [rows, n_groups]; raises ValueError on a malformed or corrupted stream."""
+    return _parse(blob).indices()
 
 
 def payload_bits(blob):
     """bits spent on indices (what bpp is computed from; header and checksum are per-file constants)."""
-    return sum(a.size for a in unpack_indices(blob)) * 16
+    return sum(a.size for a in _parse(blob).levels) * 16
 
 
 def _levels_of(model):
@@ -229,17 +237,12 @@ def encode(model, extent=None, sample_format=None, extents=None, swaps=None):
     carries it; None or the implied format changes nothing.
     extents (one size per signal, along the model's axes; swaps: one flag per signal, default none): a version-4 stream, which
     always carries a format -- sample_format, or the implied one written out (decode_signal_list)."""
+    from .utils import SampleFormat
     if extents is not None:
-        from .utils import SampleFormat
+        extent = None                                        # (ignored beside extents, as ever)
         if sample_format is None:
             sample_format = SampleFormat.implied(model.dataset)
-        lvls = _levels_of(model)
-        for lv in lvls:
-            if not lv.mask_groupwise.all():
-                raise ValueError("level %r has %d groups that are not encoded yet" % (lv.pre, int((~lv.mask_groupwise).sum())))
-        return pack_indices([lv.idx_groupwise for lv in lvls], extents=extents, swaps=swaps, sample_format=sample_format)
-    if sample_format is not None:
-        from .utils import SampleFormat
+    elif sample_format is not None:
         if not isinstance(sample_format, SampleFormat):
             raise ValueError("sample_format %r: a utils.SampleFormat expected" % (sample_format,))
         if sample_format == SampleFormat.implied(model.dataset):
@@ -248,7 +251,7 @@ def encode(model, extent=None, sample_format=None, extents=None, swaps=None):
     for lv in lvls:
         if not lv.mask_groupwise.all():
             raise ValueError("level %r has %d groups that are not encoded yet" % (lv.pre, int((~lv.mask_groupwise).sum())))
-    return pack_indices([lv.idx_groupwise for lv in lvls], extent=extent, sample_format=sample_format)
+    return pack_indices([lv.idx_groupwise for lv in lvls], extent=extent, sample_format=sample_format, extents=extents, swaps=swaps)
 
 
 def apply_indices(model, levels):
@@ -277,9 +280,9 @@ def apply_indices(model, levels):
                        enc_sample=lv.sample, enc_mask=lv.mask, done=lv.d_done, beta=lv.kl_beta, idx_groupwise=lv.d_idx)
 
 
-def _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision):
+def _decode_patches(config, dataset, checkpoint, stream, x, n_datapoints, device, seed, precision):
     from .drivers import build_test_model
-    levels = unpack_indices(blob)
+    levels = stream.indices()
     if levels[0].shape[0] != n_datapoints:
         raise ValueError("bitstream holds %d rows, %d datapoints requested" % (levels[0].shape[0], n_datapoints))
     model = build_test_model(config, dataset, checkpoint, n_datapoints, device, seed)
@@ -292,25 +295,31 @@ def _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, 
         return model, model.predict(x.to(device))
 
 
-def _stream_format(blob, dataset, sample_format, as_int):
-    """the format the decoder rounds to: the one a version-3 stream carries, else `sample_format` (a version-1 / -2 stream whose
-    caller knows it), else None -- the preset's implied format, through the code paths of versions 1 and 2.  ValueError when the
-    two disagree, or when integers are asked of a format that has none."""
+def _try_parse(blob):
+    """-> (Stream, None), or (None, the ValueError) for a decoder that has an older refusal to state first (_stream_format)"""
+    try:
+        return _parse(blob), None
+    except ValueError as e:
+        return None, e
+
+
+def _stream_format(stream, error, dataset, sample_format, as_int):
+    """the format the decoder rounds to: the one a version-3 or -4 stream carries, else `sample_format` (a version-1 / -2 stream
+    whose caller knows it), else None -- the preset's implied format, through the code paths of versions 1 and 2.  ValueError when
+    the two disagree, or when integers are asked of a format that has none.  stream None: the bytes did not parse, and `error`
+    says why -- after the refusal that is older than the parser's."""
     from .utils import METRIC_ROUNDS
     if dataset not in METRIC_ROUNDS:
         raise ValueError(dataset)
-    try:
-        fmt = unpack_header(blob)["sample_format"]
-    except ValueError:
-        if as_int and sample_format is None and not METRIC_ROUNDS[dataset]:
-            fmt = None                                       # (the older refusal below comes first, as it always did)
-        else:
-            raise
+    no_8bit = ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+    if stream is None:
+        raise no_8bit if as_int and sample_format is None and not METRIC_ROUNDS[dataset] else error
+    fmt = stream.sample_format
     if fmt is not None and sample_format is not None and fmt != sample_format:
         raise ValueError("the bitstream carries %r, sample_format says %r" % (fmt, sample_format))
     fmt = fmt if fmt is not None else sample_format
     if fmt is None and as_int and not METRIC_ROUNDS[dataset]:
-        raise ValueError("%s signals have no 8-bit form (their metric does not round): decode them as fp32" % dataset)
+        raise no_8bit
     if fmt is not None and as_int and not fmt.is_integer:
         raise ValueError("%r has no integer form: decode it as fp32" % (fmt,))
     return fmt
@@ -338,20 +347,21 @@ def decode(config, dataset, checkpoint, blob, x, n_datapoints, device="cuda", se
     A version-3 stream likewise: the reconstruction [N, P, C] is not rounded at all; as_uint8 (alias: as_integer) gives the
     integers of the stream's format in its dtype (sample_format: the format of a version-1 / -2 stream, as decode_signal's)."""
     if as_uint8 or as_integer:
-        return _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, True, sample_format)
-    return _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision)[1]
+        stream, error = _try_parse(blob)
+        fmt = _stream_format(stream, error, dataset, sample_format, True)
+        return _decode_grid(config, dataset, checkpoint, stream, x, n_datapoints, device, seed, precision, True, fmt)
+    return _decode_patches(config, dataset, checkpoint, _parse(blob), x, n_datapoints, device, seed, precision)[1]
 
 
-def _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8, sample_format=None):
+def _decode_grid(config, dataset, checkpoint, stream, x, n_datapoints, device, seed, precision, as_int, fmt):
     # the whole GRID of `config`, for any version: `decode` is the patch-level decoder -- its caller names the (fitted) config
     # and the number of patches, and knows what the grid holds
-    fmt = _stream_format(blob, dataset, sample_format, as_uint8)
-    model, y = _decode_patches(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision)
-    return _finish(y, dataset, fmt, as_uint8, model.recon_layout())
+    model, y = _decode_patches(config, dataset, checkpoint, stream, x, n_datapoints, device, seed, precision)
+    return _finish(y, dataset, fmt, as_int, model.recon_layout())
 
 
-def _refuse_list(blob, who):
-    if len(blob) >= 6 and blob[:4] == MAGIC and struct.unpack_from("<H", blob, 4)[0] == VERSION_LIST:
+def _refuse_list(stream, who):
+    if stream is not None and stream.version == VERSION_LIST:
         raise ValueError("%s: a version-4 bitstream holds signals of their own sizes and orientations -- decode it with "
                          "decode_signal_list" % who)
 
@@ -367,13 +377,13 @@ def decode_signal(config, dataset, checkpoint, blob, x, n_datapoints, device="cu
     own; ValueError when they disagree): fp32 on the format's lattice, or with as_uint8 (alias: as_integer) the integers in
     the format's dtype -- uint16 for u16, int16 for s16."""
     as_uint8 = as_uint8 or as_integer
-    _refuse_list(blob, "decode_signal")
-    fmt = _stream_format(blob, dataset, sample_format, as_uint8)
-    extent = unpack(blob)[1]
-    if extent is not None:
+    stream, error = _try_parse(blob)
+    _refuse_list(stream, "decode_signal")
+    fmt = _stream_format(stream, error, dataset, sample_format, as_uint8)
+    if stream.extent is not None:
         raise ValueError("a version-2 bitstream: its signals of size %r were edge-padded to the model's grid -- decode them with "
-                         "decode_signal_any, which crops back (this decoder would return the padding)" % (extent,))
-    return _decode_grid(config, dataset, checkpoint, blob, x, n_datapoints, device, seed, precision, as_uint8, fmt)
+                         "decode_signal_any, which crops back (this decoder would return the padding)" % (stream.extent,))
+    return _decode_grid(config, dataset, checkpoint, stream, x, n_datapoints, device, seed, precision, as_uint8, fmt)
 
 
 def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42, precision=0, as_uint8=False, as_integer=False):
@@ -387,9 +397,10 @@ def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42,
     from . import ops
     from .utils import fit_config, preset_grid
     as_uint8 = as_uint8 or as_integer
-    _refuse_list(blob, "decode_signal_any")
-    fmt = _stream_format(blob, dataset, None, as_uint8)
-    levels, extent = unpack(blob)
+    stream, error = _try_parse(blob)
+    _refuse_list(stream, "decode_signal_any")
+    fmt = _stream_format(stream, error, dataset, None, as_uint8)
+    extent = stream.extent
     if extent is None:
         raise ValueError("a version-1 bitstream carries no signal size: decode it with decode_signal")
     if len(extent) != config["data_dim"]:
@@ -397,10 +408,10 @@ def decode_signal_any(config, dataset, checkpoint, blob, device="cuda", seed=42,
     fitted = fit_config(config, extent)
     pn, ps = preset_grid(fitted)
     per = int(np.prod(pn))
-    rows = int(levels[0].shape[0])
+    rows = int(stream.levels[0].shape[0])
     if rows == 0 or rows % per:
         raise ValueError("bitstream holds %d rows, signals of size %r take %d patches each" % (rows, extent, per))
-    _, y = _decode_patches(fitted, dataset, checkpoint, blob, None, rows, device, seed, precision)
+    _, y = _decode_patches(fitted, dataset, checkpoint, stream, None, rows, device, seed, precision)
     return _finish(y, dataset, fmt, as_uint8, ops.PeLayout(pn, ps), size=extent)
 
 
@@ -414,12 +425,12 @@ def decode_signal_list(config, dataset, checkpoint, blob, device="cuda", seed=42
     for f32, which has none)."""
     from . import ops
     from .utils import fit_config, preset_grid
-    hdr = unpack_header(blob)
-    if hdr["version"] != VERSION_LIST:
+    stream = _parse(blob)
+    if stream.version != VERSION_LIST:
         raise ValueError("decode_signal_list: a version-%d bitstream -- decode it with decode_signal / decode_signal_any"
-                         % hdr["version"])
-    fmt = _stream_format(blob, dataset, None, as_integer)
-    extents, swaps = hdr["extents"], hdr["swaps"]
+                         % stream.version)
+    fmt = _stream_format(stream, None, dataset, None, as_integer)
+    extents, swaps = stream.extents, stream.swaps
     dd = config["data_dim"]
     if len(extents[0]) != dd:
         raise ValueError("bitstream extents of %d axes for a %d-D preset" % (len(extents[0]), dd))
@@ -429,10 +440,10 @@ def decode_signal_list(config, dataset, checkpoint, blob, device="cuda", seed=42
         if preset_grid(fit_config(config, size))[0] != pn:
             raise ValueError("bitstream extents %r and %r do not fit one grid of the preset" % (extents[0], size))
     per = int(np.prod(pn))
-    rows = int(unpack_indices(blob)[0].shape[0])
+    rows = int(stream.levels[0].shape[0])
     if rows != len(extents) * per:
         raise ValueError("bitstream holds %d rows, %d signals take %d patches each" % (rows, len(extents), per))
-    _, y = _decode_patches(fitted, dataset, checkpoint, blob, None, rows, device, seed, precision)
+    _, y = _decode_patches(fitted, dataset, checkpoint, stream, None, rows, device, seed, precision)
     q, whole, _, _ = ops.recon_finish_ragged(y.to(torch.float32).contiguous(), layout=ops.PeLayout(pn, ps), sizes=extents,
                                              swap=swaps, sample_format=fmt, want_int=as_integer, want_whole=not as_integer)
     return q if as_integer else whole

@@ -319,23 +319,19 @@ extern "C" int64_t rcb_recon_workspace_bytes(int64_t n_data, int64_t elems_per_d
   return n_data * n_chunks * (int64_t)(sizeof(double) + sizeof(int));
 }
 
-template <bool W16>
-static void launch_finish(bool vec, bool crop, unsigned blocks, hipStream_t st, const float* y, const float* target, uint8_t* u8,
-                          float* whole, double* part_sse, int* part_bad, const ReconGeo& x) {
-  if (!crop) {
-    if (vec) recon_kernel<true, false, W16, false><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, nullptr);
-    else recon_kernel<false, false, W16, false><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, nullptr);
-  } else {
-    if (vec) recon_kernel<true, true, W16, false><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, nullptr);
-    else recon_kernel<false, true, W16, false><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, nullptr);
-  }
+// THE dispatcher: the kernel of an entry -- by-value uncropped (neither), by-value cropped (crop) or per-signal (rag, which is
+// cropped) -- for 8-bit / raw or 16-bit words (w16), with or without whole quads (vec)
+using ReconKernel = void (*)(const float*, const float*, uint8_t*, float*, double*, int*, ReconGeo, const RaggedRow*);
+
+template <bool CROP, bool W16, bool RAG>
+static ReconKernel recon_kernel_of(bool vec) {
+  return vec ? recon_kernel<true, CROP, W16, RAG> : recon_kernel<false, CROP, W16, RAG>;
 }
 
-template <bool W16>
-static void launch_ragged(bool vec, unsigned blocks, hipStream_t st, const float* y, const float* target, uint8_t* u8, float* whole,
-                          double* part_sse, int* part_bad, const ReconGeo& x, const RaggedRow* table) {
-  if (vec) recon_kernel<true, true, W16, true><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, table);
-  else recon_kernel<false, true, W16, true><<<blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse, part_bad, x, table);
+static ReconKernel recon_kernel_of(bool vec, bool crop, bool w16, bool rag) {
+  if (rag) return w16 ? recon_kernel_of<true, true, true>(vec) : recon_kernel_of<true, false, true>(vec);
+  if (w16) return !crop ? recon_kernel_of<false, true, false>(vec) : recon_kernel_of<true, true, false>(vec);
+  return !crop ? recon_kernel_of<false, false, false>(vec) : recon_kernel_of<true, false, false>(vec);
 }
 
 // rcb_recon_finish_ragged: the caller's tables and the device buffer their copy goes to (null `sizes` .. for the other entries)
@@ -436,7 +432,12 @@ static int finish_entry(const char* who, bool fmt, const float* y, const float* 
   double* part_sse = static_cast<double*>(workspace);
   int* part_bad = reinterpret_cast<int*>(part_sse + blocks);
   hipStream_t st = (hipStream_t)stream;
-  bool vec;
+  // the 16-byte loads need only the inputs aligned; where the outputs are cropped the stores go by quad (vec_out), the cropped
+  // rows seldom being multiples of 4 -- uncropped, a quad of the outputs is a quad of the inputs and vec covers both
+  bool vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16));
+  const bool out_aligned = (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, q_align));
+  const RaggedRow* table = nullptr;
+  x.vec_out = 0, x.Ec = 0;
   if (rag) {
     RCB_REQUIRE(rag->sizes && rag->spans && rag->table, RCB_ERR_ARG, "%s: null sizes, spans or table", who);
     const int64_t tb = rcb_ragged_table_bytes(n_data);
@@ -448,31 +449,16 @@ static int finish_entry(const char* who, bool fmt, const float* y, const float* 
     if (const int err = ragged_rows(who, n_data, nd, g, channels, 1, rag->sizes, rag->spans, rows.data(), reach.data())) return err;
     if (const int err = ragged_spans(who, rows, channels, rag->out_elems)) return err;
     if (const int err = ragged_upload(who, rows.data(), n_data, rag->table, st)) return err;
-    x.Ec = 0;
-    vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16));
-    x.vec_out = (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, q_align));
-    const RaggedRow* table = static_cast<const RaggedRow*>(rag->table);
-    if (w16) launch_ragged<true>(vec, (unsigned)blocks, st, y, target, u8, whole, part_sse, part_bad, x, table);
-    else launch_ragged<false>(vec, (unsigned)blocks, st, y, target, u8, whole, part_sse, part_bad, x, table);
-    RCB_LAUNCH_CHECK();
-    if (sse || n_bad) {
-      recon_reduce_kernel<<<(unsigned)n_data, kThreads, 0, st>>>(part_sse, part_bad, g.n_chunks, sse, n_bad);
-      RCB_LAUNCH_CHECK();
-    }
-    return RCB_OK;
-  }
-  if (!size) {
-    x.vec_out = 0, x.Ec = 0;
-    vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16)) && (!whole || aligned(whole, 16)) &&
-          (!u8 || aligned(u8, q_align));
-  } else {
-    // the 16-byte loads need only the inputs aligned; the stores go by quad (vec_out), the cropped rows seldom being multiples of 4
+    x.vec_out = out_aligned;                                 // (the rest is the row's kRaggedQuad)
+    table = static_cast<const RaggedRow*>(rag->table);
+  } else if (size) {
     x.Ec = (long long)g.sz[0] * g.sz[1] * g.L;               // (L <= E: the products fit)
-    vec = g.R % 4 == 0 && aligned(y, 16) && (!target || aligned(target, 16));
-    x.vec_out = g.L % 4 == 0 && (!whole || aligned(whole, 16)) && (!u8 || aligned(u8, q_align));
+    x.vec_out = g.L % 4 == 0 && out_aligned;
+  } else {
+    vec = vec && out_aligned;
   }
-  if (w16) launch_finish<true>(vec, size != nullptr, (unsigned)blocks, st, y, target, u8, whole, part_sse, part_bad, x);
-  else launch_finish<false>(vec, size != nullptr, (unsigned)blocks, st, y, target, u8, whole, part_sse, part_bad, x);
+  recon_kernel_of(vec, size || rag, w16, rag != nullptr)<<<(unsigned)blocks, kThreads, 0, st>>>(y, target, u8, whole, part_sse,
+                                                                                                part_bad, x, table);
   RCB_LAUNCH_CHECK();
   if (sse || n_bad) {
     recon_reduce_kernel<<<(unsigned)n_data, kThreads, 0, st>>>(part_sse, part_bad, g.n_chunks, sse, n_bad);

@@ -128,22 +128,49 @@ __global__ void __launch_bounds__(kThreads) signal_patch_kernel(const void* __re
   }
 }
 
-template <int KIND>
-void launch_patch(bool vec, bool pad, unsigned blocks, hipStream_t st, const void* src, unsigned* yo, const SignalGeo& x) {
-  if (!pad) {
-    if (vec) signal_patch_kernel<KIND, true, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x, nullptr);
-    else signal_patch_kernel<KIND, false, false, false><<<blocks, kThreads, 0, st>>>(src, yo, x, nullptr);
+// THE dispatcher: the kernel of an entry -- by-value on the whole grid (neither), by-value padded (pad) or per-signal (rag, which
+// is padded) -- for a source kind, with or without whole quads of y (vec)
+using PatchKernel = void (*)(const void*, unsigned*, SignalGeo, const RaggedRow*);
+
+template <int KIND, bool RAG>
+PatchKernel patch_kernel_of(bool vec, bool pad) {
+  if constexpr (RAG) {
+    return vec ? signal_patch_kernel<KIND, true, true, true> : signal_patch_kernel<KIND, false, true, true>;
   } else {
-    if (vec) signal_patch_kernel<KIND, true, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x, nullptr);
-    else signal_patch_kernel<KIND, false, true, false><<<blocks, kThreads, 0, st>>>(src, yo, x, nullptr);
+    if (!pad) return vec ? signal_patch_kernel<KIND, true, false, false> : signal_patch_kernel<KIND, false, false, false>;
+    return vec ? signal_patch_kernel<KIND, true, true, false> : signal_patch_kernel<KIND, false, true, false>;
   }
 }
 
-// all entries: `size` null is the uncropped form (every axis has its G_i positions); `fmt`: rcb_signal_patch_fmt, which alone takes
-// the 16-bit kinds and a depth
+template <bool RAG>
+PatchKernel patch_kernel_of(int kind, bool vec, bool pad) {
+  switch (kind) {
+    case 0: return patch_kernel_of<0, RAG>(vec, pad);
+    case 1: return patch_kernel_of<1, RAG>(vec, pad);
+    case 2: return patch_kernel_of<2, RAG>(vec, pad);
+    default: return patch_kernel_of<3, RAG>(vec, pad);
+  }
+}
+
+PatchKernel patch_kernel_of(int kind, bool vec, bool pad, bool rag) {
+  return !rag ? patch_kernel_of<false>(kind, vec, pad) : patch_kernel_of<true>(kind, vec, pad);
+}
+
+// rcb_signal_patch_ragged: the caller's tables, the reach of the source and the device buffer the tables' copy goes to
+struct RaggedArgs {
+  int64_t src_elems;
+  const int32_t* sizes;
+  const int64_t* spans;
+  void* table;
+  int64_t table_bytes;
+};
+
+// all entries: `size` null is the uncropped form (every axis has its G_i positions); `fmt`: rcb_signal_patch_fmt, which alone of the
+// by-value entries takes the 16-bit kinds and a depth; `rag`: rcb_signal_patch_ragged (fmt, size / data_stride / axis_stride unused:
+// the extents and the strides are per signal) -- its refusals in its own words where they always differed
 int patch_entry(const char* who, bool fmt, const void* src, int32_t src_kind, int32_t depth, int64_t n_data, int32_t nd,
                 const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, int32_t channels, int64_t data_stride,
-                const int64_t* axis_stride, int64_t channel_stride, float* y, rcb_stream_t stream) {
+                const int64_t* axis_stride, int64_t channel_stride, float* y, rcb_stream_t stream, const RaggedArgs* rag = nullptr) {
   if (fmt) {
     RCB_REQUIRE(src_kind >= 0 && src_kind <= 3, RCB_ERR_ARG, "%s: source kind %d (0 = uint8, 1 = fp32, 2 = u16, 3 = s16)", who,
                 src_kind);
@@ -153,51 +180,65 @@ int patch_entry(const char* who, bool fmt, const void* src, int32_t src_kind, in
     RCB_REQUIRE(src_kind == 0 || src_kind == 1, RCB_ERR_ARG, "%s: source kind %d (0 = uint8, 1 = fp32)", who, src_kind);
   }
   RCB_REQUIRE(nd >= 1 && nd <= 3, RCB_ERR_UNSUPPORTED, "%s: %d grid dimensions (1 .. 3)", who, nd);
-  RCB_REQUIRE(patch_nums && patch_size && axis_stride, RCB_ERR_ARG, "%s: null patch geometry or strides", who);
+  if (rag) RCB_REQUIRE(patch_nums && patch_size, RCB_ERR_ARG, "%s: null patch geometry", who);
+  else RCB_REQUIRE(patch_nums && patch_size && axis_stride, RCB_ERR_ARG, "%s: null patch geometry or strides", who);
   RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "%s: %d channels (1 .. 32)", who, channels);
   RCB_REQUIRE(n_data >= 0, RCB_ERR_SHAPE, "%s: %lld signals", who, (long long)n_data);
   SignalGeo x;
   PatchGeo& g = x.g;
   long long per, P;
-  if (const int err = grid_axes(who, nd, patch_nums, patch_size, size, axis_stride, g, per, P)) return err;
-  RCB_REQUIRE(data_stride >= 0 && channel_stride >= 0, RCB_ERR_ARG, "%s: negative stride (signal %lld, channel %lld)", who,
-              (long long)data_stride, (long long)channel_stride);
+  const int64_t no_stride[3] = {0, 0, 0};                    // (rag: selects the per-signal wording of the 2^31 limit)
+  if (const int err = grid_axes(who, nd, patch_nums, patch_size, size, rag ? no_stride : axis_stride, g, per, P)) return err;
+  if (rag) RCB_REQUIRE(channel_stride >= 0, RCB_ERR_ARG, "%s: negative channel stride %lld", who, (long long)channel_stride);
+  else RCB_REQUIRE(data_stride >= 0 && channel_stride >= 0, RCB_ERR_ARG, "%s: negative stride (signal %lld, channel %lld)", who,
+                   (long long)data_stride, (long long)channel_stride);
   const long long E = per * P * channels;
   RCB_REQUIRE(E <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED, "%s: %lld elements per signal (up to 2^31 - 1)", who, E);
   if (n_data == 0) return RCB_OK;
   RCB_REQUIRE(src && y, RCB_ERR_ARG, "%s: null src or y", who);
+  if (rag) {
+    RCB_REQUIRE(rag->sizes && rag->spans && rag->table, RCB_ERR_ARG, "%s: null sizes, spans or table", who);
+    const int64_t need = rcb_ragged_table_bytes(n_data);
+    RCB_REQUIRE(need > 0 && rag->table_bytes >= need && aligned(rag->table, 8), RCB_ERR_SHAPE,
+                "%s: table of %lld bytes (8-byte aligned), %lld needed", who, (long long)rag->table_bytes, (long long)need);
+  }
   grid_elems(g, channels, E);
-  x.ds = data_stride;
+  x.ds = rag ? 0 : data_stride;
   x.cs = channel_stride;
   x.m = src_kind == 2 ? (float)((1 << depth) - 1) : 0.0f;
-  for (int i = 0; i < 3; ++i) x.as[i] = i < 3 - nd ? 0 : axis_stride[i - (3 - nd)];
+  for (int i = 0; i < 3; ++i) x.as[i] = rag || i < 3 - nd ? 0 : axis_stride[i - (3 - nd)];
   RCB_REQUIRE(n_data <= 0x7fffffffLL / g.n_chunks, RCB_ERR_UNSUPPORTED,
               "%s: %lld signals of %lld elements need more than 2^31 - 1 workgroups", who, (long long)n_data, E);
+  hipStream_t st = (hipStream_t)stream;
+  const uintptr_t esize = src_kind == 0 ? 1 : src_kind == 1 ? 4 : 2;
   // the 16-byte path (of y; the source quad is 4, 8 or 16 bytes): channel-last, dense last axis, and every run start -- base,
   // signal, outer positions; b2 * R by R % 4 -- a multiple of 4 elements (a stride only counts where its index can be non-zero: an
   // axis of more than one position)
-  bool vec = (channels == 1 || channel_stride == 1) && (g.sz[2] == 1 || x.as[2] == channels) && g.R % 4 == 0 &&
-             aligned(y, 16) && aligned(src, src_kind == 0 ? 4 : src_kind == 1 ? 16 : 8);
-  vec = vec && (n_data == 1 || data_stride % 4 == 0);
-  for (int i = 0; i < 2; ++i) vec = vec && (g.sz[i] == 1 || x.as[i] % 4 == 0);
-  const unsigned blocks = (unsigned)(n_data * g.n_chunks);
-  unsigned* yo = reinterpret_cast<unsigned*>(y);
-  hipStream_t st = (hipStream_t)stream;
-  switch (src_kind) {
-    case 0: launch_patch<0>(vec, size != nullptr, blocks, st, src, yo, x); break;
-    case 1: launch_patch<1>(vec, size != nullptr, blocks, st, src, yo, x); break;
-    case 2: launch_patch<2>(vec, size != nullptr, blocks, st, src, yo, x); break;
-    default: launch_patch<3>(vec, size != nullptr, blocks, st, src, yo, x); break;
+  bool vec = g.R % 4 == 0 && aligned(y, 16);                 // y takes whole quads (E % 4 == 0 by R % 4 == 0)
+  if (rag) {                                                 // ... decided per signal, on its strides and its first element's address
+    std::vector<RaggedRow> rows((size_t)n_data);
+    std::vector<long long> reach((size_t)n_data);
+    if (const int err = ragged_rows(who, n_data, nd, g, channels, channel_stride, rag->sizes, rag->spans, rows.data(), reach.data()))
+      return err;
+    for (long long d = 0; d < n_data; ++d) {
+      RaggedRow& r = rows[(size_t)d];
+      RCB_REQUIRE(reach[(size_t)d] < rag->src_elems, RCB_ERR_SHAPE, "%s: signal %lld reaches element %lld of a source of %lld", who,
+                  d, reach[(size_t)d], (long long)rag->src_elems);
+      bool quad = (channels == 1 || channel_stride == 1) && (r.sz[2] == 1 || r.as[2] == channels) &&
+                  ((uintptr_t)src + (uintptr_t)r.off * esize) % (4 * esize) == 0;
+      for (int i = 0; i < 2; ++i) quad = quad && (r.sz[i] == 1 || r.as[i] % 4 == 0);
+      r.flags = quad ? kRaggedQuad : 0;
+    }
+    if (const int err = ragged_upload(who, rows.data(), n_data, rag->table, st)) return err;
+  } else {
+    vec = vec && (channels == 1 || channel_stride == 1) && (g.sz[2] == 1 || x.as[2] == channels) && aligned(src, 4 * esize) &&
+          (n_data == 1 || data_stride % 4 == 0);
+    for (int i = 0; i < 2; ++i) vec = vec && (g.sz[i] == 1 || x.as[i] % 4 == 0);
   }
+  patch_kernel_of(src_kind, vec, size != nullptr, rag != nullptr)<<<(unsigned)(n_data * g.n_chunks), kThreads, 0, st>>>(
+      src, reinterpret_cast<unsigned*>(y), x, rag ? static_cast<const RaggedRow*>(rag->table) : nullptr);
   RCB_LAUNCH_CHECK();
   return RCB_OK;
-}
-
-template <int KIND>
-void launch_ragged(bool vec, unsigned blocks, hipStream_t st, const void* src, unsigned* yo, const SignalGeo& x,
-                   const RaggedRow* table) {
-  if (vec) signal_patch_kernel<KIND, true, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x, table);
-  else signal_patch_kernel<KIND, false, true, true><<<blocks, kThreads, 0, st>>>(src, yo, x, table);
 }
 
 }  // namespace
@@ -211,63 +252,9 @@ extern "C" int rcb_signal_patch_ragged(const void* src, int64_t src_elems, int32
                                        int32_t nd, const int32_t* patch_nums, const int32_t* patch_size, const int32_t* sizes,
                                        const int64_t* spans, int32_t channels, int64_t channel_stride, float* y, void* table,
                                        int64_t table_bytes, rcb_stream_t stream) {
-  const char* who = "signal_patch_ragged";
-  RCB_REQUIRE(src_kind >= 0 && src_kind <= 3, RCB_ERR_ARG, "%s: source kind %d (0 = uint8, 1 = fp32, 2 = u16, 3 = s16)", who, src_kind);
-  RCB_REQUIRE(src_kind == 2 ? (depth >= 9 && depth <= 16) : depth == 0, RCB_ERR_ARG,
-              "%s: depth %d for source kind %d (9 .. 16 for u16, 0 for the others)", who, depth, src_kind);
-  RCB_REQUIRE(nd >= 1 && nd <= 3, RCB_ERR_UNSUPPORTED, "%s: %d grid dimensions (1 .. 3)", who, nd);
-  RCB_REQUIRE(patch_nums && patch_size, RCB_ERR_ARG, "%s: null patch geometry", who);
-  RCB_REQUIRE(channels >= 1 && channels <= 32, RCB_ERR_SHAPE, "%s: %d channels (1 .. 32)", who, channels);
-  RCB_REQUIRE(n_data >= 0, RCB_ERR_SHAPE, "%s: %lld signals", who, (long long)n_data);
-  SignalGeo x;
-  PatchGeo& g = x.g;
-  long long per, P;
-  const int64_t no_stride[3] = {0, 0, 0};                    // (selects the per-signal wording of the 2^31 limit)
-  if (const int err = grid_axes(who, nd, patch_nums, patch_size, nullptr, no_stride, g, per, P)) return err;
-  RCB_REQUIRE(channel_stride >= 0, RCB_ERR_ARG, "%s: negative channel stride %lld", who, (long long)channel_stride);
-  const long long E = per * P * channels;
-  RCB_REQUIRE(E <= 0x7fffffffLL, RCB_ERR_UNSUPPORTED, "%s: %lld elements per signal (up to 2^31 - 1)", who, E);
-  if (n_data == 0) return RCB_OK;
-  RCB_REQUIRE(src && y, RCB_ERR_ARG, "%s: null src or y", who);
-  RCB_REQUIRE(sizes && spans && table, RCB_ERR_ARG, "%s: null sizes, spans or table", who);
-  const int64_t need = rcb_ragged_table_bytes(n_data);
-  RCB_REQUIRE(need > 0 && table_bytes >= need && aligned(table, 8), RCB_ERR_SHAPE,
-              "%s: table of %lld bytes (8-byte aligned), %lld needed", who, (long long)table_bytes, (long long)need);
-  grid_elems(g, channels, E);
-  RCB_REQUIRE(n_data <= 0x7fffffffLL / g.n_chunks, RCB_ERR_UNSUPPORTED,
-              "%s: %lld signals of %lld elements need more than 2^31 - 1 workgroups", who, (long long)n_data, E);
-  std::vector<RaggedRow> rows((size_t)n_data);
-  std::vector<long long> reach((size_t)n_data);
-  if (const int err = ragged_rows(who, n_data, nd, g, channels, channel_stride, sizes, spans, rows.data(), reach.data())) return err;
-  const uintptr_t esize = src_kind == 0 ? 1 : src_kind == 1 ? 4 : 2;
-  for (long long d = 0; d < n_data; ++d) {
-    RaggedRow& r = rows[(size_t)d];
-    RCB_REQUIRE(reach[(size_t)d] < src_elems, RCB_ERR_SHAPE, "%s: signal %lld reaches element %lld of a source of %lld", who, d,
-                reach[(size_t)d], (long long)src_elems);
-    // the vector-path conditions of patch_entry, on this signal's strides and on the address of its first element
-    bool quad = (channels == 1 || channel_stride == 1) && (r.sz[2] == 1 || r.as[2] == channels) &&
-                ((uintptr_t)src + (uintptr_t)r.off * esize) % (4 * esize) == 0;
-    for (int i = 0; i < 2; ++i) quad = quad && (r.sz[i] == 1 || r.as[i] % 4 == 0);
-    r.flags = quad ? kRaggedQuad : 0;
-  }
-  x.ds = 0;
-  x.cs = channel_stride;
-  x.m = src_kind == 2 ? (float)((1 << depth) - 1) : 0.0f;
-  for (int i = 0; i < 3; ++i) x.as[i] = 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (const int err = ragged_upload(who, rows.data(), n_data, table, st)) return err;
-  const bool vec = g.R % 4 == 0 && aligned(y, 16);           // y takes whole quads (E % 4 == 0 by R % 4 == 0)
-  const unsigned blocks = (unsigned)(n_data * g.n_chunks);
-  unsigned* yo = reinterpret_cast<unsigned*>(y);
-  const RaggedRow* tb = static_cast<const RaggedRow*>(table);
-  switch (src_kind) {
-    case 0: launch_ragged<0>(vec, blocks, st, src, yo, x, tb); break;
-    case 1: launch_ragged<1>(vec, blocks, st, src, yo, x, tb); break;
-    case 2: launch_ragged<2>(vec, blocks, st, src, yo, x, tb); break;
-    default: launch_ragged<3>(vec, blocks, st, src, yo, x, tb); break;
-  }
-  RCB_LAUNCH_CHECK();
-  return RCB_OK;
+  const RaggedArgs rag = {src_elems, sizes, spans, table, table_bytes};
+  return patch_entry("signal_patch_ragged", true, src, src_kind, depth, n_data, nd, patch_nums, patch_size, nullptr, channels, 0,
+                     nullptr, channel_stride, y, stream, &rag);
 }
 
 extern "C" int rcb_signal_patch(const void* src, int32_t src_kind, int64_t n_data, int32_t nd, const int32_t* patch_nums,

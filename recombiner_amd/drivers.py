@@ -265,18 +265,49 @@ def compress(config, dataset, checkpoint, x, y, device="cuda", seed=42, n_epochs
         verbose=verbose, lr=lr, fine_tune_gap=1, compress_from_group_with_largest_kl=True)
     if bitstream_path is not None:
         from . import bitstream
-        with open(bitstream_path, "wb") as f:
-            f.write(bitstream.encode(model, sample_format=sample_format))
+        _write_stream(bitstream_path, bitstream.encode(model, sample_format=sample_format))
     return distortion, model
 
 
-def _signal_format(what, signals, sample_format):
-    # a 16-bit tensor does not say how deep its samples are (nor, for int16, whether they are PCM or reinterpreted u16)
-    if sample_format is None and signals.dtype in (torch.uint16, torch.int16):
-        raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.u16(depth) or .s16()): the depth is not in the "
-                         "dtype" % (what, signals.dtype))
-    if sample_format is not None and not sample_format.accepts(signals.dtype):
-        raise ValueError("%s: sample_format %r reads %s signals, got %s" % (what, sample_format, sample_format.dtype, signals.dtype))
+def _write_stream(path, blob):
+    with open(path, "wb") as f:
+        f.write(blob)
+
+
+def _default_x(x, config, device, n_rows):
+    """x, or the preset's own coordinate features shared by all rows"""
+    from . import utils
+    return utils.preset_inputs(config, device)[None].expand(n_rows, -1, -1) if x is None else x
+
+
+def _signal_views(what, signals, sample_format, device, config=None, channels_first=False, listed=False):
+    """What every whole-signal driver does to its signals before they are cut, `what` naming the driver in the refusals: the format
+    check, the axis check, the move to the device, the channel axis moved last, the channel check -> the list of views.  `signals`
+    is a list of batches [n, *size, C], or with `listed` of single signals [*size, C] of one dtype.  config None: format check and
+    move only (compress_signals, whose axes utils.signal_view moves and checks)."""
+    lead = 0 if listed else 1                                # axes in front of the spatial ones
+    views = []
+    for k, t in enumerate(signals):
+        # a 16-bit tensor does not say how deep its samples are (nor, for int16, whether they are PCM or reinterpreted u16)
+        if sample_format is None and t.dtype in (torch.uint16, torch.int16):
+            raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.u16(depth) or .s16()): the depth is not in the "
+                             "dtype" % (what, t.dtype))
+        if sample_format is not None and not sample_format.accepts(t.dtype):
+            raise ValueError("%s: sample_format %r reads %s signals, got %s" % (what, sample_format, sample_format.dtype, t.dtype))
+        if config is None:
+            views.append(t.to(device))
+            continue
+        dd, Cc = config["data_dim"], config["output_dim"]
+        if t.dim() != dd + 1 + lead or t.dtype != signals[0].dtype:
+            raise ValueError("%s: signal %d is %s with %d axes; [*size, C] of %s expected for a %d-D preset"
+                             % (what, k, t.dtype, t.dim(), signals[0].dtype, dd) if listed else
+                             "%s: %d axes for a %d-D preset ([n, *size, C] expected)" % (what, t.dim(), dd))
+        v = t.to(device).movedim(lead, -1) if channels_first else t.to(device)
+        if v.shape[-1] != Cc:
+            raise ValueError("%s: signal %d has %d channels, the preset %d" % (what, k, v.shape[-1], Cc) if listed else
+                             "%s: %d channels, the preset has %d" % (what, v.shape[-1], Cc))
+        views.append(v)
+    return views
 
 
 def compress_signals(config, dataset, checkpoint, signals, x=None, channels_first=False, origin=None, landscape=True,
@@ -289,13 +320,11 @@ def compress_signals(config, dataset, checkpoint, signals, x=None, channels_firs
     sample_format (utils.SampleFormat): how the samples are stored; required for uint16 / int16 signals (ValueError without it),
     and written into the stream as `compress` documents."""
     from . import utils
-    _signal_format("compress_signals", signals, sample_format)
     device = kw.get("device", "cuda")
-    view = utils.signal_view(config, signals.to(device), channels_first=channels_first, origin=origin, landscape=landscape)
+    (moved,) = _signal_views("compress_signals", [signals], sample_format, device)
+    view = utils.signal_view(config, moved, channels_first=channels_first, origin=origin, landscape=landscape)
     y = ops.signal_patch(view, utils.signal_layout(config), sample_format=sample_format)
-    if x is None:
-        x = utils.preset_inputs(config, device)[None].expand(y.shape[0], -1, -1)
-    return compress(config, dataset, checkpoint, x, y, sample_format=sample_format, **kw)
+    return compress(config, dataset, checkpoint, _default_x(x, config, device, y.shape[0]), y, sample_format=sample_format, **kw)
 
 
 def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_first=False, bitstream_path=None,
@@ -319,26 +348,16 @@ def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_
     that is the distortion of the delivered PCM, NOT the reference's figure, which scores the unrounded reconstruction
     (utils.metric, round=False).  A format other than the preset's implied one makes the stream version 3, which carries it."""
     from . import bitstream, utils
-    _signal_format("compress_signals_any", signals, sample_format)
     device = kw.get("device", "cuda")
-    dd = config["data_dim"]
-    if signals.dim() != dd + 2:
-        raise ValueError("compress_signals_any: %d axes for a %d-D preset ([n, *size, C] expected)" % (signals.dim(), dd))
-    view = signals.to(device)
-    if channels_first:
-        view = view.movedim(1, -1)
-    if view.shape[-1] != config["output_dim"]:
-        raise ValueError("compress_signals_any: %d channels, the preset has %d" % (view.shape[-1], config["output_dim"]))
+    (view,) = _signal_views("compress_signals_any", [signals], sample_format, device, config, channels_first)
     size = tuple(int(v) for v in view.shape[1:-1])
     fitted = utils.fit_config(config, size)
     y = ops.signal_patch_pad(view, utils.signal_layout(fitted), sample_format=sample_format)
-    if x is None:
-        x = utils.preset_inputs(fitted, device)[None].expand(y.shape[0], -1, -1)
+    x = _default_x(x, fitted, device, y.shape[0])
     _, model = compress(fitted, dataset, checkpoint, x, y, **kw)
     distortion = model.report(x, y, size=size, sample_format=sample_format)
     if bitstream_path is not None:
-        with open(bitstream_path, "wb") as f:
-            f.write(bitstream.encode(model, extent=size, sample_format=sample_format))
+        _write_stream(bitstream_path, bitstream.encode(model, extent=size, sample_format=sample_format))
     return distortion, model, fitted
 
 
@@ -365,19 +384,7 @@ def compress_signal_list(config, dataset, checkpoint, signals, channels_first=Fa
     if "bitstream_path" in kw:
         raise ValueError("compress_signal_list: one stream per bucket is written, to bitstream_dir")
     device = kw.get("device", "cuda")
-    dd = config["data_dim"]
-    views = []
-    for k, t in enumerate(signals):
-        _signal_format("compress_signal_list", t, sample_format)
-        if t.dim() != dd + 1 or t.dtype != signals[0].dtype:
-            raise ValueError("compress_signal_list: signal %d is %s with %d axes; [*size, C] of %s expected for a %d-D preset"
-                             % (k, t.dtype, t.dim(), signals[0].dtype, dd))
-        v = t.to(device)
-        if channels_first:
-            v = v.movedim(0, -1)
-        if v.shape[-1] != config["output_dim"]:
-            raise ValueError("compress_signal_list: signal %d has %d channels, the preset %d" % (k, v.shape[-1], config["output_dim"]))
-        views.append(v)
+    views = _signal_views("compress_signal_list", signals, sample_format, device, config, channels_first, listed=True)
     swaps, buckets = utils.ragged_plan(config, [tuple(v.shape[:-1]) for v in views], landscape=landscape)
     per_signal = dataset in ("cifar", "protein")
     figures = np.zeros(len(views), dtype=np.float64)
@@ -387,10 +394,11 @@ def compress_signal_list(config, dataset, checkpoint, signals, channels_first=Fa
         fitted, idx, sizes = bucket["config"], bucket["indices"], bucket["sizes"]
         cut = [views[k].transpose(0, 1) if swaps[k] else views[k] for k in idx]
         y = ops.signal_patch_ragged(cut, utils.signal_layout(fitted), sample_format=sample_format)
-        x = utils.preset_inputs(fitted, device)[None].expand(y.shape[0], -1, -1)
+        x = _default_x(None, fitted, device, y.shape[0])
         _, model = compress(fitted, dataset, checkpoint, x, y, **kw)
         d = model.report(x, y, sizes=sizes, sample_format=sample_format)
-        count = float(sum(int(np.prod(s)) for s in sizes) * y.shape[-1])
+        real = sum(int(np.prod(s)) for s in sizes)           # the bucket's real sample positions
+        count = float(real * y.shape[-1])
         if per_signal:
             figures[idx] = d
         else:                                                # a PSNR over the bucket's real samples -> its share of the summed error
@@ -399,10 +407,9 @@ def compress_signal_list(config, dataset, checkpoint, signals, channels_first=Fa
         blob = bitstream.encode(model, extents=sizes, swaps=[swaps[k] for k in idx], sample_format=sample_format)
         if bitstream_dir is not None:
             os.makedirs(bitstream_dir, exist_ok=True)
-            with open(os.path.join(bitstream_dir, "bucket_%d.rcb" % b), "wb") as f:
-                f.write(blob)
+            _write_stream(os.path.join(bitstream_dir, "bucket_%d.rcb" % b), blob)
         bits += bitstream.payload_bits(blob)
-        positions += sum(int(np.prod(s)) for s in sizes)
+        positions += real
         records.append(dict(indices=list(idx), sizes=list(sizes), swaps=[swaps[k] for k in idx], model=model, config=fitted,
                             stream=blob))
     distortion = figures if per_signal else float(-10.0 * np.log10(pooled_err / pooled_n))

@@ -6,6 +6,7 @@ not on the GPU -- there is no CPU fallback.
 """
 import collections
 import ctypes as C
+import math
 import os as _os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -15,6 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import AdamCfg, AdamTensor, Level, LevelBwd, RcbError, SirenDesc, addr, check, ptr, stream_ptr
+from .utils import SampleFormat
 
 f32 = torch.float32
 f64 = torch.float64
@@ -1196,33 +1198,24 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
     `mode`, which it overrides (rcb_recon_finish_fmt) -- u8 and f32 are RECON_8BIT and RECON_RAW bit for bit, u16(b) rounds to
     k / (2^b - 1) (RECON_U16), s16 to k / 65536 (RECON_S16), and want_u8 (alias: want_int) then asks for the integer output in the
     format's dtype: uint8, uint16 or int16 in the first slot of the result (and of `out`); f32 has none."""
-    lib = _lib.load()
     want_u8 = want_u8 or want_int
-    depth, qdt = 0, torch.uint8
-    if sample_format is not None:
-        mode, depth = sample_format.kind, sample_format.depth
-        qdt = sample_format.dtype if sample_format.is_integer else torch.uint8
-    if y.dim() != 3 or y.dtype != f32 or not y.is_cuda or not y.is_contiguous():
-        raise RcbError("recon_finish: y must be a contiguous fp32 GPU tensor [N, P, C]")
-    if target is not None and (tuple(target.shape) != tuple(y.shape) or target.dtype != f32 or not target.is_contiguous()
-                               or target.device != y.device):
-        raise RcbError(f"recon_finish: target must be a contiguous fp32 tensor {list(y.shape)} on the device of y")
-    N, P, Cc = (int(v) for v in y.shape)
-    nd, pn, ps, per, _, _ = _grid_args(layout)
+    mode, depth, qdt = _sample_rule(sample_format=sample_format, mode=mode)
+    qdt = qdt or torch.uint8                                 # (integers of a format that has none: the library says so)
+    N, P, Cc = _recon_inputs("recon_finish", y, target)
+    nd, pn, ps, per, _, grid = _grid_args(layout)
     if nd > 3 or (layout is not None and len(layout.patch_size) != nd):
         raise RcbError(f"recon_finish: {nd} grid dimensions (a PeLayout of 1 to 3 axes, or None)")
     n_data = N // max(per, 1)
-    n_ws = int(lib.rcb_recon_workspace_bytes(max(n_data, 1), per * P * Cc)) if N and P and Cc else -1
     dev = y.device
-    shape = recon_whole_shape((N, P, Cc), layout) if per > 0 and N % per == 0 else (N, P, Cc)
-    crop = []
+    shape = (n_data, *grid, Cc) if nd and per > 0 and N % per == 0 else (N, P, Cc)          # (recon_whole_shape's)
+    crop = None
     if size is not None:
         size = [int(v) for v in size]
         if nd == 0 or len(size) != nd:
             raise RcbError(f"recon_finish: size of {len(size)} entries for a layout of {nd} axes (a PeLayout of as many)")
         if len(shape) == nd + 2 and all(1 <= s <= g for s, g in zip(size, shape[1:-1])):      # (else: the library says why)
             shape = (n_data, *size, Cc)
-        crop = [(C.c_int32 * 3)(*(size + [0] * (3 - nd)))]
+        crop = (C.c_int32 * 3)(*(size + [0] * (3 - nd)))
     u8, whole, sse, n_bad = out if out is not None else (None,) * 4
     if want_u8 and u8 is None:
         u8 = torch.empty(shape, device=dev, dtype=qdt)
@@ -1236,16 +1229,47 @@ def recon_finish(y, target=None, layout=None, mode=RECON_8BIT, want_u8=False, wa
         if t_ is not None and (tuple(t_.shape) != tuple(want) or t_.dtype != dt or t_.device != dev or not t_.is_contiguous()):
             raise RcbError(f"recon_finish: output of shape {tuple(t_.shape)} {t_.dtype}, expected contiguous {tuple(want)} {dt} "
                            "on the device of y")
-    ws = torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8)       # (a refused shape: the library says why)
-    if sample_format is not None:
-        _launch("rcb_recon_finish_fmt", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps, crop[0] if crop else None,
-                int(mode), depth, ptr(u8, qdt, True), ptr(whole, f32, True), ptr(sse, f64, True), ptr(n_bad, i32), ptr(ws),
-                max(n_ws, 8))
-        return u8, whole, sse, n_bad
-    _launch("rcb_recon_finish_crop" if crop else "rcb_recon_finish", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps,
-            *crop, int(mode), ptr(u8, torch.uint8, True), ptr(whole, f32, True), ptr(sse, f64, True), ptr(n_bad, i32), ptr(ws),
-            max(n_ws, 8))
+    ws, ws_bytes = _recon_workspace(n_data, per * P * Cc if N else 0, dev)
+    # which entry, and what it takes that the others do not: _fmt a size that may be null and a depth, _crop a size that is there
+    by_fmt = sample_format is not None
+    cropped = crop is not None
+    entry = "rcb_recon_finish_fmt" if by_fmt else "rcb_recon_finish_crop" if cropped else "rcb_recon_finish"
+    _launch(entry, ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps, *([crop] if by_fmt or cropped else []), int(mode),
+            *([depth] if by_fmt else []), ptr(u8, qdt, True), ptr(whole, f32, True), ptr(sse, f64, True), ptr(n_bad, i32), ptr(ws),
+            ws_bytes)
     return u8, whole, sse, n_bad
+
+
+def _sample_rule(what=None, dtype=None, sample_format=None, mode=None):
+    """THE rule from (dtype of the source, sample_format, mode) to (the library's source kind / mode, depth, dtype of the integer
+    output or None): a format decides all three and refuses (as `what`) a source dtype it does not read; without one the source
+    dtype decides between uint8 and fp32, or `mode` stands."""
+    if sample_format is not None:
+        if dtype is not None and not sample_format.accepts(dtype):
+            raise RcbError(f"{what}: {sample_format!r} reads {sample_format.dtype} signals, got {dtype}")
+        return sample_format.kind, sample_format.depth, sample_format.int_dtype
+    if dtype is not None:
+        if dtype not in SIGNAL_KINDS:
+            raise RcbError(f"{what}: signals must be uint8 or fp32, got {dtype}")
+        mode = SIGNAL_KINDS[dtype]
+    return mode, 0, SampleFormat.INT_DTYPES.get(mode)
+
+
+def _recon_inputs(who, y, target):
+    """the y / target check of the recon_finish wrappers -> (N, P, C)"""
+    _lib.load()
+    if y.dim() != 3 or y.dtype != f32 or not y.is_cuda or not y.is_contiguous():
+        raise RcbError(f"{who}: y must be a contiguous fp32 GPU tensor [N, P, C]")
+    if target is not None and (tuple(target.shape) != tuple(y.shape) or target.dtype != f32 or not target.is_contiguous()
+                               or target.device != y.device):
+        raise RcbError(f"{who}: target must be a contiguous fp32 tensor {list(y.shape)} on the device of y")
+    return tuple(int(v) for v in y.shape)
+
+
+def _recon_workspace(n_data, elems, dev):
+    """the chunk partials of n_data datapoints of `elems` elements -> (buffer, bytes); a refused shape: the library says why"""
+    n_ws = int(_lib.load().rcb_recon_workspace_bytes(max(n_data, 1), elems)) if elems else -1
+    return torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8), max(n_ws, 8)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1280,34 +1304,36 @@ def signal_patch_pad(signals, layout, out=None, sample_format=None):
 def _signal_patch(what, signals, layout, out, pad, fmt=None):
     if not isinstance(signals, torch.Tensor) or not signals.is_cuda:
         raise RcbError(f"{what}: signals must be a GPU tensor (the HIP path has no CPU fallback)")
-    if fmt is not None:
-        if not fmt.accepts(signals.dtype):
-            raise RcbError(f"{what}: {fmt!r} reads {fmt.dtype} signals, got {signals.dtype}")
-    elif signals.dtype not in SIGNAL_KINDS:
-        raise RcbError(f"{what}: signals must be uint8 or fp32, got {signals.dtype}")
+    kind, depth, _ = _sample_rule(what, signals.dtype, fmt)
     nd, pn, ps, per, P, grid = _grid_args(layout)
     if len(layout.patch_size) != nd or signals.dim() != nd + 2:
         raise RcbError(f"{what}: signals of {signals.dim()} axes for a layout of {nd} ([n, *grid, C] expected)")
     n, Cc = int(signals.shape[0]), int(signals.shape[-1])
     if not pad and tuple(signals.shape[1:-1]) != grid:       # (pad: the library holds the extent to [1, G])
         raise RcbError(f"{what}: signals on the grid {tuple(signals.shape[1:-1])}, the layout's is {grid}")
-    shape = (n * per, P, Cc)
-    fits = 0 <= per * P * Cc <= 0x7fffffff                   # (a refused shape gets no buffer: the library says why)
-    if out is None:
-        out = torch.empty(shape if fits else (1,), device=signals.device, dtype=f32)
-    elif tuple(out.shape) != shape or out.dtype != f32 or out.device != signals.device or not out.is_contiguous():
-        raise RcbError(f"{what}: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {f32} on the "
-                       "device of signals")
+    out, _ = _patch_out(what, out, n, per, P, Cc, signals.device, "signals")
     st = [int(v) for v in signals.stride()]
     arr = max(nd, 1)
-    size = [(C.c_int32 * arr)(*signals.shape[1:-1])] if pad else []
-    if fmt is not None:
-        _launch("rcb_signal_patch_fmt", C.c_void_p(signals.data_ptr()), fmt.kind, fmt.depth, n, nd, pn, ps, size[0] if pad else None,
-                Cc, st[0], (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
-        return out
-    _launch("rcb_" + what, C.c_void_p(signals.data_ptr()), SIGNAL_KINDS[signals.dtype], n, nd, pn, ps, *size, Cc, st[0],
-            (C.c_int64 * arr)(*st[1:-1]), st[-1], C.c_void_p(out.data_ptr()))
+    size = (C.c_int32 * arr)(*signals.shape[1:-1]) if pad else None
+    # which entry, and what it takes that the others do not: _fmt a depth and a size that may be null, _pad a size that is there
+    by_fmt = fmt is not None
+    _launch("rcb_signal_patch_fmt" if by_fmt else "rcb_" + what, C.c_void_p(signals.data_ptr()), kind, *([depth] if by_fmt else []),
+            n, nd, pn, ps, *([size] if by_fmt or pad else []), Cc, st[0], (C.c_int64 * arr)(*st[1:-1]), st[-1],
+            C.c_void_p(out.data_ptr()))
     return out
+
+
+def _patch_out(what, out, n, per, P, Cc, dev, of):
+    """the targets [n * per, P, C] of the signal_patch wrappers, allocated or the caller's checked -> (out, fits); a shape the
+    library will refuse (fits False) gets a one-element buffer, and the library says why"""
+    shape = (n * per, P, Cc)
+    fits = 0 <= per * P * Cc <= 0x7fffffff
+    if out is None:
+        out = torch.empty(shape if fits else (1,), device=dev, dtype=f32)
+    elif tuple(out.shape) != shape or out.dtype != f32 or out.device != dev or not out.is_contiguous():
+        raise RcbError(f"{what}: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {f32} on the "
+                       f"device of {of}")
+    return out, fits
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1356,22 +1382,9 @@ def signal_patch_ragged(signals, layout, out=None, sample_format=None):
         if t.dtype != first.dtype or t.device != first.device or t.dim() != nd + 1 or t.shape[-1] != first.shape[-1]:
             raise RcbError(f"{what}: signal {k} is {t.dtype} {tuple(t.shape)} on {t.device}; all signals are [*size, C] of one "
                            f"dtype, channel count and device, with {nd} axes of size")
-    if sample_format is not None:
-        if not sample_format.accepts(first.dtype):
-            raise RcbError(f"{what}: {sample_format!r} reads {sample_format.dtype} signals, got {first.dtype}")
-        kind, depth = sample_format.kind, sample_format.depth
-    elif first.dtype in SIGNAL_KINDS:
-        kind, depth = SIGNAL_KINDS[first.dtype], 0
-    else:
-        raise RcbError(f"{what}: signals must be uint8 or fp32, got {first.dtype}")
+    kind, depth, _ = _sample_rule(what, first.dtype, sample_format)
     n, Cc, dev, item = len(signals), int(first.shape[-1]), first.device, first.element_size()
-    shape = (n * per, P, Cc)
-    fits = 0 <= per * P * Cc <= 0x7fffffff
-    if out is None:
-        out = torch.empty(shape if fits else (1,), device=dev, dtype=f32)
-    elif tuple(out.shape) != shape or out.dtype != f32 or out.device != dev or not out.is_contiguous():
-        raise RcbError(f"{what}: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {f32} on the "
-                       "device of the signals")
+    out, fits = _patch_out(what, out, n, per, P, Cc, dev, "the signals")
     base = min(t.data_ptr() for t in signals)
     end = max(t.untyped_storage().data_ptr() + t.untyped_storage().nbytes() for t in signals)
     sizes, spans, cstride = [], [], []
@@ -1419,20 +1432,14 @@ def recon_finish_ragged_into(y, target, layout, sizes, spans, out_elems, mode=RE
     """rcb_recon_finish_ragged on the caller's own output buffers and spans (what recon_finish_ragged lays out for itself):
     q_buf / whole_buf are 1-D GPU tensors of at least out_elems elements (or None), spans[k] = (offset, *axis strides) in elements.
     -> (sse fp64 [n] or None without target, n_bad int32 [n])."""
-    lib = _lib.load()
-    if y.dim() != 3 or y.dtype != f32 or not y.is_cuda or not y.is_contiguous():
-        raise RcbError("recon_finish_ragged: y must be a contiguous fp32 GPU tensor [N, P, C]")
-    if target is not None and (tuple(target.shape) != tuple(y.shape) or target.dtype != f32 or not target.is_contiguous()
-                               or target.device != y.device):
-        raise RcbError(f"recon_finish_ragged: target must be a contiguous fp32 tensor {list(y.shape)} on the device of y")
-    N, P, Cc = (int(v) for v in y.shape)
+    N, P, Cc = _recon_inputs("recon_finish_ragged", y, target)
     nd, pn, ps, per, _, _ = _grid_args(layout)
     n = len(sizes)
     if nd == 0 or n * per != N:
         raise RcbError(f"recon_finish_ragged: {n} sizes for {N} rows of a layout of {per} patches per signal")
     sz, sp = _ragged_tables(sizes, spans, nd)
     dev = y.device
-    qdt = {RECON_8BIT: torch.uint8, RECON_U16: torch.uint16, RECON_S16: torch.int16}.get(int(mode))
+    _, _, qdt = _sample_rule(mode=int(mode))
     for b, dt in ((q_buf, qdt), (whole_buf, f32)):
         if b is not None and (dt is None or b.dtype != dt or b.dim() != 1 or b.numel() < out_elems or b.device != dev
                               or not b.is_contiguous()):
@@ -1442,12 +1449,11 @@ def recon_finish_ragged_into(y, target, layout, sizes, spans, out_elems, mode=RE
         sse = torch.empty(n, device=dev, dtype=f64)
     if n_bad is None:
         n_bad = torch.empty(n, device=dev, dtype=i32)
-    n_ws = int(lib.rcb_recon_workspace_bytes(max(n, 1), per * P * Cc)) if N and P and Cc else -1
-    ws = torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8)
+    ws, ws_bytes = _recon_workspace(n, per * P * Cc if N else 0, dev)
     table, n_bytes = _ragged_table(n, dev)
     _launch("rcb_recon_finish_ragged", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps, _np_ptr(sz), _np_ptr(sp),
             int(out_elems), int(mode), int(depth), ptr(q_buf, None, True), ptr(whole_buf, f32, True), ptr(sse, f64, True),
-            ptr(n_bad, i32), ptr(ws), max(n_ws, 8), ptr(table), n_bytes)
+            ptr(n_bad, i32), ptr(ws), ws_bytes, ptr(table), n_bytes)
     return sse, n_bad
 
 
@@ -1463,24 +1469,21 @@ def recon_finish_ragged(y, target=None, layout=None, sizes=None, swap=None, mode
     mode / sample_format / want_int / want_whole: recon_finish's.  The only host sync is the table upload."""
     if layout is None or sizes is None:
         raise RcbError("recon_finish_ragged: a layout and one size per signal are needed")
-    depth, qdt = 0, torch.uint8
-    if sample_format is not None:
-        mode, depth = sample_format.kind, sample_format.depth
-        qdt = sample_format.dtype if sample_format.is_integer else torch.uint8
+    mode, depth, qdt = _sample_rule(sample_format=sample_format, mode=mode)
     sizes = [[int(v) for v in s] for s in sizes]
     swap = [False] * len(sizes) if swap is None else [bool(v) for v in swap]
     if len(swap) != len(sizes) or (any(swap) and len(layout.patch_nums) != 2):
         raise RcbError("recon_finish_ragged: one swap flag per signal, and only 2-D signals can be swapped")
     Cc = int(y.shape[-1]) if y.dim() == 3 else 1
     spans, shapes, total = _ragged_spans(sizes, swap, Cc)
-    q_buf = torch.empty(max(total, 1), device=y.device, dtype=qdt) if want_int else None
+    q_buf = torch.empty(max(total, 1), device=y.device, dtype=qdt or torch.uint8) if want_int else None
     whole_buf = torch.empty(max(total, 1), device=y.device, dtype=f32) if want_whole else None
     sse, n_bad = recon_finish_ragged_into(y, target, layout, sizes, spans, total, mode, depth, q_buf, whole_buf)
 
     def views(buf):
         if buf is None:
             return None
-        return [buf[sp[0]:sp[0] + int(np.prod(shp))].view(shp) for sp, shp in zip(spans, shapes)]
+        return [buf[sp[0]:sp[0] + math.prod(shp)].view(shp) for sp, shp in zip(spans, shapes)]
     return views(q_buf), views(whole_buf), sse, n_bad
 
 

@@ -137,11 +137,9 @@ class InrGeometry:
             return self._report(x, y)
         with torch.no_grad():
             y_pred = self.predict(x.to(self.loc.device))
-        if sizes is not None:
-            return metric_device(y, y_pred, self.dataset, self.signal_layout(), sample_format=sample_format, sizes=sizes)
-        if size is not None:
-            return metric_device(y, y_pred, self.dataset, self.signal_layout(), size=size, sample_format=sample_format)
-        return metric_device(y, y_pred, self.dataset, self.recon_layout(), sample_format=sample_format)
+        cropped = size is not None or sizes is not None         # (an extent needs the grid of the unpatched presets too)
+        return metric_device(y, y_pred, self.dataset, self.signal_layout() if cropped else self.recon_layout(),
+                             size=None if sizes is not None else size, sample_format=sample_format, sizes=sizes)
 
     def patch_signals(self, signals, size=None, sample_format=None, sizes=None):
         """whole signals [n, *grid, C] on the GPU (uint8 or fp32, any strides: utils.signal_view) -> the targets y [N, P, C] of

@@ -235,9 +235,17 @@ class SampleFormat:
         """the torch dtype of the samples (and of the integer output of ops.recon_finish)"""
         return (torch.uint8, torch.float32, torch.uint16, torch.int16)[self.kind]
 
+    # THE integer-dtype rule: the torch dtype of the integers a reconstruction is delivered in, by kind (the library's mode); f32
+    # has none, nor has a number that is no kind.  ops.recon_finish* and the bitstream decoders read it here
+    INT_DTYPES = {U8: torch.uint8, U16: torch.uint16, S16: torch.int16}
+
+    @property
+    def int_dtype(self):
+        return self.INT_DTYPES.get(self.kind)
+
     @property
     def is_integer(self):
-        return self.kind != self.F32
+        return self.int_dtype is not None
 
     def accepts(self, dtype):
         """whether a source tensor of `dtype` can be read in this format: its own dtype; u16 also takes int16 (the bits)"""
@@ -409,21 +417,16 @@ def metric_from_sse(sse, n_elems, dataset):
     if dataset not in METRIC_ROUNDS:
         raise ValueError(dataset)
     sse = np.asarray(sse, dtype=np.float64).reshape(-1)
-    if np.ndim(n_elems) != 0:
-        counts = np.asarray(n_elems, dtype=np.float64).reshape(-1)
-        if counts.size != sse.size:
-            raise ValueError("metric_from_sse: %d element counts for %d datapoints" % (counts.size, sse.size))
-        if dataset == "cifar":
-            return -10.0 * np.log10(sse / counts)
-        if dataset == "protein":
-            return 25.0 * np.sqrt(3.0 * sse / counts)
-        return (-10.0 * np.log10(sse.sum() / counts.sum())).item()
-    n = float(n_elems)
+    counts = np.asarray(n_elems, dtype=np.float64).reshape(-1)
+    if np.ndim(n_elems) == 0:                                # one count for every datapoint
+        counts = np.broadcast_to(counts, sse.shape)
+    elif counts.size != sse.size:
+        raise ValueError("metric_from_sse: %d element counts for %d datapoints" % (counts.size, sse.size))
     if dataset == "cifar":
-        return -10.0 * np.log10(sse / n)
+        return -10.0 * np.log10(sse / counts)
     if dataset == "protein":
-        return 25.0 * np.sqrt(3.0 * sse / n)
-    return (-10.0 * np.log10(sse.sum() / (n * sse.size))).item()
+        return 25.0 * np.sqrt(3.0 * sse / counts)
+    return (-10.0 * np.log10(sse.sum() / counts.sum())).item()
 
 
 def metric_device(y_true, y_pred, dataset, layout=None, size=None, sample_format=None, sizes=None):
@@ -445,12 +448,13 @@ def metric_device(y_true, y_pred, dataset, layout=None, size=None, sample_format
     mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
     y_pred = y_pred.detach().to(torch.float32).contiguous()
     y_true = y_true.detach().to(device=y_pred.device, dtype=torch.float32).contiguous()
+    Cc = y_pred.shape[-1]
     if sizes is not None:
         if size is not None:
             raise ValueError("metric_device: size and sizes exclude each other")
         _, _, sse, _n_bad = ops.recon_finish_ragged(y_pred, y_true, layout=layout, sizes=sizes, mode=mode, sample_format=sample_format)
-        counts = [int(np.prod([int(v) for v in s])) * y_pred.shape[-1] for s in sizes]
-        return metric_from_sse(sse.cpu().numpy(), np.asarray(counts), dataset)
-    _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode, size=size, sample_format=sample_format)
-    n_elems = y_pred.numel() // sse.numel() if size is None else int(np.prod([int(v) for v in size])) * y_pred.shape[-1]
-    return metric_from_sse(sse.cpu().numpy(), n_elems, dataset)
+        counts = np.asarray([int(np.prod([int(v) for v in s])) * Cc for s in sizes])
+    else:
+        _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode, size=size, sample_format=sample_format)
+        counts = y_pred.numel() // sse.numel() if size is None else int(np.prod([int(v) for v in size])) * Cc
+    return metric_from_sse(sse.cpu().numpy(), counts, dataset)

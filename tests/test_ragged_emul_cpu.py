@@ -230,3 +230,22 @@ def test_metric_from_sse_with_count_arrays():
     assert utils.metric_from_sse(sse, 100, "kodak") == (-10.0 * np.log10(sse.sum() / (100.0 * 3))).item()
     with pytest.raises(ValueError):
         utils.metric_from_sse(sse, counts[:2], "cifar")
+
+
+# ---- the stream format did not move ----------------------------------------------------------------------------------------------
+def test_bitstream_bytes_and_outcomes_match_the_recorded_ones():
+    """tools/bitstream_digests.py: the bytes pack_indices writes for versions 1 to 4, and what unpack, unpack_header and payload_bits
+    make of one stream per version intact, with any single byte changed and cut at any length -- the value or the ValueError's
+    text -- against tests/golden/bitstream_outcomes.json, which was recorded before the container code was rewritten"""
+    import importlib.util
+    import json
+    import os
+    from golden_util import GOLDEN, ROOT
+    spec = importlib.util.spec_from_file_location("bitstream_digests", os.path.join(ROOT, "tools", "bitstream_digests.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(GOLDEN, "bitstream_outcomes.json")) as f:
+        recorded = json.load(f)
+    got = dict(tool.lines(bitstream, SampleFormat))
+    assert sorted(got) == sorted(recorded)
+    assert {k: v for k, v in got.items() if recorded[k] != v} == {}

@@ -29,6 +29,8 @@ def sha(t):
         return "None"
     if isinstance(t, ops.Planes):
         return "planes(" + sha(t.hi) + "," + sha(t.lo) + ")"
+    if isinstance(t, (list, tuple)):
+        return "[" + ",".join(sha(v) for v in t) + "]"
     return hashlib.sha256(t.detach().contiguous().cpu().view(torch.uint8).numpy().tobytes()).hexdigest()[:24]
 
 
@@ -176,3 +178,158 @@ case("rec_score exact + rec_commit", lambda: rec(ops.REC_EXACT))
 case("rec_score fast + rec_commit", lambda: rec(ops.REC_FAST))
 case("rec_score_argmax (commit without state tensors)",
      lambda: ops.rec_score_argmax(loc, scale, pl, ps, tabs, gum, [0, 1, 2, 3], [0, 5, 9, 13], [1, 2, 3, 3]))
+
+# ---- N4, whole-signal I/O: signal_patch* / recon_finish* ---------------------------------------------------------------------
+# layouts of 1 to 3 axes at C = 3; a run R = patch_size[last] * C that is a multiple of 4 (the quad path) and one that is not (the
+# element path); one signal of 2 x 2 patches of 32 x 32 x 3 = 12 288 elements, two chunks: the reduce kernel adds two partials
+from recombiner_amd.utils import SampleFormat  # noqa: E402
+
+N4_LAYOUTS = [("1d quad", (3,), (4,)), ("1d elem", (3,), (5,)), ("2d quad", (2, 2), (4, 4)), ("2d elem", (2, 2), (4, 3)),
+              ("3d quad", (2, 1, 2), (2, 3, 4)), ("2d two chunks", (2, 2), (32, 32))]
+N4_FORMATS = [("u8", SampleFormat.u8()), ("f32", SampleFormat.f32()), ("u16_12", SampleFormat.u16(12)), ("s16", SampleFormat.s16())]
+
+
+def n4_signal(rng, shape, fmt):
+    if fmt.kind == SampleFormat.F32:
+        return torch.from_numpy(rng.rand(*shape).astype(np.float32)).to(DEV)
+    if fmt.kind == SampleFormat.U8:
+        return torch.from_numpy(rng.randint(0, 256, size=shape).astype(np.uint8)).to(DEV)
+    if fmt.kind == SampleFormat.U16:
+        return torch.from_numpy(rng.randint(0, 1 << fmt.depth, size=shape).astype(np.uint16)).to(DEV)
+    return torch.from_numpy(rng.randint(-32768, 32768, size=shape).astype(np.int16)).to(DEV)
+
+
+def n4_recon(rng, y):
+    """a reconstruction near the targets y, a little outside [0, 1] here and there"""
+    return (y * 1.02 - 0.01 + torch.from_numpy(rng.randn(*y.shape).astype(np.float32) * 0.01).to(DEV)).contiguous()
+
+
+for lname, pn, ps in N4_LAYOUTS:
+    lay = ops.PeLayout(pn, ps)
+    grid = tuple(a * b for a, b in zip(pn, ps))
+    n = 1 if lname == "2d two chunks" else 2
+    for fname, fmt in N4_FORMATS:
+        rng = np.random.RandomState(len(lname) * 7 + fmt.kind)
+        sig = n4_signal(rng, (n, *grid, 3), fmt)
+        y = ops.signal_patch(sig, lay, sample_format=fmt)
+        rec = n4_recon(rng, y)
+        case(f"signal_patch {lname} {fname}", lambda: y)
+        if fmt.kind in (SampleFormat.U8, SampleFormat.F32):
+            case(f"signal_patch {lname} {fname} by dtype", lambda: ops.signal_patch(sig, lay))
+        case(f"recon_finish {lname} {fname}",
+             lambda: ops.recon_finish(rec, y, layout=lay, sample_format=fmt, want_int=fmt.is_integer, want_whole=True))
+
+lay = ops.PeLayout((2, 2), (4, 4))
+for fname, fmt in N4_FORMATS:
+    rng = np.random.RandomState(40 + fmt.kind)
+    cf = n4_signal(rng, (2, 3, 8, 8), fmt)                     # channel-first storage
+    big = n4_signal(rng, (3, 11, 13, 3), fmt)                  # a window at an offset of a larger signal
+    small = n4_signal(rng, (2, 5, 7, 3), fmt)                  # below the grid on every axis
+    small_cf = n4_signal(rng, (2, 3, 5, 7), fmt)
+    case(f"signal_patch channel-first {fname}", lambda: ops.signal_patch(cf.movedim(1, -1), lay, sample_format=fmt))
+    case(f"signal_patch offset view {fname}", lambda: ops.signal_patch(big[1:, 2:10, 3:11], lay, sample_format=fmt))
+    out = torch.empty(8, 16, 3, device=DEV)
+    case(f"signal_patch_pad 5x7 {fname} into out", lambda: ops.signal_patch_pad(small, lay, out=out, sample_format=fmt))
+    case(f"signal_patch_pad 5x7 channel-first {fname}",
+         lambda: ops.signal_patch_pad(small_cf.movedim(1, -1), lay, sample_format=fmt))
+    if fmt.kind in (SampleFormat.U8, SampleFormat.F32):
+        case(f"signal_patch_pad 5x7 {fname} by dtype", lambda: ops.signal_patch_pad(small, lay))
+    y = ops.signal_patch_pad(small, lay, sample_format=fmt)
+    rec = n4_recon(rng, y)
+    case(f"recon_finish size 5x7 {fname}",
+         lambda: ops.recon_finish(rec, y, layout=lay, size=(5, 7), sample_format=fmt, want_int=fmt.is_integer, want_whole=True))
+    case(f"recon_finish size 5x7 {fname} no target", lambda: ops.recon_finish(rec, layout=lay, size=(5, 7), sample_format=fmt,
+                                                                                want_whole=True))
+    case(f"recon_finish size 8x4 {fname} scores only", lambda: ops.recon_finish(rec, y, layout=lay, size=(8, 4), sample_format=fmt))
+
+rng = np.random.RandomState(50)
+y = torch.from_numpy(rng.rand(8, 16, 3).astype(np.float32)).to(DEV)
+rec = n4_recon(rng, y)
+for mname, mode in (("8bit", ops.RECON_8BIT), ("raw", ops.RECON_RAW)):
+    u8 = mode == ops.RECON_8BIT
+    case(f"recon_finish {mname} by mode", lambda: ops.recon_finish(rec, y, layout=lay, mode=mode, want_u8=u8, want_whole=True))
+    case(f"recon_finish {mname} by mode, size 5x7",
+         lambda: ops.recon_finish(rec, y, layout=lay, mode=mode, want_u8=u8, want_whole=True, size=(5, 7)))
+    case(f"recon_finish {mname} by mode, no layout", lambda: ops.recon_finish(rec, y, mode=mode, want_u8=u8, want_whole=True))
+    case(f"recon_finish {mname} by mode, no target, no outputs", lambda: ops.recon_finish(rec, layout=lay, mode=mode))
+
+
+def recon_into_out(size, fmt):
+    shape = (2, *(size or (8, 8)), 3)
+    q = torch.zeros(shape, device=DEV, dtype=torch.uint8 if fmt.dtype == torch.uint8 else torch.int16).view(fmt.dtype)
+    out = (q, torch.zeros(shape, device=DEV), None,
+           torch.zeros(2, device=DEV, dtype=torch.int32))
+    got = ops.recon_finish(rec, y, layout=lay, size=size, sample_format=fmt, out=out)
+    return (*got, got[0] is out[0], got[1] is out[1], got[3] is out[3])
+
+
+def flagged(fn):
+    out = fn()
+    return [v if isinstance(v, torch.Tensor) or v is None else torch.tensor([int(v)]) for v in out]
+
+
+case("recon_finish into out u16_12", lambda: flagged(lambda: recon_into_out(None, SampleFormat.u16(12))))
+case("recon_finish into out u8 size 5x7", lambda: flagged(lambda: recon_into_out((5, 7), SampleFormat.u8())))
+
+# ragged: three signals of different sizes, one transposed, one channel-first -- two runs of one channel stride, so two launches
+for fname, fmt in N4_FORMATS:
+    rng = np.random.RandomState(60 + fmt.kind)
+    a, b, c = n4_signal(rng, (8, 8, 3), fmt), n4_signal(rng, (6, 5, 3), fmt), n4_signal(rng, (3, 7, 4), fmt)
+    sigs = [a, b.transpose(0, 1), c.movedim(0, -1)]
+    sizes = [(8, 8), (5, 6), (7, 4)]
+    case(f"signal_patch_ragged {fname}", lambda: ops.signal_patch_ragged(sigs, lay, sample_format=fmt))
+    if fmt.kind in (SampleFormat.U8, SampleFormat.F32):
+        out = torch.empty(12, 16, 3, device=DEV)
+        case(f"signal_patch_ragged {fname} by dtype into out", lambda: ops.signal_patch_ragged(sigs, lay, out=out))
+    y = ops.signal_patch_ragged(sigs, lay, sample_format=fmt)
+    rec = n4_recon(rng, y)
+    case(f"recon_finish_ragged {fname} swap",
+         lambda: ops.recon_finish_ragged(rec, y, layout=lay, sizes=sizes, swap=[False, True, False], sample_format=fmt,
+                                         want_int=fmt.is_integer, want_whole=True))
+    case(f"recon_finish_ragged {fname} scores only", lambda: ops.recon_finish_ragged(rec, y, layout=lay, sizes=sizes, sample_format=fmt))
+case("recon_finish_ragged 8bit by mode, no target",
+     lambda: ops.recon_finish_ragged(rec, layout=lay, sizes=sizes, mode=ops.RECON_8BIT, want_int=True, want_whole=True))
+lay1 = ops.PeLayout((3,), (5,))
+rng = np.random.RandomState(70)
+sigs1 = [n4_signal(rng, (m, 3), SampleFormat.s16()) for m in (15, 4, 11)]
+y1 = ops.signal_patch_ragged(sigs1, lay1, sample_format=SampleFormat.s16())
+case("signal_patch_ragged 1d elem s16", lambda: y1)
+case("recon_finish_ragged 1d elem s16", lambda: ops.recon_finish_ragged(n4_recon(rng, y1), y1, layout=lay1, sizes=[(15,), (4,), (11,)],
+                                                                        sample_format=SampleFormat.s16(), want_int=True, want_whole=True))
+
+# one refused call per wrapper (and per place that refuses: the wrapper's own checks, then the library's)
+u8sig = torch.zeros(2, 8, 8, 3, device=DEV, dtype=torch.uint8)
+yz = torch.zeros(8, 16, 3, device=DEV)
+case("refusal signal_patch dtype", lambda: ops.signal_patch(u8sig.to(torch.int32), lay))
+case("refusal signal_patch format dtype", lambda: ops.signal_patch(u8sig, lay, sample_format=SampleFormat.s16()))
+case("refusal signal_patch grid", lambda: ops.signal_patch(u8sig[:, :7], lay))
+case("refusal signal_patch out", lambda: ops.signal_patch(u8sig, lay, out=torch.empty(8, 16, 4, device=DEV)))
+case("refusal signal_patch_pad above the grid", lambda: ops.signal_patch_pad(torch.zeros(2, 9, 8, 3, device=DEV), lay))
+case("refusal signal_patch_pad 33 channels", lambda: ops.signal_patch_pad(torch.zeros(1, 8, 8, 33, device=DEV), lay))
+case("refusal signal_patch_fmt 33 channels", lambda: ops.signal_patch(torch.zeros(1, 8, 8, 33, device=DEV), lay,
+                                                                      sample_format=SampleFormat.f32()))
+case("refusal signal_patch_ragged empty", lambda: ops.signal_patch_ragged([], lay))
+case("refusal signal_patch_ragged mixed", lambda: ops.signal_patch_ragged([u8sig[0], u8sig[0].float()], lay))
+case("refusal signal_patch_ragged dtype", lambda: ops.signal_patch_ragged([u8sig[0].to(torch.int32)], lay))
+case("refusal signal_patch_ragged out", lambda: ops.signal_patch_ragged([u8sig[0]], lay, out=torch.empty(4, 16, 3, device=DEV).half()))
+case("refusal signal_patch_ragged above the grid", lambda: ops.signal_patch_ragged([torch.zeros(9, 8, 3, device=DEV)], lay))
+case("refusal recon_finish y", lambda: ops.recon_finish(yz.transpose(0, 1)))
+case("refusal recon_finish target", lambda: ops.recon_finish(yz, yz[:4], layout=lay))
+case("refusal recon_finish size axes", lambda: ops.recon_finish(yz, layout=lay, size=(5,)))
+case("refusal recon_finish out", lambda: ops.recon_finish(yz, layout=lay, out=(None, torch.empty(2, 8, 8, 4, device=DEV), None, None)))
+case("refusal recon_finish size above the grid", lambda: ops.recon_finish(yz, layout=lay, size=(9, 8), want_whole=True))
+case("refusal recon_finish rows", lambda: ops.recon_finish(yz[:6].contiguous(), layout=lay, want_whole=True))
+case("refusal recon_finish raw mode integers", lambda: ops.recon_finish(yz, layout=lay, mode=ops.RECON_RAW, want_u8=True))
+case("refusal recon_finish_fmt f32 integers", lambda: ops.recon_finish(yz, layout=lay, sample_format=SampleFormat.f32(), want_int=True))
+case("refusal recon_finish_ragged no sizes", lambda: ops.recon_finish_ragged(yz, layout=lay))
+case("refusal recon_finish_ragged swap", lambda: ops.recon_finish_ragged(yz, layout=lay, sizes=[(8, 8), (8, 8)], swap=[True]))
+case("refusal recon_finish_ragged y", lambda: ops.recon_finish_ragged(yz.double(), layout=lay, sizes=[(8, 8), (8, 8)]))
+case("refusal recon_finish_ragged target", lambda: ops.recon_finish_ragged(yz, yz.half(), layout=lay, sizes=[(8, 8), (8, 8)]))
+case("refusal recon_finish_ragged count", lambda: ops.recon_finish_ragged(yz, layout=lay, sizes=[(8, 8)]))
+case("refusal recon_finish_ragged above the grid", lambda: ops.recon_finish_ragged(yz, layout=lay, sizes=[(8, 8), (8, 9)], want_whole=True))
+case("refusal recon_finish_ragged_into buffer",
+     lambda: ops.recon_finish_ragged_into(yz, None, lay, [(8, 8), (8, 8)], [(0, 24, 3), (192, 24, 3)], 384, ops.RECON_U16, 12,
+                                          q_buf=torch.empty(384, device=DEV, dtype=torch.uint8)))
+case("refusal recon_finish_ragged_into overlap",
+     lambda: ops.recon_finish_ragged_into(yz, None, lay, [(8, 8), (8, 8)], [(0, 24, 3), (100, 24, 3)], 384, ops.RECON_8BIT, 0,
+                                          q_buf=torch.empty(384, device=DEV, dtype=torch.uint8)))
