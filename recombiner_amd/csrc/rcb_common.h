@@ -15,10 +15,12 @@ constexpr int kWave = 64;
 char* last_error_buf();
 int fail(int code, const char* fmt, ...);
 
+#ifndef RCB_REQUIRE   // (siren_route.h states the same macro for programs built without HIP; either order of inclusion works)
 #define RCB_REQUIRE(cond, code, ...)            \
   do {                                          \
     if (!(cond)) return rcb::fail((code), __VA_ARGS__); \
   } while (0)
+#endif
 
 #define RCB_LAUNCH_CHECK()                                                         \
   do {                                                                             \

@@ -1,18 +1,16 @@
-// Declarations shared by the fp32 and bf16 SIREN kernels.
+// Declarations shared by the SIREN kernels: the kernel argument block, the pe addressing, and the one launcher.
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 
 #include "rcb_common.h"
+#include "siren_route.h"   // HID, MAXL, MODE_*, the descriptor / layer / route rules
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace rcb {
 
-constexpr int HID = 32;      // hidden width
 constexpr int TS = 36;       // LDS tile row stride in floats (32 + 4 pad: conflict-free b128 reads)
-constexpr int MAXL = 5;      // max linear layers
-
-enum { MODE_FWD = 0, MODE_BWD = 1, MODE_LOSS = 2 };
 
 struct SirenArgs {
   const float* xf;
@@ -73,29 +71,49 @@ __device__ __forceinline__ f32x16 mfma2(float a, float b, f32x16 c) {
 }
 
 
-int siren_bf16_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);
-int siren_wide_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);   // hidden width 48 / 64
-int siren_generic_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);   // fp32, widths other than 32
-// width 32, loss / backward, one wave per row (siren_mlp_wave.hip); *taken = false when that family has no instance for the request
+// ---- launching (the route: siren_route.h; the one entry body that routes and calls these: siren_mlp.hip) ------------------
+// one launcher per family, in its kernel file: the instance the route names with that family's grid and LDS bytes, nothing else
+using SirenLaunch = int(int mode, const rcb_siren_desc* d, const SirenRoute& r, SirenArgs& a, hipStream_t st);
+SirenLaunch siren_fp32_launch, siren_generic_launch, siren_bf16_launch, siren_wave_launch, siren_wide_launch, siren_rowwave_launch;
 int& siren_wave_tiles();      // 1: one wave per row where instantiated, 0: the workgroup kernel everywhere (rcb_debug_siren_wave_tiles)
-int siren_wave_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st, int variant, bool* taken);
 
-// the 16-bit kernel family of a descriptor: width 32 (siren_mlp_bf16.hip) or the kernel with dealt gradient tiles for widths
-// 48 / 64 (siren_mlp_wide.hip; in a -DRCB_SIREN_DEALT32 build RCB_SIREN_W32_DEALT=1 sends the width-32 loss / backward
-// launches there too, for A/B runs)
-inline int siren_16bit_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
-#ifdef RCB_SIREN_DEALT32
-  static const bool dealt32 = getenv("RCB_SIREN_W32_DEALT") != nullptr;
-  if (dealt32 && mode != MODE_FWD) return siren_wide_dispatch(mode, d, a, st);
-#endif
-  if (d->hidden > HID) return siren_wide_dispatch(mode, d, a, st);
-  const int wave_variant = siren_wave_tiles();
-  if (wave_variant > 0 && mode != MODE_FWD) {
-    bool taken = false;
-    const int rc = siren_wave_dispatch(mode, d, a, st, wave_variant, &taken);
-    if (taken) return rc;
+constexpr int SIREN_LDS_MAX = 160 * 1024;
+
+// Set the LDS limit (attr_bytes > 0; per launch: the attribute belongs to the (function, device) pair, a process may drive
+// several devices or call from several threads, and the call is a table write), launch, check.
+template <class K, class... A>
+int siren_launch(K kernel, unsigned grid, unsigned block, size_t lds_bytes, int attr_bytes, const char* tag, hipStream_t st,
+                 const A&... args) {
+  if (attr_bytes > 0) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, attr_bytes);
+    if (e != hipSuccess) return fail((int)e, "%s: hipFuncSetAttribute: %s", tag, hipGetErrorString(e));
   }
-  return siren_bf16_dispatch(mode, d, a, st);
+  kernel<<<grid, block, lds_bytes, st>>>(args...);
+  RCB_LAUNCH_CHECK();
+  return RCB_OK;
+}
+
+// The instances of one geometry of the workgroup and wide families: forward, backward, loss, and the loss with both input
+// halves as 16-bit rows (siren_can16; route.in16).  launch(mode_c, in16_c) launches the instance of those two constants.
+template <int E, class L>
+int siren_launch_mode(int mode, bool in16, L&& launch) {
+  constexpr bool can16 = siren_can16(E);
+  if (can16 && in16 && mode == MODE_LOSS) return launch(std::integral_constant<int, MODE_LOSS>{}, std::integral_constant<bool, can16>{});
+  if (mode == MODE_FWD) return launch(std::integral_constant<int, MODE_FWD>{}, std::false_type{});
+  if (mode == MODE_BWD) return launch(std::integral_constant<int, MODE_BWD>{}, std::false_type{});
+  return launch(std::integral_constant<int, MODE_LOSS>{}, std::false_type{});
+}
+
+// compute units of the current device (cached per device: a process may drive several)
+inline int cu_count() {
+  static int n_cu[64];
+  int dev_id = 0;
+  if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) dev_id = 0;
+  if (n_cu[dev_id] == 0) {
+    hipDeviceProp_t prop;
+    n_cu[dev_id] = (hipGetDeviceProperties(&prop, dev_id) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+  }
+  return n_cu[dev_id];
 }
 
 }  // namespace rcb

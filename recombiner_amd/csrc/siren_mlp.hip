@@ -15,20 +15,15 @@
 // The backward pass recomputes the forward in registers: nothing but inputs and weights is read.
 //
 // fp32 path: v_mfma_f32_32x32x2_f32 (exact fp32 products, k-ordered fma chain).
+//
+// This file also holds the one body of the three entry points (siren_run): which descriptors are accepted, how long a row of
+// layer vectors is, which instances exist and which of the five kernel families runs a descriptor is stated in siren_route.h;
+// the launcher in siren_common.h; every kernel file keeps "launch this instance" (siren_<family>_launch).
 #include "rcb_common.h"
 
 using namespace rcb;
 
 #include "siren_common.h"
-
-namespace rcb {
-// one wave per row in the 16-bit modes (siren_mlp_rowwave.hip): uniform hidden width 16 or 24 at 1 .. 4 hidden layers, and every
-// descriptor of 5 .. 7 hidden layers (one width 16, 24 or 32: fill_args)
-int siren_rowwave_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st);
-inline bool siren_rowwave(const rcb_siren_desc* d) {
-  return d->precision >= 1 && (d->n_hidden >= 5 || ((d->hidden == 16 || d->hidden == 24) && d->hidden_dims[0] == 0));
-}
-}  // namespace rcb
 
 namespace {
 
@@ -340,127 +335,27 @@ __global__ void __launch_bounds__(256) siren_kernel(SirenArgs a) {
 }
 
 
-template <int NH, int KS0, int NB0, int MODE>
-int launch(const SirenArgs& a, size_t smem_bytes, hipStream_t st) {
-    auto kfn = siren_kernel<NH, KS0, NB0, MODE>;
-  // (per launch: the attribute belongs to the (function, device) pair; a process may drive several devices)
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     160 * 1024);
-  if (e != hipSuccess) return fail((int)e, "siren: hipFuncSetAttribute: %s", hipGetErrorString(e));
-  kfn<<<a.G, 256, smem_bytes, st>>>(a);
-  RCB_LAUNCH_CHECK();
-  return RCB_OK;
-}
+// what an entry passes besides the descriptor
+struct SirenPtrs {
+  const float *xf; const void* pe; const float *wvec, *yin;   // yin: rcb_siren_bwd dy, rcb_siren_loss_bwd target
+  float *yout, *sse, *dwvec; void* dpe; float dy_scale;
+};
 
-template <int MODE>
-int dispatch(const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
-  // fp32 at other widths / per-layer widths / 5..7 hidden layers: siren_mlp_generic.hip
-  if (d->hidden != HID || d->hidden_dims[0] != 0 || d->n_hidden > 4) return siren_generic_dispatch(MODE, d, a, st);
-  const int in0 = d->fourier_dim + d->pe_dim;
-  const int ks = d->fourier_dim > d->pe_dim ? d->fourier_dim : d->pe_dim;
-  const int nb0 = (in0 + 31) / 32;
-  const int NL = d->n_hidden + 1;
-  int dnet = 0, wt = 0;
-  for (int l = 0; l < NL; ++l) {
-    int li = l == 0 ? in0 : HID, lo = l == NL - 1 ? d->out_dim : HID;
-    dnet += lo * (li + 1);
-    wt += lo * li;
-  }
-  a.dnet = dnet;
-  a.wt_total = wt;
-  a.tile_base = (dnet + wt + 3) & ~3;
-  int need = a.tile_base + 4 * (32 + 32 * nb0) * TS;
-  if (need < 4 * dnet) need = 4 * dnet;
-  need = (need + 3) & ~3;
-  a.smem_floats = need;
-  size_t smem = (size_t)need * sizeof(float);
-  RCB_REQUIRE(smem <= 160 * 1024, RCB_ERR_UNSUPPORTED, "siren: %zu B of LDS needed", smem);
-#define RCB_SIREN_CASE(NHv, KSv, NBv)                                       \
-  if (d->n_hidden == NHv && ks <= KSv && nb0 == NBv) return launch<NHv, KSv, NBv, MODE>(a, smem, st);
-  RCB_SIREN_CASE(3, 16, 1)
-  RCB_SIREN_CASE(2, 16, 1)
-  RCB_SIREN_CASE(3, 18, 2)
-  RCB_SIREN_CASE(1, 16, 1)
-  RCB_SIREN_CASE(4, 16, 1)
-  RCB_SIREN_CASE(3, 32, 2)
-#undef RCB_SIREN_CASE
-  return fail(RCB_ERR_UNSUPPORTED, "siren: no kernel for n_hidden=%d, F=%d, E=%d", d->n_hidden, d->fourier_dim, d->pe_dim);
-}
-
-int fill_args(const rcb_siren_desc* d, SirenArgs& a) {
-  RCB_REQUIRE(d, RCB_ERR_ARG, "siren: null descriptor");
-  RCB_REQUIRE(d->hidden == HID || (d->precision >= 1 && (d->hidden == 16 || d->hidden == 24 || d->hidden == 48 || d->hidden == 64)) ||
-                  (d->precision == 0 && d->hidden >= 1 && d->hidden <= 64),
-              RCB_ERR_UNSUPPORTED, "siren: hidden width %d (fp32 mode: up to 64; 16-bit modes: 16, 24, 32, 48, 64)", d->hidden);
-  RCB_REQUIRE(d->n_hidden >= 1 && d->n_hidden <= 7, RCB_ERR_UNSUPPORTED,
-              "siren: n_hidden=%d (1..7 hidden layers: the A transform takes up to 8 linear layers)", d->n_hidden);
-  RCB_REQUIRE(d->n_hidden <= 4 || d->hidden_dims[0] == 0, RCB_ERR_UNSUPPORTED,
-              "siren: per-layer hidden widths exist for 1..4 hidden layers only (5..7 layers take one width)");
-  RCB_REQUIRE(d->n_hidden <= 4 || d->precision == 0 || d->hidden == 16 || d->hidden == 24 || d->hidden == HID, RCB_ERR_UNSUPPORTED,
-              "siren: hidden width %d at %d hidden layers (16-bit modes: 16, 24 or 32 beyond 4 layers)", d->hidden, d->n_hidden);
-  RCB_REQUIRE(d->hidden_dims[0] == 0 || d->precision == 0, RCB_ERR_UNSUPPORTED,
-              "siren: per-layer hidden widths exist in the fp32 mode only (the 16-bit kernels take one width: 16, 24, 32, 48 or 64)");
-  RCB_REQUIRE(d->out_dim >= 1 && d->out_dim <= 32, RCB_ERR_UNSUPPORTED, "siren: out_dim=%d", d->out_dim);
-  RCB_REQUIRE(d->fourier_dim >= 1 && d->pe_dim >= 0 && d->fourier_dim + d->pe_dim <= 64, RCB_ERR_UNSUPPORTED,
-              "siren: F=%d E=%d", d->fourier_dim, d->pe_dim);
-  RCB_REQUIRE(d->fourier_dim % 2 == 0 && d->pe_dim % 2 == 0, RCB_ERR_UNSUPPORTED, "siren: odd feature dims");
-  RCB_REQUIRE(d->n_rows > 0 && d->samples > 0 && d->n_pix > 0 && d->n_rows % d->samples == 0, RCB_ERR_SHAPE,
-              "siren: rows=%d samples=%d pix=%d", d->n_rows, d->samples, d->n_pix);
-  RCB_REQUIRE(d->precision >= 0 && d->precision <= 2, RCB_ERR_UNSUPPORTED, "siren: precision %d not built", d->precision);
-  RCB_REQUIRE((long long)d->n_pix * d->out_dim < (1ll << 31), RCB_ERR_SHAPE, "siren: n_pix x out_dim = %lld elements per row of targets (32-bit offsets inside a row)",
-              (long long)d->n_pix * d->out_dim);
-  RCB_REQUIRE(d->pe_bf16 == 0 || (d->pe_bf16 == 1 && d->precision >= 1 && d->pe_dim % 8 == 0), RCB_ERR_UNSUPPORTED,
-              "siren: bf16 pe storage needs a 16-bit precision mode and pe_dim %% 8 == 0 (precision=%d, E=%d)", d->precision,
-              d->pe_dim);
-  RCB_REQUIRE(d->dw_bf16 == nullptr || d->precision >= 1, RCB_ERR_UNSUPPORTED,
-              "siren: the bf16 copy of the gradient exists in the 16-bit kernels only");
-  RCB_REQUIRE(d->dw_lo == nullptr || d->dw_bf16 != nullptr, RCB_ERR_ARG, "siren: dw_lo (low plane) comes with dw_bf16 (high plane)");
-  {
-    const int nl = d->n_hidden + 1;
-    long long dn = 0;
-    for (int l = 0; l < nl; ++l) {
-      const int hw_in = l == 0 ? 0 : (d->hidden_dims[0] ? d->hidden_dims[l - 1] : d->hidden);
-      const int hw_out = d->hidden_dims[0] && l < d->n_hidden ? d->hidden_dims[l] : d->hidden;
-      const int li = l == 0 ? d->fourier_dim + d->pe_dim : hw_in, lo = l == nl - 1 ? d->out_dim : hw_out;
-      dn += (long long)lo * (li + 1);
-    }
-    RCB_REQUIRE(d->w_row_stride >= dn, RCB_ERR_SHAPE, "siren: w_row_stride %lld below the %lld elements of a row of layer vectors",
-                (long long)d->w_row_stride, dn);
-    // (a C caller that sets dw_bf16 but leaves the stride field zero would make every row of the copy overlap)
-    RCB_REQUIRE(d->dw_bf16 == nullptr || d->dw_bf16_stride >= dn, RCB_ERR_SHAPE,
-                "siren: dw_bf16_stride %lld below the %lld elements of a row of layer vectors", (long long)d->dw_bf16_stride, dn);
-  }
-  const int chunks = d->pixel_chunks > 1 ? d->pixel_chunks : 1;
-  RCB_REQUIRE(chunks == 1 || (d->precision >= 1 && chunks <= (d->n_pix + 31) / 32 && d->dw_bf16 == nullptr &&
-                              (long long)d->n_rows * chunks < (1ll << 30)),
-              RCB_ERR_UNSUPPORTED,
-              "siren: pixel_chunks=%d needs a 16-bit precision mode, at most one chunk per 32-pixel tile and dw_bf16 == NULL "
-              "(rcb_siren_reduce_chunks emits it)", d->pixel_chunks);
-  memset(&a, 0, sizeof(a));
+// the kernel argument block of a descriptor siren_check_desc accepted
+void fill_args(const rcb_siren_desc* d, const SirenLayers& L, const SirenPtrs& p, SirenArgs& a) {
+  a = SirenArgs{p.xf, static_cast<const float*>(p.pe), p.wvec, p.yin, p.yout, p.sse, p.dwvec, static_cast<float*>(p.dpe)};   // the rest: zero
+  a.dy_scale = p.dy_scale;
   if (d->pe_grid_dims != 0) {
-    const int nd = d->pe_grid_dims;
-    RCB_REQUIRE(nd >= 1 && nd <= 3 && d->precision >= 1 && d->pe_dim > 0, RCB_ERR_UNSUPPORTED,
-                "siren: pe_grid_dims=%d (1..3, 16-bit kernels, pe_dim > 0)", nd);
-    long long np = 1, pp = 1;
-    for (int i = 0; i < 3; ++i) a.pe_pn[i] = a.pe_ps[i] = 1;
-    for (int i = 0; i < nd; ++i) {                                  // right-aligned: unused leading axes are 1
-      RCB_REQUIRE(d->pe_patch_nums[i] >= 1 && d->pe_patch_size[i] >= 1, RCB_ERR_SHAPE, "siren: stitched pe axis %d: %d x %d", i,
-                  d->pe_patch_nums[i], d->pe_patch_size[i]);
-      a.pe_pn[3 - nd + i] = d->pe_patch_nums[i];
-      a.pe_ps[3 - nd + i] = d->pe_patch_size[i];
-      np *= d->pe_patch_nums[i];
-      pp *= d->pe_patch_size[i];
-    }
-    RCB_REQUIRE(pp == d->n_pix && (d->n_rows / d->samples) % np == 0 && pp * 4096 < (1ll << 32) && a.pe_ps[1] <= 4096 &&
-                    a.pe_ps[2] <= 4096,
-                RCB_ERR_SHAPE, "siren: stitched pe layout: patch of %lld pixels for n_pix=%d, %lld patches per datapoint for %d INRs",
-                pp, d->n_pix, np, d->n_rows / d->samples);
-    a.pe_nd = nd;
-    a.pe_ndc = (int)((d->n_rows / d->samples) / np);
+    const SirenPeGrid g = siren_pe_grid(d);
+    for (int i = 0; i < 3; ++i) a.pe_pn[i] = g.pn[i], a.pe_ps[i] = g.ps[i];
+    a.pe_nd = d->pe_grid_dims;
+    a.pe_ndc = (int)((d->n_rows / d->samples) / g.np);
     a.pe_m1 = (unsigned)(((1ull << 32) + a.pe_ps[1] - 1) / a.pe_ps[1]);
     a.pe_m2 = (unsigned)(((1ull << 32) + a.pe_ps[2] - 1) / a.pe_ps[2]);
   }
-  a.chunks = chunks;
+  a.dnet = (int)L.dnet;
+  a.wt_total = (int)L.wt;
+  a.chunks = d->pixel_chunks > 1 ? d->pixel_chunks : 1;
   a.pe_bf16 = d->pe_bf16;
   a.dw16 = reinterpret_cast<__bf16*>(d->dw_bf16);
   a.dwlo = reinterpret_cast<__bf16*>(d->dw_lo);
@@ -479,7 +374,28 @@ int fill_args(const rcb_siren_desc* d, SirenArgs& a) {
   double k = (double)d->w0 / (2.0 * 3.14159265358979323846);
   a.k_hi = (float)k;
   a.k_lo = (float)(k - (double)a.k_hi);
-  return RCB_OK;
+}
+
+// The one body of rcb_siren_fwd / _bwd / _loss_bwd: check the descriptor, fill the arguments, check the pointers, route, launch.
+int siren_run(int mode, const rcb_siren_desc* d, const SirenPtrs& p, hipStream_t st) {
+  static const char* const who[] = {"siren_fwd", "siren_bwd", "siren_loss_bwd"};
+  SirenLayers L;
+  const int rc = siren_check_desc(d, L);
+  if (rc) return rc;
+  SirenArgs a;
+  fill_args(d, L, p, a);
+  RCB_REQUIRE(p.xf && p.wvec && (mode == MODE_FWD ? p.yout != nullptr : p.yin != nullptr) && (mode != MODE_LOSS || p.sse) &&
+                  (p.pe || d->pe_dim == 0),
+              RCB_ERR_ARG, "%s: null pointer", who[mode]);
+  RCB_REQUIRE(mode == MODE_FWD || p.dwvec || (d->dw_bf16 && d->dw_lo && a.chunks == 1), RCB_ERR_ARG,
+              "%s: dwvec may be NULL only when both planes (dw_bf16, dw_lo) receive the gradient of an unchunked launch", who[mode]);
+  static const bool dealt32 = getenv("RCB_SIREN_W32_DEALT") != nullptr;   // (A/B runs; only a -DRCB_SIREN_DEALT32 build looks at it)
+  // (the device is asked only where the route looks at the answer: the wave family's fill rule, width-32 bf16 loss / backward)
+  const int n_cu = mode != MODE_FWD && d->precision == 1 && d->hidden == HID ? cu_count() : 0;
+  const SirenRoute r = siren_route(d, mode, a.dpe != nullptr, a.pe_bf16 && a.xf16 != nullptr, siren_wave_tiles(), n_cu, dealt32);
+  static SirenLaunch* const launch[] = {nullptr,           siren_fp32_launch, siren_generic_launch, siren_bf16_launch,
+                                        siren_wave_launch, siren_wide_launch, siren_rowwave_launch};   // by SirenFamily
+  return r.family == SIREN_REFUSED ? fail(r.code, "%s", r.text) : launch[r.family](mode, d, r, a, st);
 }
 
 // ---- sum of the per-chunk partials of a pixel_chunks launch (fixed chunk order: deterministic) ------------------------------
@@ -515,61 +431,43 @@ __global__ void __launch_bounds__(256) siren_reduce_chunks_kernel(ReduceArgs r) 
 
 }  // namespace
 
+namespace rcb {
+int siren_fp32_launch(int mode, const rcb_siren_desc*, const SirenRoute& r, SirenArgs& a, hipStream_t st) {
+  const int nb0 = r.p[2];
+  a.tile_base = (a.dnet + a.wt_total + 3) & ~3;
+  int need = a.tile_base + 4 * (32 + 32 * nb0) * TS;
+  if (need < 4 * a.dnet) need = 4 * a.dnet;
+  need = (need + 3) & ~3;
+  a.smem_floats = need;
+  const size_t smem = (size_t)need * sizeof(float);
+  RCB_REQUIRE(smem <= SIREN_LDS_MAX, RCB_ERR_UNSUPPORTED, "siren: %zu B of LDS needed", smem);
+  auto launch = [&](void (*k)(SirenArgs)) { return siren_launch(k, a.G, 256, smem, SIREN_LDS_MAX, "siren", st, a); };
+#define RCB_SIREN_CASE(NHv, KSv, NBv)                                                              \
+  if (r.p[0] == NHv && r.p[1] == KSv && r.p[2] == NBv)                                             \
+    return launch(mode == MODE_FWD ? siren_kernel<NHv, KSv, NBv, MODE_FWD>                         \
+                                   : mode == MODE_BWD ? siren_kernel<NHv, KSv, NBv, MODE_BWD> : siren_kernel<NHv, KSv, NBv, MODE_LOSS>);
+  RCB_SIREN_FP32_INSTANCES(RCB_SIREN_CASE)
+#undef RCB_SIREN_CASE
+  return fail(RCB_ERR_UNSUPPORTED, "siren: the route names an fp32 instance that is not built");
+}
+}  // namespace rcb
+
 extern "C" int rcb_siren_fwd(const rcb_siren_desc* d, const float* xf, const void* pe, const float* wvec,
                              float* y_out, rcb_stream_t stream) {
-  SirenArgs a;
-  int rc = fill_args(d, a);
-  if (rc) return rc;
-  RCB_REQUIRE(xf && wvec && y_out && (pe || d->pe_dim == 0), RCB_ERR_ARG, "siren_fwd: null pointer");
-  a.xf = xf;
-  a.pe = static_cast<const float*>(pe);
-  a.wvec = wvec;
-  a.yout = y_out;
-  if (siren_rowwave(d)) return siren_rowwave_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
-  if (d->precision >= 1) return siren_16bit_dispatch(MODE_FWD, d, a, (hipStream_t)stream);
-  return dispatch<MODE_FWD>(d, a, (hipStream_t)stream);
+  return siren_run(MODE_FWD, d, SirenPtrs{xf, pe, wvec, nullptr, y_out, nullptr, nullptr, nullptr, 0.f}, (hipStream_t)stream);
 }
 
 extern "C" int rcb_siren_bwd(const rcb_siren_desc* d, const float* xf, const void* pe, const float* wvec,
                              const float* dy, float* dwvec, void* dpe, rcb_stream_t stream) {
-  SirenArgs a;
-  int rc = fill_args(d, a);
-  if (rc) return rc;
-  RCB_REQUIRE(xf && wvec && dy && (pe || d->pe_dim == 0), RCB_ERR_ARG, "siren_bwd: null pointer");
-  RCB_REQUIRE(dwvec || (d->dw_bf16 && d->dw_lo && a.chunks == 1), RCB_ERR_ARG,
-              "siren_bwd: dwvec may be NULL only when both planes (dw_bf16, dw_lo) receive the gradient of an unchunked launch");
-  a.xf = xf;
-  a.pe = static_cast<const float*>(pe);
-  a.wvec = wvec;
-  a.yin = dy;
-  a.dwvec = dwvec;
-  a.dpe = static_cast<float*>(dpe);
-  if (siren_rowwave(d)) return siren_rowwave_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
-  if (d->precision >= 1) return siren_16bit_dispatch(MODE_BWD, d, a, (hipStream_t)stream);
-  return dispatch<MODE_BWD>(d, a, (hipStream_t)stream);
+  return siren_run(MODE_BWD, d, SirenPtrs{xf, pe, wvec, dy, nullptr, nullptr, dwvec, dpe, 0.f}, (hipStream_t)stream);
 }
 
 extern "C" int rcb_siren_loss_bwd(const rcb_siren_desc* d, const float* xf, const void* pe, const float* wvec,
                                   const float* target, float dy_scale, float* sse, float* dwvec, void* dpe,
                                   rcb_stream_t stream) {
-  SirenArgs a;
-  int rc = fill_args(d, a);
-  if (rc) return rc;
-  RCB_REQUIRE(xf && wvec && target && sse && (pe || d->pe_dim == 0), RCB_ERR_ARG, "siren_loss_bwd: null pointer");
-  RCB_REQUIRE(dwvec || (d->dw_bf16 && d->dw_lo && a.chunks == 1), RCB_ERR_ARG,
-              "siren_loss_bwd: dwvec may be NULL only when both planes (dw_bf16, dw_lo) receive the gradient of an unchunked launch");
-  a.xf = xf;
-  a.pe = static_cast<const float*>(pe);
-  a.wvec = wvec;
-  a.yin = target;
-  a.sse = sse;
-  a.dwvec = dwvec;
-  a.dpe = static_cast<float*>(dpe);
-  a.dy_scale = dy_scale;
-  if (siren_rowwave(d)) return siren_rowwave_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
-  if (d->precision >= 1) return siren_16bit_dispatch(MODE_LOSS, d, a, (hipStream_t)stream);
-  return dispatch<MODE_LOSS>(d, a, (hipStream_t)stream);
+  return siren_run(MODE_LOSS, d, SirenPtrs{xf, pe, wvec, target, nullptr, sse, dwvec, dpe, dy_scale}, (hipStream_t)stream);
 }
+
 
 extern "C" int rcb_siren_reduce_chunks(const rcb_siren_desc* d, const float* dw_partial, const float* sse_partial, float* dwvec,
                                        float* sse, rcb_stream_t stream) {
@@ -590,13 +488,7 @@ extern "C" int rcb_siren_reduce_chunks(const rcb_siren_desc* d, const float* dw_
   r.stride = d->w_row_stride;
   r.G = d->n_rows;
   r.chunks = d->pixel_chunks;
-  const int nl = d->n_hidden + 1;
-  int o = 0;
-  for (int l = 0; l < nl; ++l) {
-    const int li = l == 0 ? d->fourier_dim + d->pe_dim : d->hidden, lo = l == nl - 1 ? d->out_dim : d->hidden;
-    o += lo * (li + 1);
-  }
-  r.dnet = o;
+  r.dnet = (int)siren_layers(d).dnet;
   RCB_REQUIRE(r.dw16 == nullptr || r.stride16 >= r.dnet, RCB_ERR_SHAPE, "siren_reduce_chunks: bf16 row stride %lld < %d", r.stride16, r.dnet);
   RCB_REQUIRE(r.stride >= r.dnet, RCB_ERR_SHAPE, "siren_reduce_chunks: row stride %lld < %d", r.stride, r.dnet);
   const long long total = (long long)r.G * r.dnet;

@@ -694,43 +694,25 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
   }
 }
 
-template <typename T, int NH, int F, int E, int C, int MODE, bool IN16>
-int launch_one(const SirenArgs& a, hipStream_t st) {
-  using G = Geo<NH, F, E, C>;
-    auto kfn = siren_bf16_kernel<T, NH, F, E, C, MODE, IN16>;
-  // (per launch: the attribute belongs to the (function, device) pair; a process may drive several devices)
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     160 * 1024);
-  if (e != hipSuccess) return fail((int)e, "siren(bf16): hipFuncSetAttribute: %s", hipGetErrorString(e));
-  kfn<<<a.G * a.chunks, 256, G::LDS_BYTES, st>>>(a);
-  RCB_LAUNCH_CHECK();
-  return RCB_OK;
-}
-
+// the four instances of one geometry and operand type (siren_launch_mode)
 template <typename T, int NH, int F, int E, int C>
-int launch_mode(int mode, const SirenArgs& a, hipStream_t st) {
-  // both input halves as 16-bit rows: pe stored as bf16, a 16-bit copy of xf in the operand format supplied (rows padded to 8 features)
-  constexpr bool can16 = (E % 8 == 0) && E > 0;
-  if (can16 && a.pe_bf16 && a.xf16 != nullptr && mode == MODE_LOSS) return launch_one<T, NH, F, E, C, MODE_LOSS, can16>(a, st);
-  if (mode == MODE_FWD) return launch_one<T, NH, F, E, C, MODE_FWD, false>(a, st);
-  if (mode == MODE_BWD) return launch_one<T, NH, F, E, C, MODE_BWD, false>(a, st);
-  return launch_one<T, NH, F, E, C, MODE_LOSS, false>(a, st);
+int launch_mode(int mode, bool in16, const SirenArgs& a, hipStream_t st) {
+  return siren_launch_mode<E>(mode, in16, [&](auto mode_c, auto in16_c) {
+    return siren_launch(siren_bf16_kernel<T, NH, F, E, C, decltype(mode_c)::value, decltype(in16_c)::value>, a.G * a.chunks, 256,
+                        Geo<NH, F, E, C>::LDS_BYTES, SIREN_LDS_MAX, "siren(bf16)", st, a);
+  });
 }
 
 }  // namespace
 
 namespace rcb {
-int siren_bf16_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
+int siren_bf16_launch(int mode, const rcb_siren_desc* d, const SirenRoute& r, SirenArgs& a, hipStream_t st) {
 #define RCB_CASE(NHv, Fv, Ev, Cv)                                                                   \
-  if (d->n_hidden == NHv && d->fourier_dim == Fv && d->pe_dim == Ev && d->out_dim == Cv)              \
-    return d->precision == 2 ? launch_mode<_Float16, NHv, Fv, Ev, Cv>(mode, a, st)                  \
-                             : launch_mode<__bf16, NHv, Fv, Ev, Cv>(mode, a, st);
-  RCB_CASE(3, 16, 16, 3)   // cifar / kodak / protein
-  RCB_CASE(3, 16, 16, 1)   // audio
-  RCB_CASE(3, 18, 16, 3)   // video
-  RCB_CASE(2, 16, 16, 3)   // 2 hidden layers
+  if (r.p[0] == NHv && r.p[1] == Fv && r.p[2] == Ev && r.p[3] == Cv)                                  \
+    return d->precision == 2 ? launch_mode<_Float16, NHv, Fv, Ev, Cv>(mode, r.in16, a, st)          \
+                             : launch_mode<__bf16, NHv, Fv, Ev, Cv>(mode, r.in16, a, st);
+  RCB_SIREN_WG_INSTANCES(RCB_CASE)
 #undef RCB_CASE
-  return fail(RCB_ERR_UNSUPPORTED, "siren(bf16): geometry n_hidden=%d F=%d E=%d C=%d is not instantiated", d->n_hidden,
-              d->fourier_dim, d->pe_dim, d->out_dim);
+  return fail(RCB_ERR_UNSUPPORTED, "siren(bf16): the route names an instance that is not built");
 }
 }  // namespace rcb

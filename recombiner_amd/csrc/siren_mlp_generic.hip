@@ -207,46 +207,22 @@ __global__ void __launch_bounds__(256) siren_generic_kernel(SirenArgs a, GenGeo 
   }
 }
 
-template <int MODE, int ML>
-int launch_generic(const SirenArgs& a, const GenGeo& geo, hipStream_t st) {
-  auto kfn = siren_generic_kernel<MODE, ML>;
-  // per launch, not once per process: the attribute belongs to the (function, device) pair and a process may drive
-  // several devices or call from several threads; the call is a table write
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return fail((int)e, "siren(generic): hipFuncSetAttribute: %s", hipGetErrorString(e));
-  kfn<<<a.G, 256, (size_t)geo.total * sizeof(float), st>>>(a, geo);
-  RCB_LAUNCH_CHECK();
-  return RCB_OK;
-}
-
 }  // namespace
 
 namespace rcb {
-int siren_generic_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
-  RCB_REQUIRE(d->precision == 0 && d->hidden >= 1 && d->hidden <= GEN_MAXW && d->n_hidden + 1 <= GEN_MAXL && d->out_dim <= 32 &&
-                  d->pixel_chunks <= 1,
-              RCB_ERR_UNSUPPORTED, "siren(generic fp32): hidden=%d n_hidden=%d out_dim=%d pixel_chunks=%d", d->hidden, d->n_hidden,
-              d->out_dim, d->pixel_chunks);
+// widths 1 .. 64 per hidden layer and up to 8 linear layers: siren_route names this family only for such descriptors
+int siren_generic_launch(int mode, const rcb_siren_desc* d, const SirenRoute&, SirenArgs& a, hipStream_t st) {
+  const SirenLayers L = siren_layers(d);
   GenGeo geo;
   geo.NH = d->n_hidden;
-  geo.in0 = d->fourier_dim + d->pe_dim;
-  const bool listed = d->hidden_dims[0] != 0;
+  geo.in0 = (int)L.in[0];
   geo.W = 0;
-  for (int l = 0; l < geo.NH; ++l) {
-    geo.wid[l] = listed ? d->hidden_dims[l] : d->hidden;
-    RCB_REQUIRE(geo.wid[l] >= 1 && geo.wid[l] <= GEN_MAXW, RCB_ERR_UNSUPPORTED, "siren(generic fp32): hidden layer %d is %d wide (1..%d)", l,
-                geo.wid[l], GEN_MAXW);
-    geo.W = geo.wid[l] > geo.W ? geo.wid[l] : geo.W;
-  }
-  geo.wid[geo.NH] = d->out_dim;
-  int o = 0;
   for (int l = 0; l <= geo.NH; ++l) {
-    geo.off[l] = o;
-    const int li = l == 0 ? geo.in0 : geo.wid[l - 1], lo = geo.wid[l];
-    o += lo * (li + 1);
+    geo.wid[l] = (int)L.out[l];
+    geo.off[l] = (int)L.off[l];
+    if (l < geo.NH && geo.wid[l] > geo.W) geo.W = geo.wid[l];
   }
-  geo.dnet = o;
-  a.dnet = o;
+  geo.dnet = a.dnet;
   geo.x0s = geo.in0 | 1;
   geo.ws = (geo.W > d->out_dim ? geo.W : d->out_dim) | 1;
   int f = (geo.dnet + 3) & ~3;
@@ -263,15 +239,12 @@ int siren_generic_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipS
   geo.red = f;
   f += 256;
   geo.total = f;
-  RCB_REQUIRE((size_t)f * sizeof(float) <= 160 * 1024, RCB_ERR_UNSUPPORTED, "siren(generic fp32): %zu B of LDS needed",
-              (size_t)f * sizeof(float));
-  if (geo.NH + 1 > MAXL) {
-    if (mode == MODE_FWD) return launch_generic<MODE_FWD, GEN_MAXL>(a, geo, st);
-    if (mode == MODE_BWD) return launch_generic<MODE_BWD, GEN_MAXL>(a, geo, st);
-    return launch_generic<MODE_LOSS, GEN_MAXL>(a, geo, st);
-  }
-  if (mode == MODE_FWD) return launch_generic<MODE_FWD, MAXL>(a, geo, st);
-  if (mode == MODE_BWD) return launch_generic<MODE_BWD, MAXL>(a, geo, st);
-  return launch_generic<MODE_LOSS, MAXL>(a, geo, st);
+  const size_t lds = (size_t)f * sizeof(float);
+  RCB_REQUIRE(lds <= SIREN_LDS_MAX, RCB_ERR_UNSUPPORTED, "siren(generic fp32): %zu B of LDS needed", lds);
+  auto launch = [&](void (*k)(SirenArgs, GenGeo)) { return siren_launch(k, a.G, 256, lds, SIREN_LDS_MAX, "siren(generic)", st, a, geo); };
+  const bool deep = geo.NH + 1 > MAXL;
+  if (mode == MODE_FWD) return launch(deep ? siren_generic_kernel<MODE_FWD, GEN_MAXL> : siren_generic_kernel<MODE_FWD, MAXL>);
+  if (mode == MODE_BWD) return launch(deep ? siren_generic_kernel<MODE_BWD, GEN_MAXL> : siren_generic_kernel<MODE_BWD, MAXL>);
+  return launch(deep ? siren_generic_kernel<MODE_LOSS, GEN_MAXL> : siren_generic_kernel<MODE_LOSS, MAXL>);
 }
 }  // namespace rcb

@@ -736,59 +736,22 @@ int launch(int mode, const SirenArgs& a, hipStream_t st) {
   using G = Geo<NH, HW, KS>;
   using Store = std::conditional_t<(NH <= 4), RegStore<T, G>, LdsStore<T, G>>;
   const size_t lds = Store::lds_bytes(a.dnet);
-  if (mode == MODE_FWD) siren_rowwave_kernel<T, NH, HW, KS, true, Store><<<a.G * a.chunks, 64, lds, st>>>(a);
-  else siren_rowwave_kernel<T, NH, HW, KS, false, Store><<<a.G * a.chunks, 64, lds, st>>>(a);
-  RCB_LAUNCH_CHECK();
-  return RCB_OK;
-}
-
-template <typename T, int HW, int KS>
-int launch_nh(int mode, int nh, const SirenArgs& a, hipStream_t st) {
-  if constexpr (HW < 32) {          // 1 .. 4 layers of width 32 belong to the workgroup and wave families
-    switch (nh) {
-      case 1: return launch<T, 1, HW, KS>(mode, a, st);
-      case 2: return launch<T, 2, HW, KS>(mode, a, st);
-      case 3: return launch<T, 3, HW, KS>(mode, a, st);
-      case 4: return launch<T, 4, HW, KS>(mode, a, st);
-      default: break;
-    }
-  }
-  switch (nh) {
-    case 5: return launch<T, 5, HW, KS>(mode, a, st);
-    case 6: return launch<T, 6, HW, KS>(mode, a, st);
-    case 7: return launch<T, 7, HW, KS>(mode, a, st);
-    default: return rcb::fail(RCB_ERR_UNSUPPORTED, "siren: no one-wave-per-row instance for %d hidden layers of width %d", nh, HW);
-  }
-}
-
-template <typename T>
-int launch_t(int mode, const rcb_siren_desc* d, const SirenArgs& a, hipStream_t st) {
-  const bool small = d->fourier_dim <= 16 && d->pe_dim <= 16 && d->out_dim <= 16;
-  const int nh = d->n_hidden;
-  if (d->hidden == 16) return small ? launch_nh<T, 16, 1>(mode, nh, a, st) : launch_nh<T, 16, 2>(mode, nh, a, st);
-  if (d->hidden == 24) return small ? launch_nh<T, 24, 1>(mode, nh, a, st) : launch_nh<T, 24, 2>(mode, nh, a, st);
-  return small ? launch_nh<T, 32, 1>(mode, nh, a, st) : launch_nh<T, 32, 2>(mode, nh, a, st);
+  if (mode == MODE_FWD) return siren_launch(siren_rowwave_kernel<T, NH, HW, KS, true, Store>, a.G * a.chunks, 64, lds, 0, "siren(rowwave)", st, a);
+  return siren_launch(siren_rowwave_kernel<T, NH, HW, KS, false, Store>, a.G * a.chunks, 64, lds, 0, "siren(rowwave)", st, a);
 }
 
 }  // namespace
 
 namespace rcb {
 // 16-bit modes, one width for every hidden layer: 1 .. 4 layers of width 16 / 24 (narrow), 5 .. 7 layers of width 16 / 24 / 32
-// (deep); the descriptor is checked by siren_mlp.hip's fill_args
-int siren_rowwave_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
-  const int nh = d->n_hidden, hw = d->hidden;
-  const char* fam = nh >= 5 ? "deep" : "narrow";
-  RCB_REQUIRE(nh >= 1 && nh <= 7 && (hw == 16 || hw == 24 || (hw == 32 && nh >= 5)) && d->hidden_dims[0] == 0, RCB_ERR_UNSUPPORTED,
-              "siren(%s): %d hidden layers of width %d (1..4 layers of one width 16 or 24, 5..7 layers of one width 16, 24 or 32)", fam,
-              nh, hw);
-  RCB_REQUIRE(d->fourier_dim <= 32 && d->pe_dim <= 32 && d->out_dim <= 32, RCB_ERR_UNSUPPORTED,
-              "siren(%s): F=%d E=%d C=%d (the one-wave-per-row kernels take up to 32 features from each input half and 32 outputs)", fam,
-              d->fourier_dim, d->pe_dim, d->out_dim);
-  RCB_REQUIRE(d->clock_probe == nullptr, RCB_ERR_UNSUPPORTED, "siren(%s): clock_probe exists in the width-32 kernel of 1..4 layers only", fam);
-  RCB_REQUIRE(mode != MODE_LOSS || a.sse != nullptr, RCB_ERR_ARG, "siren(%s): sse", fam);
-  const int in0 = d->fourier_dim + d->pe_dim;
-  a.dnet = hw * (in0 + 1) + (nh - 1) * hw * (hw + 1) + d->out_dim * (hw + 1);
+// (deep): RCB_SIREN_ROWWAVE_INSTANCES; siren_route refuses what the family does not take (F, E, C above 32; clock_probe)
+int siren_rowwave_launch(int mode, const rcb_siren_desc* d, const SirenRoute& r, SirenArgs& a, hipStream_t st) {
   if (mode == MODE_BWD) a.sse = nullptr;          // the kernel tells loss from backward by the sse pointer
-  return d->precision == 2 ? launch_t<_Float16>(mode, d, a, st) : launch_t<__bf16>(mode, d, a, st);
+#define RCB_CASE(NHv, HWv, KSv)                                  \
+  if (r.p[0] == NHv && r.p[1] == HWv && r.p[2] == KSv)           \
+    return d->precision == 2 ? launch<_Float16, NHv, HWv, KSv>(mode, a, st) : launch<__bf16, NHv, HWv, KSv>(mode, a, st);
+  RCB_SIREN_ROWWAVE_INSTANCES(RCB_CASE)
+#undef RCB_CASE
+  return fail(RCB_ERR_UNSUPPORTED, "siren(rowwave): the route names an instance that is not built");
 }
 }  // namespace rcb

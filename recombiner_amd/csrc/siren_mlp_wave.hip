@@ -853,33 +853,13 @@ extern "C" int rcb_debug_wave_stamps(unsigned long long* dst, int n_entries) {
 namespace {
 #endif
 
-// compute units of the current device (cached per device: a process may drive several)
-int cu_count() {
-  static int n_cu[64];
-  int dev_id = 0;
-  if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) dev_id = 0;
-  if (n_cu[dev_id] == 0) {
-    hipDeviceProp_t prop;
-    n_cu[dev_id] = (hipGetDeviceProperties(&prop, dev_id) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return n_cu[dev_id];
-}
-
-template <typename T, int NH, int F, int E, int C, int MODE, bool DPE>
-int launch_wave(const SirenArgs& a, hipStream_t st) {
-  using G = WGeo<NH, F, E, C>;
-  auto kfn = siren_wave_kernel<T, NH, F, E, C, MODE, DPE>;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e != hipSuccess) return fail((int)e, "siren(wave): hipFuncSetAttribute: %s", hipGetErrorString(e));
+int launch_wave(void (*kernel)(SirenArgs), size_t lds_bytes, const SirenArgs& a, hipStream_t st, int n_cu) {
   const long long units = (long long)a.G * a.chunks;
   long long blocks = (units + 3) / 4;
-  const int cus = cu_count();
   static const long long cap_env = getenv("RCB_WAVE_BLOCKS") ? atoll(getenv("RCB_WAVE_BLOCKS")) : 0;   // (A/B runs)
-  const long long cap = cap_env > 0 ? cap_env : 2ll * cus;
+  const long long cap = cap_env > 0 ? cap_env : 2ll * n_cu;
   if (blocks > cap) blocks = cap;                       // two workgroups (four independent waves each) per CU
-  kfn<<<(unsigned)blocks, 256, G::LDS_BYTES, st>>>(a);
-  RCB_LAUNCH_CHECK();
-  return RCB_OK;
+  return siren_launch(kernel, (unsigned)blocks, 256, lds_bytes, SIREN_LDS_MAX, "siren(wave)", st, a);
 }
 
 }  // namespace
@@ -896,32 +876,18 @@ int& siren_wave_tiles() {
   }();
   return v;
 }
-// *taken = true when this family has an instance for the request (the launch result is returned); otherwise the workgroup
-// kernel (siren_mlp_bf16.hip) runs it
-int siren_wave_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st, int variant, bool* taken) {
-  *taken = false;
-  if (mode == MODE_FWD || d->precision != 1 || !a.pe_bf16 || a.xf16 == nullptr || d->hidden != HID || (a.P & 31) != 0 || a.pe_nd != 0)
-    return RCB_OK;
-  {
-    // A wave walks whole rows: the launch is as long as the wave with the most rows.  Unless the (row, chunk) units fill the
-    // resident waves (two 4-wave workgroups per CU) to 90 % in the last round, the workgroup family -- four waves per row,
-    // any number of rows -- is the better fit (the test-time batches: 500 images x 5 samples = 2500 rows on 2048 waves).
-    const long long units = (long long)a.G * a.chunks, waves = 8ll * cu_count();
-    const long long rounds = (units + waves - 1) / waves;
-    if (variant != 2 && units * 10 < rounds * waves * 9) return RCB_OK;      // (2: forced, tests)
-  }
-#define RCB_CASE(NHv, Fv, Ev, Cv)                                                                               \
-  if (d->n_hidden == NHv && d->fourier_dim == Fv && d->pe_dim == Ev && d->out_dim == Cv) {                      \
-    *taken = true;                                                                                              \
-    if (a.dpe != nullptr)                                                                                       \
-      return mode == MODE_LOSS ? launch_wave<__bf16, NHv, Fv, Ev, Cv, MODE_LOSS, true>(a, st)                   \
-                               : launch_wave<__bf16, NHv, Fv, Ev, Cv, MODE_BWD, true>(a, st);                   \
-    return mode == MODE_LOSS ? launch_wave<__bf16, NHv, Fv, Ev, Cv, MODE_LOSS, false>(a, st)                    \
-                             : launch_wave<__bf16, NHv, Fv, Ev, Cv, MODE_BWD, false>(a, st);                    \
-  }
-  RCB_CASE(3, 16, 16, 3)
+// loss / backward of the instance siren_route chose (its fill rule decides between this family and the workgroup kernel)
+int siren_wave_launch(int mode, const rcb_siren_desc*, const SirenRoute& r, SirenArgs& a, hipStream_t st) {
+#define RCB_CASE(NHv, Fv, Ev, Cv)                                                                                     \
+  if (r.p[0] == NHv && r.p[1] == Fv && r.p[2] == Ev && r.p[3] == Cv)                                                  \
+    return launch_wave(r.dpe ? (mode == MODE_LOSS ? siren_wave_kernel<__bf16, NHv, Fv, Ev, Cv, MODE_LOSS, true>       \
+                                                  : siren_wave_kernel<__bf16, NHv, Fv, Ev, Cv, MODE_BWD, true>)       \
+                             : (mode == MODE_LOSS ? siren_wave_kernel<__bf16, NHv, Fv, Ev, Cv, MODE_LOSS, false>      \
+                                                  : siren_wave_kernel<__bf16, NHv, Fv, Ev, Cv, MODE_BWD, false>),     \
+                       WGeo<NHv, Fv, Ev, Cv>::LDS_BYTES, a, st, r.n_cu);
+  RCB_SIREN_WAVE_INSTANCES(RCB_CASE)
 #undef RCB_CASE
-  return RCB_OK;
+  return fail(RCB_ERR_UNSUPPORTED, "siren(wave): the route names an instance that is not built");
 }
 }  // namespace rcb
 

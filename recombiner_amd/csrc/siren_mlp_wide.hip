@@ -906,51 +906,26 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
   RCB_WSTAMP(7);
 }
 
-template <typename T, int NH, int F, int E, int C, int W, int MODE, bool IN16>
-int launch_one(const SirenArgs& a, hipStream_t st) {
-  using G = GeoW<NH, F, E, C, W>;
-  auto kfn = siren_wide_kernel<T, NH, F, E, C, W, MODE, IN16>;
-  // (per launch: the attribute belongs to the (function, device) pair; a process may drive several devices)
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     G::LDS_BYTES);
-  if (e != hipSuccess) return fail((int)e, "siren(wide): hipFuncSetAttribute: %s", hipGetErrorString(e));
-  kfn<<<a.G * a.chunks, 256, G::LDS_BYTES, st>>>(a);
-  RCB_LAUNCH_CHECK();
-  return RCB_OK;
-}
-
+// the four instances of one geometry and operand type (siren_launch_mode)
 template <typename T, int NH, int F, int E, int C, int W>
-int launch_mode(int mode, const SirenArgs& a, hipStream_t st) {
-  constexpr bool can16 = (E % 8 == 0) && E > 0;
-  if (can16 && a.pe_bf16 && a.xf16 != nullptr && mode == MODE_LOSS) return launch_one<T, NH, F, E, C, W, MODE_LOSS, can16>(a, st);
-  if (mode == MODE_FWD) return launch_one<T, NH, F, E, C, W, MODE_FWD, false>(a, st);
-  if (mode == MODE_BWD) return launch_one<T, NH, F, E, C, W, MODE_BWD, false>(a, st);
-  return launch_one<T, NH, F, E, C, W, MODE_LOSS, false>(a, st);
+int launch_mode(int mode, bool in16, const SirenArgs& a, hipStream_t st) {
+  return siren_launch_mode<E>(mode, in16, [&](auto mode_c, auto in16_c) {
+    using G = GeoW<NH, F, E, C, W>;
+    return siren_launch(siren_wide_kernel<T, NH, F, E, C, W, decltype(mode_c)::value, decltype(in16_c)::value>, a.G * a.chunks, 256,
+                        G::LDS_BYTES, G::LDS_BYTES, "siren(wide)", st, a);
+  });
 }
 
 }  // namespace
 
 namespace rcb {
-int siren_wide_dispatch(int mode, const rcb_siren_desc* d, SirenArgs& a, hipStream_t st) {
+int siren_wide_launch(int mode, const rcb_siren_desc* d, const SirenRoute& r, SirenArgs& a, hipStream_t st) {
 #define RCB_CASE(NHv, Fv, Ev, Cv, Wv)                                                                              \
-  if (d->n_hidden == NHv && d->fourier_dim == Fv && d->pe_dim == Ev && d->out_dim == Cv && d->hidden == Wv)          \
-    return d->precision == 2 ? launch_mode<_Float16, NHv, Fv, Ev, Cv, Wv>(mode, a, st)                             \
-                             : launch_mode<__bf16, NHv, Fv, Ev, Cv, Wv>(mode, a, st);
-#ifdef RCB_SIREN_DEALT32
-  // width 32 on this kernel (wave l owns layer l's gradient tile, three workgroups per CU): measured 0.284 ms against the
-  // 0.25 ms of siren_mlp_bf16.hip in the same back-to-back loop (4096 x 1024 px) -- eight barriers per pass are too many for
-  // its short layers -- so these instances are only built on request (-DRCB_SIREN_DEALT32, selected by RCB_SIREN_W32_DEALT=1)
-  RCB_CASE(3, 16, 16, 3, 32)
-  RCB_CASE(3, 16, 16, 1, 32)
-  RCB_CASE(3, 18, 16, 3, 32)
-  RCB_CASE(2, 16, 16, 3, 32)
-#endif
-  RCB_CASE(3, 16, 16, 3, 48)   // kodak / cifar / protein geometry at width 48
-  RCB_CASE(3, 16, 16, 3, 64)
-  RCB_CASE(3, 18, 16, 3, 64)   // video geometry at width 64
-  RCB_CASE(3, 16, 16, 1, 64)   // audio geometry at width 64
+  if (r.p[0] == NHv && r.p[1] == Fv && r.p[2] == Ev && r.p[3] == Cv && r.p[4] == Wv)                                 \
+    return d->precision == 2 ? launch_mode<_Float16, NHv, Fv, Ev, Cv, Wv>(mode, r.in16, a, st)                     \
+                             : launch_mode<__bf16, NHv, Fv, Ev, Cv, Wv>(mode, r.in16, a, st);
+  RCB_SIREN_WIDE_INSTANCES(RCB_CASE)
 #undef RCB_CASE
-  return fail(RCB_ERR_UNSUPPORTED, "siren(wide): geometry n_hidden=%d F=%d E=%d C=%d width=%d is not instantiated",
-              d->n_hidden, d->fourier_dim, d->pe_dim, d->out_dim, d->hidden);
+  return fail(RCB_ERR_UNSUPPORTED, "siren(wide): the route names an instance that is not built");
 }
 }  // namespace rcb

@@ -156,6 +156,17 @@ class PeLayout:
         return (meta.samples * (G // meta.samples // per),) + grid + (meta.pe_dim,)
 
 
+def _gradient_forms(d, G, meta, dw_bf16=None, dw_planes=None):
+    """the gradient fields of a descriptor: a bf16 copy of dwvec (rcb_siren_desc.dw_bf16), or the gradient as its (hi, lo)
+    planes (ops.Planes: dw_bf16 + dw_lo)"""
+    d.dw_bf16, d.dw_bf16_stride = (None, 0) if dw_bf16 is None else (dw_bf16.data_ptr(), int(dw_bf16.stride(0)))
+    if dw_planes is not None:
+        if (dw_planes.rows, dw_planes.cols) != (G, meta.d_net):
+            raise RcbError("siren: gradient planes do not match the rows of wvec")
+        d.dw_bf16, d.dw_lo, d.dw_bf16_stride = dw_planes.buf[0].data_ptr(), dw_planes.buf[1].data_ptr(), int(dw_planes.ld)
+    return d
+
+
 def _siren_desc(meta: SirenMeta, wvec, xf, pe=None, dw_bf16=None, chunks=1, pe_layout=None, xf16=None, dw_planes=None):
     if wvec.dim() != 2 or wvec.stride(1) != 1:
         raise RcbError("wvec must be 2-D with unit column stride")
@@ -166,12 +177,9 @@ def _siren_desc(meta: SirenMeta, wvec, xf, pe=None, dw_bf16=None, chunks=1, pe_l
         raise RcbError("rows of wvec must be a multiple of samples")
     d = SirenDesc(G, meta.samples, meta.n_pix, meta.fourier_dim, meta.pe_dim, meta.n_hidden, meta.hidden,
                   meta.out_dim, _xf_stride(xf, meta, G // meta.samples), int(wvec.stride(0)), meta.w0,
-                  meta.precision, int(pe is not None and pe.dtype == bf16), None if dw_bf16 is None else dw_bf16.data_ptr(), int(chunks), None)
-    d.dw_bf16_stride = 0 if dw_bf16 is None else int(dw_bf16.stride(0))
-    if dw_planes is not None:              # the gradient as (hi, lo) planes (ops.Planes)
-        if (dw_planes.rows, dw_planes.cols) != (G, meta.d_net):
-            raise RcbError("siren: gradient planes do not match the rows of wvec")
-        d.dw_bf16, d.dw_lo, d.dw_bf16_stride = dw_planes.buf[0].data_ptr(), dw_planes.buf[1].data_ptr(), int(dw_planes.ld)
+                  meta.precision, int(pe is not None and pe.dtype == bf16), None, int(chunks), None)
+    if dw_bf16 is not None or dw_planes is not None:
+        _gradient_forms(d, G, meta, dw_bf16, dw_planes)
     if meta.hidden_dims and len(set(meta.hidden_dims)) > 1:
         if meta.precision != 0 or len(meta.hidden_dims) != meta.n_hidden:
             raise RcbError("per-layer hidden widths: fp32 mode only, one width per hidden layer")
@@ -229,12 +237,14 @@ def siren_fwd(xf, pe, wvec, meta: SirenMeta, pixel_chunks=None, pe_layout=None):
     return y
 
 
-def _chunk_partials(chunks, G, wvec, want_sse):
-    """few rows, pixel tiles split over several workgroups per row: (partial gradients [chunks, G, stride], partial sse [chunks, G])"""
+def _grad_buffers(chunks, G, wvec, meta, want_sse, want_dw=True):
+    """-> (dw [G, d_net] with wvec's row stride, or None; the buffers of a launch of several workgroups per row, whose pixel
+    tiles are split: partial gradients [chunks, G, stride] and partial sse [chunks, G], None for one chunk)"""
+    dw = torch.empty(G, wvec.stride(0), device=wvec.device, dtype=f32)[:, :meta.d_net] if want_dw else None
     if chunks == 1:
-        return None, None
+        return dw, None, None
     part = torch.empty(chunks, G, wvec.stride(0), device=wvec.device, dtype=f32)
-    return part, (torch.empty(chunks, G, device=wvec.device, dtype=f32) if want_sse else None)
+    return dw, part, (torch.empty(chunks, G, device=wvec.device, dtype=f32) if want_sse else None)
 
 
 def _reduce_chunks(d, part, sse_part, dw, sse):
@@ -249,8 +259,7 @@ def siren_bwd(xf, pe, wvec, dy, meta: SirenMeta, want_dpe=True, pixel_chunks=Non
     _check_pe(pe, G, meta)
     if tuple(dy.shape) != (G, meta.n_pix, meta.out_dim):
         raise RcbError("dy shape mismatch")
-    dw = torch.empty(G, wvec.stride(0), device=wvec.device, dtype=f32)[:, :meta.d_net]
-    part, _ = _chunk_partials(chunks, G, wvec, False)
+    dw, part, _ = _grad_buffers(chunks, G, wvec, meta, False)
     dpe = torch.empty_like(pe) if (want_dpe and meta.pe_dim) else None
     _launch("rcb_siren_bwd", C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec),
             ptr(dy.contiguous(), f32), _dev_ptr_strided(dw if part is None else part), ptr(dpe, None, True))
@@ -295,15 +304,14 @@ def siren_loss_bwd(xf, pe, wvec, target, dy_scale: float, meta: SirenMeta, want_
     if tuple(target.shape) != (N, meta.n_pix, meta.out_dim):
         raise RcbError(f"target must be [{N},{meta.n_pix},{meta.out_dim}], got {tuple(target.shape)}")
     sse = torch.empty(G, device=wvec.device, dtype=f32)
-    dw = None if want_planes else torch.empty(G, wvec.stride(0), device=wvec.device, dtype=f32)[:, :meta.d_net]
+    dw, part, sse_part = _grad_buffers(chunks, G, wvec, meta, True, want_dw=not want_planes)
     dpe = torch.empty_like(pe) if (want_dpe and meta.pe_dim) else None
-    part, sse_part = _chunk_partials(chunks, G, wvec, True)
     _launch("rcb_siren_loss_bwd", C.byref(d), _dev_ptr_strided(xf), ptr(pe, None, True), _dev_ptr_strided(wvec), ptr(target, f32),
             dy_scale, ptr(sse if part is None else sse_part), _dev_ptr_strided(dw if part is None else part, True),
             ptr(dpe, None, True))
+    # (a chunked launch leaves the 16-bit forms of the gradient to the reduction: the same descriptor with them named)
     if part is not None:
-        d2, _ = _siren_desc(meta, wvec, xf, pe, dw16, chunks, None, xf16, planes)
-        _reduce_chunks(d2, part, sse_part, dw, sse)
+        _reduce_chunks(_gradient_forms(SirenDesc.from_buffer_copy(d), G, meta, dw16, planes), part, sse_part, dw, sse)
     if want_planes:
         return sse, None, dpe, planes
     return (sse, dw, dpe, dw16) if want_bf16 else (sse, dw, dpe)
