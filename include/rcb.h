@@ -25,9 +25,10 @@ extern "C" {
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
  * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23;
  * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop; 412: rcb_signal_patch_fmt,
- * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged).  A binding compares
+ * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged; 414: rcb_ssim_workspace_bytes, rcb_ssim).  A binding
+ * compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 413
+#define RCB_VERSION 414
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -822,6 +823,42 @@ int rcb_recon_finish_ragged(const float* y, const float* target, int64_t n_rows,
                             const int32_t* patch_nums, const int32_t* patch_size, const int32_t* sizes, const int64_t* spans,
                             int64_t out_elems, int32_t mode, int32_t depth, void* q_out, float* whole, double* sse, int32_t* n_bad,
                             void* workspace, int64_t workspace_bytes, void* table, int64_t table_bytes, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (414): SSIM and the sums of MS-SSIM (Wang et al. 2004, the usual constants) of decoded images against their sources, on the
+ * INTEGERS of both: the second column of every codec comparison, which the reference (PSNR alone, utils.py:200-260) does not
+ * report.  a, b: [n_img][H][W][C] samples of kind 0 (uint8, depth 0, L = 255) or kind 2 (16-bit unsigned words at `depth` b,
+ * 9 <= b <= 16, L = 2^b - 1; a stored value above L is used as it is, as rcb_signal_patch_fmt does).  Each operand has its own
+ * ELEMENT strides {image, row, column, channel} (HOST int64[4], >= 0): the addressing rule of rcb_signal_patch, 64-bit offsets --
+ * channel-first storage, transposed axes, a window of a larger image, a broadcast channel; nothing need be contiguous.
+ * The definition, every product and sum one IEEE fp64 operation (no contraction), divisions correctly rounded:
+ *   window   `win`: HOST double[11], w = g / sum(g), g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)); c1 = (0.01 L)^2, c2 = (0.03 L)^2.  The
+ *            caller forms all three (utils.ssim_window, utils.ssim_constants); the device evaluates no exp and no constant.
+ *   filter   "valid" positions only, (H - 10) x (W - 10) per channel; separable, the LAST spatial axis first, taps ascending, the
+ *            first product starting the sum:  t(r, x) = ((w0 v(r, x) + w1 v(r, x+1)) + ...) + w10 v(r, x+10), and m(y, x) the same
+ *            over t(y+i, x); for v in {a, b, a a, b b, a b}, the products exact.
+ *   formula  maa = ma ma, mbb = mb mb, mab = ma mb;  saa = m(a a) - maa, sbb = m(b b) - mbb, sab = m(a b) - mab (not clamped);
+ *            cs = (2 sab + c2) / ((saa + sbb) + c2);  l = (2 mab + c1) / ((maa + mbb) + c1);  ssim = l cs.
+ *            Identical operands give ssim = cs = 1.0 exactly: numerator and denominator are the same expressions.
+ *   scales   scale s = 0 .. scales-1 works on floor(H / 2^s) x floor(W / 2^s); a sample is the INTEGER sum of its 2^s x 2^s block (a
+ *            trailing odd row or column is dropped at each halving), used as sum / 4^s in fp64, which is exact.  Each scale needs
+ *            both sides >= 11: five scales need min(H, W) >= 176.
+ * sums [n_img][scales][C][2] int64, written (not accumulated into): {sum of rint(ssim * RCB_SSIM_FX_SCALE), sum of rint(cs *
+ *      RCB_SSIM_FX_SCALE)} over the positions of that image, scale and channel, rint to nearest even.  Integer sums have no order,
+ *      so an image's sums are bitwise the same alone, in a batch, in any batch order and from run to run (64-bit integer atomics
+ *      after a memset of `sums` on the stream).  Terms lie in [-1, 1] * 2^36 and an image has at most 2^26 positions: |sum| < 2^62.
+ * map  nullable, [n_img][H-10][W-10][C][2] fp64: {ssim, cs} of scale 0 per position.
+ * workspace: rcb_ssim_workspace_bytes(n_img, H, W, C, scales) bytes (the block sums of scales 1 ..; 0 for one scale, when the pointer
+ *      may be null; -1: shape refused), 16-byte aligned, caller-allocated.  No host synchronisation and no readback.
+ * n_img = 0 succeeds and launches nothing.  Refused (RCB_ERR_*), nothing launched: kind 1 or 3 (or any other), a depth outside
+ * 9 .. 16 for kind 2 or a non-zero depth for kind 0, C outside 1 .. 32, H or W below 11, scales outside 1 .. 5 or more scales than
+ * the size allows, more than 2^26 positions per image, a negative stride, null a / b / sums / win / strides, a workspace that is too
+ * small or misaligned.  The figures are formed on the host (utils.ssim_from_sums, utils.msssim_from_sums). */
+#define RCB_SSIM_FX_SCALE 68719476736.0          /* 2^36 */
+int64_t rcb_ssim_workspace_bytes(int64_t n_img, int32_t H, int32_t W, int32_t C, int32_t scales);
+int rcb_ssim(const void* a, const void* b, int32_t kind, int32_t depth, int64_t n_img, int32_t H, int32_t W, int32_t C,
+             const int64_t* a_strides, const int64_t* b_strides, const double* win, double c1, double c2, int32_t scales,
+             int64_t* sums, double* map, void* workspace, int64_t workspace_bytes, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import AdamCfg, AdamTensor, Level, LevelBwd, RcbError, SirenDesc, addr, check, ptr, stream_ptr
-from .utils import SampleFormat
+from .utils import SampleFormat, ssim_constants, ssim_window
 
 f32 = torch.float32
 f64 = torch.float64
@@ -1493,6 +1493,51 @@ def recon_finish_ragged(y, target=None, layout=None, sizes=None, swap=None, mode
             return None
         return [buf[sp[0]:sp[0] + math.prod(shp)].view(shp) for sp, shp in zip(spans, shapes)]
     return views(q_buf), views(whole_buf), sse, n_bad
+
+
+# ---------------------------------------------------------------------------------------------------
+# N4 (414): SSIM / MS-SSIM sums of integer images (rcb_ssim)
+# ---------------------------------------------------------------------------------------------------
+def ssim_sums(a, b, sample_format=None, scales=1, want_map=False):
+    """The exact fixed-point sums of SSIM between integer images a and b [n, H, W, C] on the GPU (rcb_ssim; the definition is
+    include/rcb.h's): -> (sums int64 [n, scales, C, 2] = per image, scale and channel {sum rint(ssim * 2^36), sum rint(cs * 2^36)}
+    over the (H_s - 10) x (W_s - 10) window positions of scale s, map fp64 [n, H-10, W-10, C, 2] = {ssim, cs} of scale 0 per
+    position with want_map, else None), both device tensors; nothing is read back.  utils.ssim_from_sums / msssim_from_sums
+    turn the sums into the figures.  a and b keep whatever strides they have -- a utils.signal_view, a transposed or
+    channel-first view, a window of a larger image, an expanded channel: the strides go to the kernel and nothing is copied.
+    The sums are integer sums: bitwise the same for an image alone, in any batch and from run to run.
+    sample_format (utils.SampleFormat; None: uint8): u8, or u16(depth) for uint16 tensors (or int16, the bits reinterpreted); a
+    16-bit tensor without a format is a ValueError (the depth is not in the dtype), a dtype the format does not read an
+    RcbError.  fp32 and s16 have no SSIM here: the library refuses their kinds."""
+    what = "ssim_sums"
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RcbError(f"{what}: a and b must be GPU tensors (the HIP path has no CPU fallback)")
+        if sample_format is None and t.dtype in (torch.uint16, torch.int16):
+            raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.u16(depth) or .s16()): the depth is not in the "
+                             "dtype" % (what, t.dtype))
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise RcbError(f"{what}: a {tuple(a.shape)} and b {tuple(b.shape)} must be [n, H, W, C] of one shape on one device")
+    kind, depth, _ = _sample_rule(what, a.dtype, sample_format)
+    _sample_rule(what, b.dtype, sample_format)
+    if sample_format is None and a.dtype != b.dtype:
+        raise RcbError(f"{what}: a is {a.dtype}, b is {b.dtype}")
+    n, H, W, Cc = (int(v) for v in a.shape)
+    scales = int(scales)
+    dev = a.device
+    lib = _lib.load()
+    n_ws = int(lib.rcb_ssim_workspace_bytes(n, H, W, Cc, scales))
+    fits = n_ws >= 0                                         # (a refused shape: one-element outputs, and the library says why)
+    sums = torch.empty((n, scales, Cc, 2) if fits else (1,), device=dev, dtype=torch.int64)
+    smap = torch.empty((n, H - 10, W - 10, Cc, 2) if fits else (1,), device=dev, dtype=f64) if want_map else None
+    ws = torch.empty(max(n_ws, 16), device=dev, dtype=torch.uint8)
+    c1, c2 = ssim_constants(SampleFormat(kind, depth)) if kind in (SampleFormat.U8, SampleFormat.U16) else (0.0, 0.0)
+    win = np.ascontiguousarray(ssim_window(), dtype=np.float64)
+    st_a = (C.c_int64 * 4)(*(int(v) for v in a.stride()))
+    st_b = (C.c_int64 * 4)(*(int(v) for v in b.stride()))
+    _launch("rcb_ssim", C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), kind, depth, n, H, W, Cc, st_a, st_b, _np_ptr(win),
+            c1, c2, scales, ptr(sums, torch.int64), ptr(smap, f64, True), ptr(ws), max(n_ws, 0))
+    return sums, smap
 
 
 def _win_geo(shape):

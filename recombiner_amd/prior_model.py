@@ -21,7 +21,7 @@ from . import train_step
 from .ops import LevelSpec, SirenMeta
 from .upsample_fast import (hip_path_supported, tiled_2d_preferred, phase_form_preferred, phase_module,
                             stitched2d_module, upsample_cifar_hip)
-from .utils import count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs, metric_device
+from .utils import SampleFormat, count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs, metric_device, ssim_device
 from .utils import map_hierarchical_model_to_int_weights  # noqa: F401  (module-level name, as upstream imports it)
 
 
@@ -167,6 +167,58 @@ class InrGeometry:
         """`report` against whole signals instead of patch targets (sizes: a list of signals, as patch_signals takes it)"""
         return self.report(x, self.patch_signals(signals, size, sample_format, sizes=sizes), size=size, sample_format=sample_format,
                            sizes=sizes)
+
+    def report_ssim(self, x, signals, size=None, sample_format=None, sizes=None, multiscale=False):
+        """SSIM (with `multiscale`: MS-SSIM) of the images this model delivers against the whole source `signals`, fp64 per signal
+        (the model with `predict`, as `report`): predict, round to the format's integers at each signal's own size
+        (ops.recon_finish(want_int=True, size=) / ops.recon_finish_ragged for sizes=), then rcb_ssim on those integers against the
+        integers of `signals` (utils.ssim_device; the definition is include/rcb.h's).  The figure of the DELIVERED image: nothing
+        but the sums leaves the device.
+        signals: [n, *size, C] integer images on the model's grid (size None) or of extent `size` inside it, any strides; with
+        sizes= a LIST of [*sizes[k], C] tensors -- a portrait signal as compress_signal_list cuts it: its transposed view, and
+        sizes[k] the landscape extent it fits the grid with.  sample_format: needed for 16-bit signals (None: uint8).
+        ValueError, with the reason: a 1-D or 3-D preset, fp32 (or s16) signals, a 16-bit tensor without a format, an image
+        smaller than 11 (multiscale: 176) per side."""
+        if self.data_dim != 2:
+            raise ValueError("report_ssim: SSIM is defined for 2-D presets, this one has %d axes" % self.data_dim)
+        if sizes is not None and size is not None:
+            raise ValueError("report_ssim: size and sizes exclude each other")
+        listed = sizes is not None
+        sigs = list(signals) if listed else [signals]
+        for t in sigs:
+            if sample_format is None and t.dtype in (torch.uint16, torch.int16):
+                raise ValueError("report_ssim: %s signals need sample_format= (utils.SampleFormat.u16(depth)): the depth is not in "
+                                 "the dtype" % (t.dtype,))
+            if t.dtype.is_floating_point:
+                raise ValueError("report_ssim: SSIM compares the delivered integers with the source's: %s signals have none"
+                                 % (t.dtype,))
+        fmt = sample_format if sample_format is not None else SampleFormat.u8()
+        if fmt.kind not in (SampleFormat.U8, SampleFormat.U16):
+            raise ValueError("report_ssim: SSIM is defined for u8 and u16 images, not %r" % (fmt,))
+        layout = self.signal_layout()
+        grid = tuple(n * s for n, s in zip(layout.patch_nums, layout.patch_size))
+        if listed:
+            extents = [tuple(int(v) for v in s) for s in sizes]
+        else:
+            extents = [tuple(int(v) for v in size) if size is not None else grid]
+        need = 176 if multiscale else 11
+        for e in extents:
+            if len(e) != 2 or min(e) < need:
+                raise ValueError("report_ssim: an image of %s is too small for %s (both sides at least %d)"
+                                 % (" x ".join(str(v) for v in e),
+                                    "MS-SSIM's five scales" if multiscale else "SSIM's 11-tap window", need))
+        dev = self.loc.device
+        want = [e + (self.dims[-1],) for e in extents]
+        got = [tuple(t.shape) for t in sigs] if listed else [tuple(signals.shape[1:])]
+        if got != want:
+            raise ValueError("report_ssim: signals of shape %r, expected %r" % (got, want))
+        with torch.no_grad():
+            y_pred = self.predict(x.to(dev)).detach().to(torch.float32).contiguous()
+        if listed:
+            q, _, _, _ = ops.recon_finish_ragged(y_pred, layout=layout, sizes=extents, sample_format=fmt, want_int=True)
+            return ssim_device(q, [t.to(dev) for t in sigs], sample_format=fmt, multiscale=multiscale)
+        q, _, _, _ = ops.recon_finish(y_pred, layout=layout, size=size, sample_format=fmt, want_int=True)
+        return ssim_device(q, signals.to(dev), sample_format=fmt, multiscale=multiscale)
 
 
 class PriorBNNmodel(nn.Module, InrGeometry):

@@ -458,3 +458,95 @@ def metric_device(y_true, y_pred, dataset, layout=None, size=None, sample_format
         _, _, sse, _n_bad = ops.recon_finish(y_pred, y_true, layout=layout, mode=mode, size=size, sample_format=sample_format)
         counts = y_pred.numel() // sse.numel() if size is None else int(np.prod([int(v) for v in size])) * Cc
     return metric_from_sse(sse.cpu().numpy(), counts, dataset)
+
+
+# ---------------------------------------------------------------------------------------------
+# SSIM / MS-SSIM of delivered integers against the source's, from the exact fixed-point sums of rcb_ssim (include/rcb.h, N4 414)
+# ---------------------------------------------------------------------------------------------
+SSIM_TAPS = 11
+SSIM_FX_SCALE = float(1 << 36)                               # RCB_SSIM_FX_SCALE
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def ssim_window():
+    """THE window of rcb_ssim: 11 taps, sigma 1.5, normalised, numpy fp64 -- formed here and nowhere else; the device gets the
+    11 doubles and evaluates no exp"""
+    k = np.arange(SSIM_TAPS, dtype=np.float64)
+    g = np.exp(-(k - 5) ** 2 / (2 * 1.5 ** 2))
+    return g / g.sum()
+
+
+def ssim_constants(sample_format):
+    """(C1, C2) = ((0.01 L)^2, (0.03 L)^2) of an integer sample format, L = 255 (u8) or 2^depth - 1 (u16)"""
+    if sample_format.kind not in (SampleFormat.U8, SampleFormat.U16):
+        raise ValueError("SSIM is defined here for u8 and u16 samples, not %r" % (sample_format,))
+    L = 255 if sample_format.kind == SampleFormat.U8 else (1 << sample_format.depth) - 1
+    return (0.01 * L) ** 2, (0.03 * L) ** 2
+
+
+def ssim_positions(H, W, scale=0):
+    """window positions of scale `scale` of an H x W image: (floor(H / 2^s) - 10) * (floor(W / 2^s) - 10)"""
+    return ((int(H) >> scale) - (SSIM_TAPS - 1)) * ((int(W) >> scale) - (SSIM_TAPS - 1))
+
+
+def _ssim_sums_host(sums, H, W, scales=None):
+    s = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    if s.ndim != 4 or s.shape[-1] != 2 or s.dtype != np.int64:
+        raise ValueError("the sums of rcb_ssim are int64 [n, scales, C, 2], got %s %r" % (s.dtype, s.shape))
+    if scales is not None and s.shape[1] != scales:
+        raise ValueError("%d scales are needed, the sums hold %d" % (scales, s.shape[1]))
+    if ssim_positions(H, W, s.shape[1] - 1) < 1 or min(int(H) >> (s.shape[1] - 1), int(W) >> (s.shape[1] - 1)) < SSIM_TAPS:
+        raise ValueError("an image of %d x %d has no %d scales (both sides at least %d)"
+                         % (H, W, s.shape[1], SSIM_TAPS << (s.shape[1] - 1)))
+    return s
+
+
+def ssim_from_sums(sums, H, W):
+    """SSIM per image, fp64 [n], from rcb_ssim's sums [n, scales, C, 2] of H x W images: the mean over the scale-0 positions and
+    the channels, (exact integer sum over the channels) / 2^36 / (positions * C)"""
+    s = _ssim_sums_host(sums, H, W)
+    count = float(ssim_positions(H, W) * s.shape[2])
+    return np.asarray([float(sum(int(v) for v in img[0, :, 0])) / SSIM_FX_SCALE / count for img in s], dtype=np.float64)
+
+
+def msssim_from_sums(sums, H, W):
+    """MS-SSIM per image, fp64 [n], from five-scale sums (min(H, W) >= 176): per channel prod_{s<4} max(mean cs_s, 0)^w_s *
+    max(mean ssim_4, 0)^w_4 with w = MSSSIM_WEIGHTS, the factors multiplied in scale order, then the mean over the channels --
+    the per-channel convention of the common PyTorch implementation.  Scale s is the floor-pooled one of rcb_ssim; for even
+    sizes it coincides with the padded and the truncating conventions."""
+    s = _ssim_sums_host(sums, H, W, scales=5)
+    out = []
+    for img in s:
+        total = None
+        for c in range(s.shape[2]):
+            p = None
+            for k in range(5):
+                mean = float(int(img[k, c, 1 if k < 4 else 0])) / SSIM_FX_SCALE / float(ssim_positions(H, W, k))
+                f = max(mean, 0.0) ** MSSSIM_WEIGHTS[k]
+                p = f if p is None else p * f
+            total = p if total is None else total + p
+        out.append(total / float(s.shape[2]))
+    return np.asarray(out, dtype=np.float64)
+
+
+def ssim_device(a, b, sample_format=None, multiscale=False):
+    """SSIM (or with `multiscale` MS-SSIM) of integer images on the GPU, fp64 [n]: a, b are [n, H, W, C] tensors of one integer
+    dtype with ANY strides (ops.ssim_sums), or two LISTS of [H_k, W_k, C] tensors of mixed sizes, scored with one rcb_ssim call
+    per signal (a one-launch list form does not exist).  Only the sums are read back.  sample_format: ops.ssim_sums's.  An image
+    too small for the scales asked (11 for SSIM, 176 for MS-SSIM, per side) is a ValueError."""
+    from . import ops
+    if isinstance(a, (list, tuple)) or isinstance(b, (list, tuple)):
+        if not isinstance(a, (list, tuple)) or not isinstance(b, (list, tuple)) or len(a) != len(b):
+            raise ValueError("ssim_device: two lists of as many signals, or two tensors")
+        if not a:
+            return np.zeros(0, dtype=np.float64)
+        return np.concatenate([ssim_device(x[None], y[None], sample_format, multiscale) for x, y in zip(a, b)])
+    if a.dim() != 4:
+        raise ValueError("ssim_device: images are [n, H, W, C], got %d axes" % a.dim())
+    H, W = int(a.shape[1]), int(a.shape[2])
+    need = SSIM_TAPS << 4 if multiscale else SSIM_TAPS
+    if min(H, W) < need:
+        raise ValueError("ssim_device: an image of %d x %d is too small for %s (both sides at least %d)"
+                         % (H, W, "MS-SSIM's five scales" if multiscale else "SSIM's 11-tap window", need))
+    sums, _ = ops.ssim_sums(a, b, sample_format=sample_format, scales=5 if multiscale else 1)
+    return msssim_from_sums(sums, H, W) if multiscale else ssim_from_sums(sums, H, W)
