@@ -23,7 +23,8 @@ Rounding points (DESIGN.md section 4.4.1 has the same table, with one column per
   --  epilogues, fp32, not rounded      dW = sum_pixels dz (x) input / GS;  dpe = dz_0 @ R4^T / (GS WS);  y = acc / WS + b_out
 
 GS = WS = 1 for bf16 and 2^10 for f16.  With mode=None nothing is rounded and k_hi is w0 / 2 pi in fp64: the evaluator is then
-the plain MLP (test_siren_emul_cpu.py ties that to autograd).
+the plain MLP (test_siren_emul_cpu.py ties that to autograd).  That form is what the two fp32 families (siren_mlp.hip,
+siren_mlp_generic.hip) are held to; their case sets, their route and the fp32 yardstick of their limits are at the end.
 """
 import math
 
@@ -85,6 +86,8 @@ class Faults:
     fourier_scale = None           # factor on the Fourier half of layer 0's weight gradient
     round_before_khi = False       # weights rounded before the multiplication by k_hi
     no_grad_scale = False          # dz rounded without GRAD_SCALE
+    leak_last_dz = False           # the last valid pixel's dz also left in one padded slot of its tile (whose inputs the kernels
+                                   # clamp to, or zero beside, the last valid pixel): that pixel twice in dW; needs P % 32 != 0
 
     def __init__(self, **kw):
         for k, v in kw.items():
@@ -158,6 +161,10 @@ def siren_emul(dims, xf, pe, wv, S, *, mode=None, bias="fp32", cos="packed", dpe
         lo, nin, nout = layer_slices(dims)[l]
         gb = dz[:, :nP].sum(1) / GS
         gw = inputs[l][:, :nP].transpose(1, 2) @ dz[:, :nP] / GS
+        if ft.leak_last_dz:
+            assert P % 32, "no padded slot in the last tile"
+            gb = gb + dz[:, P - 1] / GS
+            gw = gw + inputs[l][:, P - 1:].transpose(1, 2) @ dz[:, P - 1:] / GS
         if ft.bias_grad_scale is not None and ft.bias_grad_scale[0] == l:
             gb = gb * ft.bias_grad_scale[1]
         if l == 0 and ft.fourier_scale is not None:
@@ -193,14 +200,19 @@ def make_case(F, E, dims_hidden, C, P, N, S, seed, scale="init"):
     y = torch.rand(N, P, C, generator=gen)
     dy = 1e-3 * torch.randn(G, P, C, generator=gen)          # gradient-sized: unit-scale dy overflows the f16 operands
     return dict(dims=dims, F=F, E=E, C=C, P=P, N=N, S=S, D=D, xf=xf, pe=pe, wv=wv, y=y, dy=dy, dy_scale=1.0 / (S * P * C),
-                hidden=dims_hidden[0], n_hidden=len(dims_hidden), scale=scale)
+                hidden=dims_hidden[0], n_hidden=len(dims_hidden), scale=scale, hidden_dims=tuple(dims_hidden))
 
 
 # ---- the input sets of test_hip_siren_operand_exact.py (GPU) and test_siren_emul_cpu.py -----------------------------------------
-def case_of(hidden, nh, F=16, C=3, P=33, N=1, S=1, chunks=1, scale="init", variant="f32pe", seed=0):
+def case_of(hidden, nh, F=16, C=3, P=33, N=1, S=1, chunks=1, scale="init", variant="f32pe", seed=0, E=16, hidden_dims=None):
     """variant: "f32pe" fp32 pe storage; "in16" bf16 pe + the 16-bit copy of xf (16-bit input rows); "pe16" bf16 pe with
-    RCB_SIREN_NO_XF16=1 (fp32 xf rows, bf16 pe rows)"""
-    return dict(hidden=hidden, nh=nh, F=F, C=C, P=P, N=N, S=S, chunks=chunks, scale=scale, variant=variant, seed=seed)
+    RCB_SIREN_NO_XF16=1 (fp32 xf rows, bf16 pe rows).  hidden_dims: the hidden widths one by one where they differ (fp32 mode
+    only; `hidden` is then their maximum and `nh` their number, as in ops.SirenMeta)"""
+    if hidden_dims is not None:
+        assert len(hidden_dims) == nh and max(hidden_dims) == hidden
+        hidden_dims = tuple(hidden_dims)
+    return dict(hidden=hidden, nh=nh, F=F, C=C, P=P, N=N, S=S, chunks=chunks, scale=scale, variant=variant, seed=seed, E=E,
+                hidden_dims=hidden_dims)
 
 
 # The smallest shapes at which these kernels can still go wrong: one 32-pixel tile, one tile plus one pixel (also as the only
@@ -230,6 +242,39 @@ CASES = {
 }
 CASES["wg32"] += CASES["wave"]          # the sibling families are held to the same evaluator on the same inputs
 
+# The two fp32 families (precision 0; test_hip_siren_fp32_exact.py), held to the evaluator with mode=None: the plain MLP in fp64.
+# At most 4 rows of one to five tiles.
+CASES_FP32 = {
+    # siren_mlp.hip, width 32 on the fp32 MFMA: every instance X(NH, KS, NB) of RCB_SIREN_FP32_INSTANCES (test_siren_emul_cpu.py
+    # holds that against siren_route.h); P = 32 leaves three of the four waves without a tile, P = 1 / 31 / 33 pad a tile, 160 is
+    # five tiles dealt 2, 1, 1, 1; C beyond 16 fills the second half of the output rows; F + E = 48 pads the second input block
+    "fp32": [case_of(32, 3, P=32, seed=101), case_of(32, 1, C=1, P=1, seed=102), case_of(32, 2, P=31, N=2, S=2, seed=103),
+             case_of(32, 4, C=17, seed=104), case_of(32, 3, F=18, P=160, N=2, seed=105), case_of(32, 3, F=32, E=32, C=32, seed=106),
+             case_of(32, 3, F=16, E=32, S=2, seed=107), case_of(32, 3, E=0, N=2, seed=108), case_of(32, 1, E=0, C=1, seed=109),
+             case_of(32, 2, N=2, scale="model", seed=110), case_of(32, 3, F=32, E=32, scale="model", seed=111)],
+    # siren_mlp_generic.hip, plain FMAs: the instance of up to 5 linear layers (ML = 5) and the one of up to 8; width 1; widths that
+    # are no multiple of 8; the 64 x 65 layer vector that fills all 17 gradient registers of a thread; per-layer widths, the widest
+    # in the middle and at the end; C above every hidden width (it then sets the LDS row stride ws)
+    "generic": [case_of(1, 1, seed=121), case_of(12, 3, N=2, S=2, seed=122), case_of(40, 2, P=160, seed=123),
+                case_of(64, 1, F=32, E=32, seed=124), case_of(40, 3, hidden_dims=(24, 40, 16), seed=125),
+                case_of(64, 3, C=1, hidden_dims=(8, 12, 64), seed=126), case_of(16, 5, seed=127), case_of(40, 7, N=2, seed=128),
+                case_of(16, 7, C=32, P=1, seed=129), case_of(40, 5, E=0, seed=130), case_of(12, 2, C=32, S=2, seed=131),
+                case_of(40, 3, N=2, scale="model", seed=132), case_of(16, 5, scale="model", seed=133)],
+}
+CASES.update(CASES_FP32)
+
+
+def fp32_route(c):
+    """the kernel instance that runs a case at precision 0, restated from siren_route.h (test_siren_emul_cpu.py holds this
+    function to the header on every case of CASES_FP32): ("fp32", NH, KS, NB), ("generic", ML) or None (refused)"""
+    nh, F, E = c["nh"], c["F"], c["E"]
+    if c["hidden"] != 32 or c["hidden_dims"] is not None or nh > 4:
+        return ("generic", 8 if nh + 1 > 5 else 5)
+    for NH, KS, NB in ((3, 16, 1), (2, 16, 1), (3, 18, 2), (1, 16, 1), (4, 16, 1), (3, 32, 2)):
+        if nh == NH and max(F, E) <= KS and (F + E + 31) // 32 == NB:
+            return ("fp32", NH, KS, NB)
+    return None
+
 
 def switches(family, c):
     """the evaluator switches of a family: the wave family feeds the hidden biases through the matrix pipe as
@@ -245,13 +290,15 @@ def switches(family, c):
 
 
 def build(c):
-    return make_case(c["F"], 16, [c["hidden"]] * c["nh"], c["C"], c["P"], c["N"], c["S"], c["seed"], c["scale"])
+    return make_case(c["F"], c["E"], list(c["hidden_dims"] or [c["hidden"]] * c["nh"]), c["C"], c["P"], c["N"], c["S"], c["seed"], c["scale"])
 
 
 # one small case per family, three hidden layers (the deep family's smallest is five), taken from CASES so that it is one of the
 # cases the limits of test_hip_siren_operand_exact.py were measured on
 DISCRIMINATION = {"wg32": CASES["wg32"][2], "wave": CASES["wave"][1], "wide": CASES["wide"][4], "narrow": CASES["narrow"][5],
                   "deep": CASES["deep"][1]}
+# the fp32 families: a tile with padded slots (the fault that leaks into one needs it) and a target shared by two rows
+DISCRIMINATION.update({"fp32": CASES["fp32"][2], "generic": CASES["generic"][1]})
 
 
 # ---- the flip floor ------------------------------------------------------------------------------------------------------------
@@ -290,11 +337,15 @@ def block_errors(case, out, ref, suffix=""):
     G = ref["y"].shape[0]
 
     def add(key, o, r):
+        if r.numel() == 0:                                  # E = 0: no dpe, no pe rows in layer 0
+            return
         e = ((o.to(F64) - r).abs() / (r.abs().max() + 1e-300)).reshape(-1)
         res.setdefault(key, []).append(e)
 
     for name in ("y", "sse", "dpe", "bwd_dpe"):
         if out.get(name) is None:
+            continue
+        if ref[name].numel() == 0:
             continue
         for g_ in range(G):
             add((name + (suffix if "dpe" in name else ""), "row"), out[name][g_].cpu(), ref[name][g_])
@@ -317,3 +368,94 @@ def block_stats(errs):
         out[(name, kind, "max")] = max(float(e.max()) for e in blocks)
         out[(name, kind, "med")] = max(float(e.median()) for e in blocks)
     return out
+
+
+# ---- the fp32 families: yardstick and limits -------------------------------------------------------------------------------------
+# The fp32 kernels (siren_mlp.hip, siren_mlp_generic.hip) round nowhere but in their fp32 arithmetic, so the evaluator they are held
+# to is mode=None, and what a correct kernel differs by is fp32 rounding in ITS order of operations.  How large that is on a
+# given input set is measured, not assumed: fp32_restatement below is the same MLP and its gradients in fp32 torch on the CPU, run
+# as the case stands and once more with the hidden units of every layer and the pixels reversed (an exact permutation of the
+# problem; the outputs are permuted back) -- two correct fp32 evaluations that differ only in summation order.  The yardstick of
+# a key (output, block kind, "max" | "med") is the larger of the two runs' block_stats against the fp64 evaluator, the worst over
+# the cases of a family and scale group (pooled: a bias block at C = 1 has one element, whose error can be 0 by chance); the
+# limit is FP32_K times that, at least LIMIT_FLOOR.  Nothing here comes from a kernel.
+LIMIT_FLOOR = 2.0 ** -20          # sixteen fp32 ulps of the block's largest entry (the floor of test_hip_siren_operand_exact.py)
+FP32_K = 4.0                      # the kernel and the restatement make the same number of fp32 roundings in different orders, so
+                                  # their error ratio scatters around 1 (the kernels' two-float range reduction is the more
+                                  # accurate sine, which pushes it below); 4 leaves room for the scatter on blocks of few elements
+FP32_CONDITION = {"init": 1e-4, "model": 1e-5}      # no limit of a scale group may exceed this share of a block's largest entry
+
+
+def _reverse_hidden(dims, wv):
+    """rows of layer vectors with the hidden units of every layer in reverse order (its own inverse; also maps a gradient back)"""
+    out, G, nl = torch.empty_like(wv), wv.shape[0], len(dims) - 1
+    for l, (lo, nin, nout) in enumerate(layer_slices(dims)):
+        b, W = wv[:, lo:lo + nout], wv[:, lo + nout:lo + nout * (nin + 1)].reshape(G, nin, nout)
+        if l > 0:
+            W = W.flip(1)
+        if l < nl - 1:
+            W, b = W.flip(2), b.flip(1)
+        out[:, lo:lo + nout] = b
+        out[:, lo + nout:lo + nout * (nin + 1)] = W.reshape(G, -1)
+    return out
+
+
+def fp32_restatement(case, reverse=False):
+    """the outputs of run_emul in fp32 torch with autograd, forward as test_hip_kernels._oracle_mlp (x @ W + b, sin(30 x));
+    reverse: the hidden units of every layer and the pixels in reverse order, the outputs permuted back"""
+    dims, S, f = case["dims"], case["S"], torch.float32
+    xf, pe0, wv0, tgt, dy = (case[k].to(f) for k in ("xf", "pe", "wv", "y", "dy"))
+    if reverse:
+        xf, pe0, tgt, dy, wv0 = xf.flip(0), pe0.flip(1), tgt.flip(1), dy.flip(1), _reverse_hidden(dims, wv0)
+    G, nl, out = pe0.shape[0], len(dims) - 1, {}
+    for plain in (False, True):
+        pe, wv = pe0.clone().requires_grad_(True), wv0.clone().requires_grad_(True)
+        x = torch.cat([xf[None].expand(G, -1, -1), pe], -1)
+        for l, (lo, nin, nout) in enumerate(layer_slices(dims)):
+            x = x @ wv[:, lo + nout:lo + nout * (nin + 1)].reshape(G, nin, nout) + wv[:, lo:lo + nout].unsqueeze(1)
+            if l != nl - 1:
+                x = torch.sin(30.0 * x)
+        if plain:
+            x.backward(dy)
+            out.update(bwd_dW=wv.grad, bwd_dpe=pe.grad)
+        else:
+            diff = x - tgt.repeat_interleave(S, 0)
+            ((diff * diff).sum() * case["dy_scale"]).backward()
+            out.update(y=x.detach(), sse=(diff.detach() ** 2).sum((1, 2)), dW=wv.grad, dpe=pe.grad)
+    if reverse:
+        out = {k: _reverse_hidden(dims, v) if "dW" in k else v if k == "sse" else v.flip(1) for k, v in out.items()}
+    return out
+
+
+_BUILT, _YARDSTICK = {}, {}
+
+
+def fp32_cases(family):
+    """[(c, its inputs, the fp64 evaluator's outputs)] of CASES_FP32[family], computed once and shared (leave them unchanged)"""
+    if family not in _BUILT:
+        built = [(c, build(c)) for c in CASES_FP32[family]]
+        _BUILT[family] = [(c, case, run_emul(case, None)) for c, case in built]
+    return _BUILT[family]
+
+
+def fp32_yardstick(family):
+    """{scale group: {key: the worst over the group's cases of the two restatement runs' block_stats against the fp64 evaluator}}"""
+    if family not in _YARDSTICK:
+        tab = {}
+        for c, case, ref in fp32_cases(family):
+            grp = tab.setdefault(c["scale"], {})
+            for rev in (False, True):
+                for k, v in block_stats(block_errors(case, fp32_restatement(case, rev), ref)).items():
+                    grp[k] = max(grp.get(k, 0.0), v)
+        _YARDSTICK[family] = tab
+    return _YARDSTICK[family]
+
+
+def fp32_limits(family):
+    """{scale group: {key: max(FP32_K * yardstick, LIMIT_FLOOR)}}"""
+    return {grp: {k: max(FP32_K * v, LIMIT_FLOOR) for k, v in tab.items()} for grp, tab in fp32_yardstick(family).items()}
+
+
+def over_limits(stats, limits):
+    """the entries of block_stats that exceed their limit (or are no number): [(key, value, limit)]"""
+    return [(k, v, limits[k]) for k, v in stats.items() if not v <= limits[k]]
