@@ -7,7 +7,7 @@
  * (file:line relative to the reference root).  Conventions:
  *   - plain device pointers + explicit sizes; the caller (PyTorch, or any HIP host) allocates
  *     every buffer including outputs; nothing is allocated, freed or synchronised inside (but for the one table upload of the
- *     two per-signal entries of 413, which says so);
+ *     two per-signal entries of 413 and of the list entry of 415, which say so);
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it;
  *   - return value: 0 = ok, < 0 = argument/shape error (RCB_ERR_*), > 0 = hipError_t;
  *   - no global mutable state besides the thread-local last-error string; re-entrant per stream;
@@ -25,10 +25,11 @@ extern "C" {
 /* major * 100 + minor; bumped with every change of a signature or of a structure layout (100: rounds 1-3; 400: round 4 --
  * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23;
  * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop; 412: rcb_signal_patch_fmt,
- * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged; 414: rcb_ssim_workspace_bytes, rcb_ssim).  A binding
+ * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged; 414: rcb_ssim_workspace_bytes, rcb_ssim;
+ * 415: rcb_ssim_list_table_bytes, rcb_ssim_list_workspace_bytes, rcb_ssim_list_plan, rcb_ssim_list).  A binding
  * compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 414
+#define RCB_VERSION 415
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -859,6 +860,47 @@ int64_t rcb_ssim_workspace_bytes(int64_t n_img, int32_t H, int32_t W, int32_t C,
 int rcb_ssim(const void* a, const void* b, int32_t kind, int32_t depth, int64_t n_img, int32_t H, int32_t W, int32_t C,
              const int64_t* a_strides, const int64_t* b_strides, const double* win, double c1, double c2, int32_t scales,
              int64_t* sums, double* map, void* workspace, int64_t workspace_bytes, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (415): rcb_ssim for a LIST of images of mixed sizes and memory layouts -- and so for the frames of video clips -- in one call:
+ * one memset, scales - 1 pooling launches and `scales` SSIM launches, whatever n_img is.  All images share C, the sample format,
+ * the window, the constants and `scales`; each keeps its own extent and its own place and strides in the operands' buffers:
+ *   sizes    HOST int32 [n_img][2] = {H, W}.
+ *   a_spans, b_spans  HOST int64 [n_img][4] = {offset, row stride, column stride, channel stride}, in elements, all >= 0.  Element
+ *            (y, x, c) of image k lies at base + offset + y * rs + x * cs + c * chs, 64-bit offsets.  The channel stride is per
+ *            image: channel-last, channel-first, transposed, windowed and broadcast-channel images may share one call.
+ *   a_elems, b_elems  elements of the buffers from `a` and `b`; an image whose farthest element offset + (H - 1) rs + (W - 1) cs +
+ *            (C - 1) chs is >= that count is refused, so every read lies inside [a, a + a_elems) and [b, b + b_elems).
+ *   table    device buffer of rcb_ssim_list_table_bytes(n_img, scales) bytes (-1: n_img or scales refused), 8-byte aligned, the
+ *            caller's to allocate.  The entry validates the host tables, writes their device copy there on `stream` and
+ *            synchronises the stream ONCE for that upload -- the rule of the per-signal entries of 413: this entry is NOT for
+ *            graph capture.  On return the host arrays are the caller's again.
+ *   workspace  rcb_ssim_list_workspace_bytes(n_img, sizes, C, scales) bytes = the sum over k of rcb_ssim_workspace_bytes(1, H_k,
+ *            W_k, C, scales) (-1: a shape refused), image k's block laid out as that call lays it out; 16-byte aligned; may be
+ *            null for one scale.
+ * Image k is scored exactly as rcb_ssim scores it with n_img = 1 and H_k x W_k -- same window, filter order, formula, floor pooling
+ * of integer block sums, fixed-point terms.  sums [n_img][scales][C][2] int64, written (not accumulated into): image k's slice is
+ * bitwise what rcb_ssim gives for that image alone, in any list, in any list order and from run to run.  Every image must allow
+ * `scales`.  The list form has NO `map` output: the per-position {ssim, cs} of an image come from rcb_ssim.
+ *
+ * rcb_ssim_list_plan: the host arithmetic of the table, callable without a device; rcb_ssim_list builds its table through it.
+ * Writes plan[(s * n_img + k) * 5 + {0 .. 4}] = {first tile, first pooling workgroup, workspace offset in uint32 elements of
+ * operand a's block sums (b's follow 16-byte aligned behind them), H_s, W_s} of image k at scale s -- a tile is 16 x 16 window
+ * positions, a pooling workgroup 256 block sums of both operands; scale 0 pools nothing: 0, 0 there -- then per scale
+ * plan[5 * scales * n_img + 2 s + {0, 1}] = {tiles, pooling workgroups} of the whole list.  -> the number of ints written,
+ * scales * (5 n_img + 2), or an error (< 0); max_ints below that number is RCB_ERR_SHAPE.
+ *
+ * Refused (RCB_ERR_*), nothing launched and nothing uploaded: everything rcb_ssim refuses, per image and naming the image; null
+ * sizes, spans or table; a table or workspace that is too small or misaligned; a negative offset or stride; a reach past a_elems /
+ * b_elems; more than 2^31 - 1 tiles (or pooling workgroups) at one scale over the list; more than 2^24 images.  n_img = 0
+ * succeeds and launches nothing. */
+int64_t rcb_ssim_list_table_bytes(int64_t n_img, int32_t scales);
+int64_t rcb_ssim_list_workspace_bytes(int64_t n_img, const int32_t* sizes, int32_t C, int32_t scales);
+int rcb_ssim_list_plan(int64_t n_img, const int32_t* sizes, int32_t C, int32_t scales, int64_t* plan, int64_t max_ints);
+int rcb_ssim_list(const void* a, int64_t a_elems, const void* b, int64_t b_elems, int32_t kind, int32_t depth, int64_t n_img,
+                  const int32_t* sizes, const int64_t* a_spans, const int64_t* b_spans, int32_t C, const double* win, double c1,
+                  double c2, int32_t scales, int64_t* sums, void* workspace, int64_t workspace_bytes, void* table,
+                  int64_t table_bytes, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

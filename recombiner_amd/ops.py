@@ -1510,18 +1510,9 @@ def ssim_sums(a, b, sample_format=None, scales=1, want_map=False):
     16-bit tensor without a format is a ValueError (the depth is not in the dtype), a dtype the format does not read an
     RcbError.  fp32 and s16 have no SSIM here: the library refuses their kinds."""
     what = "ssim_sums"
-    for t in (a, b):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RcbError(f"{what}: a and b must be GPU tensors (the HIP path has no CPU fallback)")
-        if sample_format is None and t.dtype in (torch.uint16, torch.int16):
-            raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.u16(depth) or .s16()): the depth is not in the "
-                             "dtype" % (what, t.dtype))
-    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+    kind, depth = _ssim_operand_rule(what, [a, b], sample_format)
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape):
         raise RcbError(f"{what}: a {tuple(a.shape)} and b {tuple(b.shape)} must be [n, H, W, C] of one shape on one device")
-    kind, depth, _ = _sample_rule(what, a.dtype, sample_format)
-    _sample_rule(what, b.dtype, sample_format)
-    if sample_format is None and a.dtype != b.dtype:
-        raise RcbError(f"{what}: a is {a.dtype}, b is {b.dtype}")
     n, H, W, Cc = (int(v) for v in a.shape)
     scales = int(scales)
     dev = a.device
@@ -1538,6 +1529,113 @@ def ssim_sums(a, b, sample_format=None, scales=1, want_map=False):
     _launch("rcb_ssim", C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), kind, depth, n, H, W, Cc, st_a, st_b, _np_ptr(win),
             c1, c2, scales, ptr(sums, torch.int64), ptr(smap, f64, True), ptr(ws), max(n_ws, 0))
     return sums, smap
+
+
+# N4 (415): the same sums for a list of images of mixed sizes and layouts, and for the frames of clips (rcb_ssim_list)
+def _ssim_list_launch(a_base, a_elems, b_base, b_elems, kind, depth, sizes, a_spans, b_spans, Cc, scales, dev):
+    """THE call of rcb_ssim_list: the host tables sizes int32 [n, 2], a_spans / b_spans int64 [n, 4] (elements from the two base
+    addresses) -> sums int64 [n, scales, C, 2] on `dev`.  Allocates sums, workspace and table; a refused list: the library says why."""
+    lib = _lib.load()
+    n, scales = int(sizes.shape[0]), int(scales)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32).reshape(n, 2)
+    a_spans = np.ascontiguousarray(a_spans, dtype=np.int64).reshape(n, 4)
+    b_spans = np.ascontiguousarray(b_spans, dtype=np.int64).reshape(n, 4)
+    n_ws = int(lib.rcb_ssim_list_workspace_bytes(n, _np_ptr(sizes), Cc, scales))
+    n_tab = int(lib.rcb_ssim_list_table_bytes(n, scales))
+    fits = n_ws >= 0 and n_tab >= 0                          # (a refused list: one-element outputs, and the library says why)
+    sums = torch.empty((n, scales, Cc, 2) if fits else (1,), device=dev, dtype=torch.int64)
+    ws = torch.empty(max(n_ws, 16), device=dev, dtype=torch.uint8)
+    table = torch.empty(max(n_tab, 8), device=dev, dtype=torch.uint8)
+    c1, c2 = ssim_constants(SampleFormat(kind, depth)) if kind in (SampleFormat.U8, SampleFormat.U16) else (0.0, 0.0)
+    win = np.ascontiguousarray(ssim_window(), dtype=np.float64)
+    _launch("rcb_ssim_list", C.c_void_p(a_base), int(a_elems), C.c_void_p(b_base), int(b_elems), kind, depth, n, _np_ptr(sizes),
+            _np_ptr(a_spans), _np_ptr(b_spans), Cc, _np_ptr(win), c1, c2, scales, ptr(sums, torch.int64), ptr(ws), max(n_ws, 0),
+            ptr(table), max(n_tab, 0))
+    return sums
+
+
+def _ssim_operand_rule(what, tensors, sample_format):
+    """the checks ssim_sums makes of its operands, for every tensor of `tensors` -> (kind, depth)"""
+    first = tensors[0]
+    for t in tensors:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RcbError(f"{what}: a and b must be GPU tensors (the HIP path has no CPU fallback)")
+        if sample_format is None and t.dtype in (torch.uint16, torch.int16):
+            raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.u16(depth) or .s16()): the depth is not in the "
+                             "dtype" % (what, t.dtype))
+        if t.device != first.device:
+            raise RcbError(f"{what}: operands on {first.device} and {t.device}")
+    for t in tensors:                                        # (a format reads every dtype of its width: uint16 and int16 views)
+        kind, depth, _ = _sample_rule(what, t.dtype, sample_format)
+        if sample_format is None and t.dtype != first.dtype:
+            raise RcbError(f"{what}: operands of {first.dtype} and {t.dtype}: one dtype per call")
+    return kind, depth
+
+
+def _list_spans(what, name, tensors):
+    """a list of [H, W, C] tensors of one dtype as one operand of rcb_ssim_list: the lowest address among them is the base, the
+    buffer runs to the end of the highest storage (signal_patch_ragged's rule) -> (base address, elements, spans int64 [n, 4])"""
+    item = tensors[0].element_size()
+    base = min(t.data_ptr() for t in tensors)
+    end = max(t.untyped_storage().data_ptr() + t.untyped_storage().nbytes() for t in tensors)
+    spans = np.zeros((len(tensors), 4), dtype=np.int64)
+    for k, t in enumerate(tensors):
+        if (t.data_ptr() - base) % item:
+            raise RcbError(f"{what}: image {k} of {name} lies {t.data_ptr() - base} bytes above the lowest one: no whole number of "
+                           f"{item}-byte elements")
+        spans[k] = [(t.data_ptr() - base) // item] + [int(v) for v in t.stride()]
+    return base, (end - base) // item, spans
+
+
+def ssim_sums_list(a, b, sample_format=None, scales=1):
+    """`ssim_sums` for two LISTS of images of mixed sizes in ONE call (rcb_ssim_list: one memset, scales - 1 pooling and `scales`
+    SSIM launches, however long the lists are): a[k], b[k] are GPU tensors [H_k, W_k, C] of one dtype, C and device.  Each tensor
+    of each operand has ANY strides, storage offset and allocation -- a transposed or channel-first view, a window of a larger
+    image, an expanded channel; nothing is copied: per operand the lowest address is the base and every image goes to the kernel
+    as its offset from it and its own strides (an offset that is no whole number of elements is an RcbError).
+    -> sums int64 [n, scales, C, 2]; row k is bitwise ssim_sums(a[k][None], b[k][None]).  There is no map.  `scales` holds for
+    the whole list: every image must allow it.  sample_format: ssim_sums's.  The only host sync is the table upload."""
+    what = "ssim_sums_list"
+    a, b = list(a), list(b)
+    if len(a) != len(b):
+        raise RcbError(f"{what}: {len(a)} images in a, {len(b)} in b")
+    if not a:
+        raise RcbError(f"{what}: an empty list of images")
+    kind, depth = _ssim_operand_rule(what, a + b, sample_format)
+    Cc = int(a[0].shape[-1]) if a[0].dim() == 3 else 0
+    for k, (x, y) in enumerate(zip(a, b)):
+        if x.dim() != 3 or tuple(x.shape) != tuple(y.shape) or x.shape[-1] != Cc:
+            raise RcbError(f"{what}: image {k} is {tuple(x.shape)} in a and {tuple(y.shape)} in b; both are [H, W, C] with the C of "
+                           "the whole list")
+    sizes = np.asarray([[int(t.shape[0]), int(t.shape[1])] for t in a], dtype=np.int32)
+    a_base, a_elems, a_spans = _list_spans(what, "a", a)
+    b_base, b_elems, b_spans = _list_spans(what, "b", b)
+    return _ssim_list_launch(a_base, a_elems, b_base, b_elems, kind, depth, sizes, a_spans, b_spans, Cc, scales, a[0].device)
+
+
+def ssim_sums_frames(a, b, sample_format=None, scales=1):
+    """The per-FRAME sums of clips a, b [n, T, H, W, C] (any strides) in one rcb_ssim_list call: the n * T frames are the list, frame
+    (i, t) at offset i * stride_n + t * stride_T with the clip's row, column and channel strides -- table rows built from the
+    strides, no views.  -> sums int64 [n, T, scales, C, 2]; frame (i, t)'s slice is bitwise ssim_sums(a[i, t][None], b[i, t][None])."""
+    what = "ssim_sums_frames"
+    kind, depth = _ssim_operand_rule(what, [a, b], sample_format)
+    if a.dim() != 5 or tuple(a.shape) != tuple(b.shape):
+        raise RcbError(f"{what}: a {tuple(a.shape)} and b {tuple(b.shape)} must be [n, T, H, W, C] of one shape")
+    n, T, H, W, Cc = (int(v) for v in a.shape)
+    if n * T == 0:
+        raise RcbError(f"{what}: no frames in {tuple(a.shape)}")
+    sizes = np.empty((n * T, 2), dtype=np.int32)
+    sizes[:] = (H, W)
+    ends = []
+    for t_ in (a, b):
+        st = [int(v) for v in t_.stride()]
+        spans = np.empty((n, T, 4), dtype=np.int64)
+        spans[..., 0] = np.arange(n, dtype=np.int64)[:, None] * st[0] + np.arange(T, dtype=np.int64)[None, :] * st[1]
+        spans[..., 1:] = st[2:]
+        store = t_.untyped_storage()
+        ends.append((t_.data_ptr(), (store.data_ptr() + store.nbytes() - t_.data_ptr()) // t_.element_size(), spans.reshape(n * T, 4)))
+    sums = _ssim_list_launch(*ends[0][:2], *ends[1][:2], kind, depth, sizes, ends[0][2], ends[1][2], Cc, scales, a.device)
+    return sums.view(n, T, int(scales), Cc, 2)
 
 
 def _win_geo(shape):

@@ -21,7 +21,7 @@ from . import train_step
 from .ops import LevelSpec, SirenMeta
 from .upsample_fast import (hip_path_supported, tiled_2d_preferred, phase_form_preferred, phase_module,
                             stitched2d_module, upsample_cifar_hip)
-from .utils import SampleFormat, count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs, metric_device, ssim_device
+from .utils import SampleFormat, count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs, metric_device, ssim_device, ssim_frames_device
 from .utils import map_hierarchical_model_to_int_weights  # noqa: F401  (module-level name, as upstream imports it)
 
 
@@ -168,11 +168,27 @@ class InrGeometry:
         return self.report(x, self.patch_signals(signals, size, sample_format, sizes=sizes), size=size, sample_format=sample_format,
                            sizes=sizes)
 
+    @staticmethod
+    def _ssim_format(who, sigs, sample_format):
+        """what the SSIM reports refuse of their sources -> the format the reconstruction is rounded to"""
+        for t in sigs:
+            if sample_format is None and t.dtype in (torch.uint16, torch.int16):
+                raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.u16(depth)): the depth is not in "
+                                 "the dtype" % (who, t.dtype))
+            if t.dtype.is_floating_point:
+                raise ValueError("%s: SSIM compares the delivered integers with the source's: %s signals have none"
+                                 % (who, t.dtype))
+        fmt = sample_format if sample_format is not None else SampleFormat.u8()
+        if fmt.kind not in (SampleFormat.U8, SampleFormat.U16):
+            raise ValueError("%s: SSIM is defined for u8 and u16 images, not %r" % (who, fmt))
+        return fmt
+
     def report_ssim(self, x, signals, size=None, sample_format=None, sizes=None, multiscale=False):
         """SSIM (with `multiscale`: MS-SSIM) of the images this model delivers against the whole source `signals`, fp64 per signal
         (the model with `predict`, as `report`): predict, round to the format's integers at each signal's own size
-        (ops.recon_finish(want_int=True, size=) / ops.recon_finish_ragged for sizes=), then rcb_ssim on those integers against the
-        integers of `signals` (utils.ssim_device; the definition is include/rcb.h's).  The figure of the DELIVERED image: nothing
+        (ops.recon_finish(want_int=True, size=) / ops.recon_finish_ragged for sizes=), then rcb_ssim -- for sizes= ONE rcb_ssim_list
+        call, whatever the length of the list -- on those integers against the integers of `signals` (utils.ssim_device; the
+        definition is include/rcb.h's).  The figure of the DELIVERED image: nothing
         but the sums leaves the device.
         signals: [n, *size, C] integer images on the model's grid (size None) or of extent `size` inside it, any strides; with
         sizes= a LIST of [*sizes[k], C] tensors -- a portrait signal as compress_signal_list cuts it: its transposed view, and
@@ -185,16 +201,7 @@ class InrGeometry:
             raise ValueError("report_ssim: size and sizes exclude each other")
         listed = sizes is not None
         sigs = list(signals) if listed else [signals]
-        for t in sigs:
-            if sample_format is None and t.dtype in (torch.uint16, torch.int16):
-                raise ValueError("report_ssim: %s signals need sample_format= (utils.SampleFormat.u16(depth)): the depth is not in "
-                                 "the dtype" % (t.dtype,))
-            if t.dtype.is_floating_point:
-                raise ValueError("report_ssim: SSIM compares the delivered integers with the source's: %s signals have none"
-                                 % (t.dtype,))
-        fmt = sample_format if sample_format is not None else SampleFormat.u8()
-        if fmt.kind not in (SampleFormat.U8, SampleFormat.U16):
-            raise ValueError("report_ssim: SSIM is defined for u8 and u16 images, not %r" % (fmt,))
+        fmt = self._ssim_format("report_ssim", sigs, sample_format)
         layout = self.signal_layout()
         grid = tuple(n * s for n, s in zip(layout.patch_nums, layout.patch_size))
         if listed:
@@ -219,6 +226,36 @@ class InrGeometry:
             return ssim_device(q, [t.to(dev) for t in sigs], sample_format=fmt, multiscale=multiscale)
         q, _, _, _ = ops.recon_finish(y_pred, layout=layout, size=size, sample_format=fmt, want_int=True)
         return ssim_device(q, signals.to(dev), sample_format=fmt, multiscale=multiscale)
+
+    def report_ssim_frames(self, x, signals, size=None, sample_format=None, multiscale=False):
+        """Per-frame SSIM (with `multiscale`: MS-SSIM) of the clips this model delivers against the whole source `signals`, fp64
+        [n, T]; the caller averages.  For the 3-D presets, axis 0 of the grid being the frame axis: predict, round to the format's
+        integers (ops.recon_finish(want_int=True, size=)), then every frame of every clip in ONE rcb_ssim_list call against the
+        source's (ops.ssim_sums_frames): nothing but the sums leaves the device.
+        signals: [n, T, H, W, C] integer clips on the model's grid (size None) or of extent `size` = (T, H, W) inside it, any
+        strides.  sample_format: needed for 16-bit signals (None: uint8).
+        ValueError, with the reason: a preset that is not 3-D, fp32 (or s16) signals, a 16-bit tensor without a format, a frame
+        smaller than 11 (multiscale: 176) per side, a wrong shape."""
+        who = "report_ssim_frames"
+        if self.data_dim != 3:
+            raise ValueError("%s: per-frame SSIM is defined for 3-D presets, this one has %d axes" % (who, self.data_dim))
+        fmt = self._ssim_format(who, [signals], sample_format)
+        layout = self.signal_layout()
+        grid = tuple(n * s for n, s in zip(layout.patch_nums, layout.patch_size))
+        extent = tuple(int(v) for v in size) if size is not None else grid
+        need = 176 if multiscale else 11
+        if len(extent) != 3 or min(extent[1:]) < need:
+            raise ValueError("%s: a frame of %s is too small for %s (both sides at least %d)"
+                             % (who, " x ".join(str(v) for v in extent[1:]),
+                                "MS-SSIM's five scales" if multiscale else "SSIM's 11-tap window", need))
+        want = extent + (self.dims[-1],)
+        if tuple(signals.shape[1:]) != want:
+            raise ValueError("%s: signals of shape %r, expected %r" % (who, tuple(signals.shape[1:]), want))
+        dev = self.loc.device
+        with torch.no_grad():
+            y_pred = self.predict(x.to(dev)).detach().to(torch.float32).contiguous()
+        q, _, _, _ = ops.recon_finish(y_pred, layout=layout, size=size, sample_format=fmt, want_int=True)
+        return ssim_frames_device(q, signals.to(dev), sample_format=fmt, multiscale=multiscale)
 
 
 class PriorBNNmodel(nn.Module, InrGeometry):

@@ -490,38 +490,48 @@ def ssim_positions(H, W, scale=0):
 
 
 def _ssim_sums_host(sums, H, W, scales=None):
+    """-> (the sums as numpy int64 [n, scales, C, 2], H per image, W per image); H and W are one size for all images or one
+    per image"""
     s = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
     if s.ndim != 4 or s.shape[-1] != 2 or s.dtype != np.int64:
         raise ValueError("the sums of rcb_ssim are int64 [n, scales, C, 2], got %s %r" % (s.dtype, s.shape))
     if scales is not None and s.shape[1] != scales:
         raise ValueError("%d scales are needed, the sums hold %d" % (scales, s.shape[1]))
-    if ssim_positions(H, W, s.shape[1] - 1) < 1 or min(int(H) >> (s.shape[1] - 1), int(W) >> (s.shape[1] - 1)) < SSIM_TAPS:
-        raise ValueError("an image of %d x %d has no %d scales (both sides at least %d)"
-                         % (H, W, s.shape[1], SSIM_TAPS << (s.shape[1] - 1)))
-    return s
+    per = []
+    for name, v in (("H", H), ("W", W)):
+        v = [int(u) for u in np.asarray(v).reshape(-1)] if np.ndim(v) else [int(v)] * s.shape[0]
+        if len(v) != s.shape[0]:
+            raise ValueError("%d values of %s for the sums of %d images" % (len(v), name, s.shape[0]))
+        per.append(v)
+    for h, w in zip(*per):
+        if ssim_positions(h, w, s.shape[1] - 1) < 1 or min(h >> (s.shape[1] - 1), w >> (s.shape[1] - 1)) < SSIM_TAPS:
+            raise ValueError("an image of %d x %d has no %d scales (both sides at least %d)"
+                             % (h, w, s.shape[1], SSIM_TAPS << (s.shape[1] - 1)))
+    return s, per[0], per[1]
 
 
 def ssim_from_sums(sums, H, W):
-    """SSIM per image, fp64 [n], from rcb_ssim's sums [n, scales, C, 2] of H x W images: the mean over the scale-0 positions and
-    the channels, (exact integer sum over the channels) / 2^36 / (positions * C)"""
-    s = _ssim_sums_host(sums, H, W)
-    count = float(ssim_positions(H, W) * s.shape[2])
-    return np.asarray([float(sum(int(v) for v in img[0, :, 0])) / SSIM_FX_SCALE / count for img in s], dtype=np.float64)
+    """SSIM per image, fp64 [n], from rcb_ssim's sums [n, scales, C, 2] of H x W images (H, W: one size, or one per image as
+    rcb_ssim_list scores them): the mean over the scale-0 positions and the channels, (exact integer sum over the channels) /
+    2^36 / (positions * C)"""
+    s, Hs, Ws = _ssim_sums_host(sums, H, W)
+    return np.asarray([float(sum(int(v) for v in img[0, :, 0])) / SSIM_FX_SCALE / float(ssim_positions(h, w) * s.shape[2])
+                       for img, h, w in zip(s, Hs, Ws)], dtype=np.float64)
 
 
 def msssim_from_sums(sums, H, W):
-    """MS-SSIM per image, fp64 [n], from five-scale sums (min(H, W) >= 176): per channel prod_{s<4} max(mean cs_s, 0)^w_s *
-    max(mean ssim_4, 0)^w_4 with w = MSSSIM_WEIGHTS, the factors multiplied in scale order, then the mean over the channels --
-    the per-channel convention of the common PyTorch implementation.  Scale s is the floor-pooled one of rcb_ssim; for even
-    sizes it coincides with the padded and the truncating conventions."""
-    s = _ssim_sums_host(sums, H, W, scales=5)
+    """MS-SSIM per image, fp64 [n], from five-scale sums (min(H, W) >= 176; H, W: one size, or one per image): per channel
+    prod_{s<4} max(mean cs_s, 0)^w_s * max(mean ssim_4, 0)^w_4 with w = MSSSIM_WEIGHTS, the factors multiplied in scale order,
+    then the mean over the channels -- the per-channel convention of the common PyTorch implementation.  Scale s is the
+    floor-pooled one of rcb_ssim; for even sizes it coincides with the padded and the truncating conventions."""
+    s, Hs, Ws = _ssim_sums_host(sums, H, W, scales=5)
     out = []
-    for img in s:
+    for img, h, w in zip(s, Hs, Ws):
         total = None
         for c in range(s.shape[2]):
             p = None
             for k in range(5):
-                mean = float(int(img[k, c, 1 if k < 4 else 0])) / SSIM_FX_SCALE / float(ssim_positions(H, W, k))
+                mean = float(int(img[k, c, 1 if k < 4 else 0])) / SSIM_FX_SCALE / float(ssim_positions(h, w, k))
                 f = max(mean, 0.0) ** MSSSIM_WEIGHTS[k]
                 p = f if p is None else p * f
             total = p if total is None else total + p
@@ -529,24 +539,49 @@ def msssim_from_sums(sums, H, W):
     return np.asarray(out, dtype=np.float64)
 
 
+def _ssim_need(who, H, W, multiscale):
+    need = SSIM_TAPS << 4 if multiscale else SSIM_TAPS
+    if min(H, W) < need:
+        raise ValueError("%s: an image of %d x %d is too small for %s (both sides at least %d)"
+                         % (who, H, W, "MS-SSIM's five scales" if multiscale else "SSIM's 11-tap window", need))
+
+
 def ssim_device(a, b, sample_format=None, multiscale=False):
     """SSIM (or with `multiscale` MS-SSIM) of integer images on the GPU, fp64 [n]: a, b are [n, H, W, C] tensors of one integer
-    dtype with ANY strides (ops.ssim_sums), or two LISTS of [H_k, W_k, C] tensors of mixed sizes, scored with one rcb_ssim call
-    per signal (a one-launch list form does not exist).  Only the sums are read back.  sample_format: ops.ssim_sums's.  An image
-    too small for the scales asked (11 for SSIM, 176 for MS-SSIM, per side) is a ValueError."""
+    dtype with ANY strides (ops.ssim_sums), or two LISTS of [H_k, W_k, C] tensors of mixed sizes and layouts, scored in one call
+    whatever their number (ops.ssim_sums_list).  Only the sums are read back.  sample_format: ops.ssim_sums's.  An image too
+    small for the scales asked (11 for SSIM, 176 for MS-SSIM, per side) is a ValueError."""
     from . import ops
     if isinstance(a, (list, tuple)) or isinstance(b, (list, tuple)):
         if not isinstance(a, (list, tuple)) or not isinstance(b, (list, tuple)) or len(a) != len(b):
             raise ValueError("ssim_device: two lists of as many signals, or two tensors")
         if not a:
             return np.zeros(0, dtype=np.float64)
-        return np.concatenate([ssim_device(x[None], y[None], sample_format, multiscale) for x, y in zip(a, b)])
+        for x in a:
+            if x.dim() != 3:
+                raise ValueError("ssim_device: images are [n, H, W, C], got %d axes" % (x.dim() + 1))
+            _ssim_need("ssim_device", int(x.shape[0]), int(x.shape[1]), multiscale)
+        sums = ops.ssim_sums_list(a, b, sample_format=sample_format, scales=5 if multiscale else 1)
+        Hs, Ws = [int(x.shape[0]) for x in a], [int(x.shape[1]) for x in a]
+        return msssim_from_sums(sums, Hs, Ws) if multiscale else ssim_from_sums(sums, Hs, Ws)
     if a.dim() != 4:
         raise ValueError("ssim_device: images are [n, H, W, C], got %d axes" % a.dim())
     H, W = int(a.shape[1]), int(a.shape[2])
-    need = SSIM_TAPS << 4 if multiscale else SSIM_TAPS
-    if min(H, W) < need:
-        raise ValueError("ssim_device: an image of %d x %d is too small for %s (both sides at least %d)"
-                         % (H, W, "MS-SSIM's five scales" if multiscale else "SSIM's 11-tap window", need))
+    _ssim_need("ssim_device", H, W, multiscale)
     sums, _ = ops.ssim_sums(a, b, sample_format=sample_format, scales=5 if multiscale else 1)
     return msssim_from_sums(sums, H, W) if multiscale else ssim_from_sums(sums, H, W)
+
+
+def ssim_frames_device(a, b, sample_format=None, multiscale=False):
+    """SSIM (with `multiscale` MS-SSIM) per FRAME of integer clips a, b [n, T, H, W, C] (any strides) on the GPU, fp64 [n, T], in one
+    call (ops.ssim_sums_frames); the caller averages.  sample_format and the size rule: ssim_device's."""
+    from . import ops
+    if a.dim() != 5:
+        raise ValueError("ssim_frames_device: clips are [n, T, H, W, C], got %d axes" % a.dim())
+    n, T, H, W = (int(v) for v in a.shape[:4])
+    _ssim_need("ssim_frames_device", H, W, multiscale)
+    if n * T == 0:
+        return np.zeros((n, T), dtype=np.float64)
+    sums = ops.ssim_sums_frames(a, b, sample_format=sample_format, scales=5 if multiscale else 1)
+    flat = sums.reshape(n * T, *sums.shape[2:])
+    return (msssim_from_sums(flat, H, W) if multiscale else ssim_from_sums(flat, H, W)).reshape(n, T)
