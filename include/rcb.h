@@ -7,7 +7,7 @@
  * (file:line relative to the reference root).  Conventions:
  *   - plain device pointers + explicit sizes; the caller (PyTorch, or any HIP host) allocates
  *     every buffer including outputs; nothing is allocated, freed or synchronised inside (but for the one table upload of the
- *     two per-signal entries of 413 and of the list entry of 415, which say so);
+ *     two per-signal entries of 413, of the list entry of 415 and of the resize entry of 416, which say so);
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it;
  *   - return value: 0 = ok, < 0 = argument/shape error (RCB_ERR_*), > 0 = hipError_t;
  *   - no global mutable state besides the thread-local last-error string; re-entrant per stream;
@@ -26,10 +26,10 @@ extern "C" {
  * rcb_level.scale_is_sigma, rcb_struct_bytes, the hi / lo operand planes of the A transform; 408: rcb_upconv_fwd23;
  * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop; 412: rcb_signal_patch_fmt,
  * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged; 414: rcb_ssim_workspace_bytes, rcb_ssim;
- * 415: rcb_ssim_list_table_bytes, rcb_ssim_list_workspace_bytes, rcb_ssim_list_plan, rcb_ssim_list).  A binding
- * compares
+ * 415: rcb_ssim_list_table_bytes, rcb_ssim_list_workspace_bytes, rcb_ssim_list_plan, rcb_ssim_list;
+ * 416: rcb_resize_taps, rcb_resize_table_bytes, rcb_resize).  A binding compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 415
+#define RCB_VERSION 416
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -901,6 +901,70 @@ int rcb_ssim_list(const void* a, int64_t a_elems, const void* b, int64_t b_elems
                   const int32_t* sizes, const int64_t* a_spans, const int64_t* b_spans, int32_t C, const double* win, double c1,
                   double c2, int32_t scales, int64_t* sums, void* workspace, int64_t workspace_bytes, void* table,
                   int64_t table_bytes, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (416): resize image and video sources -- what the reference's video loader does before anything else (data/video.py:26-31:
+ * the first 24 frames, centre-cropped to 240 x 240 and resized to 128 x 128 with torchvision's Resize: bilinear, antialiased,
+ * half-pixel centres) and what every codec comparison at a reduced resolution starts with.  The resized integers are the SOURCE
+ * the finish and SSIM entries score against.  The centre crop is a view (utils.center_crop: top = int(round((H - h) / 2.0)),
+ * Python's round, torchvision's rule); the filter is defined here.
+ *
+ * Taps of one axis of n_in input and n_out output positions, every step one IEEE fp64 operation (no contraction):
+ *   scale = (double)n_in / n_out;  support = scale >= 1 ? scale : 1;  inv = scale >= 1 ? 1 / scale : 1
+ *   output i:  center = scale * (i + 0.5);  first = max((int)((center - support) + 0.5), 0), the conversion truncating;
+ *              last = min((int)((center + support) + 0.5), n_in);  count = last - first
+ *              g_j = max(0, 1 - |(((first + j) - center) + 0.5) * inv|), j = 0 .. count - 1;  total = ((g_0 + g_1) + ...), ascending;
+ *              w_j = g_j / total
+ *   n_in == n_out:  first = i, count = 1, w_0 = 1.0 -- the formulas give that tap and behind it one of weight exactly 0, which is
+ *   dropped on this axis, so that the identity returns every sample bit for bit, -0.0 and the non-finite ones included.
+ *   n_in <= 16 n_out, hence count <= 33 = RCB_RESIZE_MAX_TAPS; a steeper reduction is RCB_ERR_UNSUPPORTED.  Upscaling by any
+ *   factor is allowed.  Sides up to 2^24.
+ * Filter: separable, the LAST spatial axis first, taps ascending, the first product starting the sum (w, f the taps of column x;
+ *   u, g those of row y):  t(r, x) = ((w_0 v(r, f) + w_1 v(r, f+1)) + ...),  a(y, x) = ((u_0 t(g, x) + u_1 t(g+1, x)) + ...), v the
+ *   sample as an exact fp64 value, t never rounded below fp64.
+ * Output, L = 255 (kind 0) or 2^depth - 1 (kind 2):
+ *   kind 0 (uint8) and kind 2 (u16 at depth 9 .. 16):  q = (int)rint(fmin(fmax(a, 0), L)), half to even: ONE rounding, at the end.  A
+ *          stored 16-bit value above L goes in as it is and comes out clamped.
+ *   kind 1 (fp32):  (float)a, one rounding, no clamp.  Non-finite values follow the arithmetic: a zero weight times an infinity
+ *          is a NaN.
+ *   kind 3 (s16) is refused: resampling audio is a different filter question.
+ * This is torch.nn.functional.interpolate(mode="bilinear", antialias=True, align_corners=False) evaluated in fp64 and rounded
+ * once (tests/test_resize_emul_cpu.py holds the two together).  torchvision's uint8 path -- fixed-point weights, a rounding to
+ * uint8 BETWEEN the two passes -- is NOT copied: it differs from this definition by at most one step in a share of the samples
+ * (12 - 20 % on random images; profiles/r22_resize_vs_uint8_path.txt).
+ *
+ * rcb_resize_taps: the host arithmetic above, callable without a device.  first, count: int32 [n_out]; w: double [n_out][max_taps],
+ * row i holding its count taps and then +0.0.  -> the longest count of the axis, or an error (< 0): a size below 1 (RCB_ERR_SHAPE),
+ * more than 16 : 1 or a side above 2^24 (RCB_ERR_UNSUPPORTED), a null pointer (RCB_ERR_ARG), max_taps below the longest count
+ * (RCB_ERR_SHAPE; nothing is written).
+ *
+ * rcb_resize_table_bytes: the device table of rcb_resize for these sizes, 8 * (H_out * (1 + ky) + W_out * (1 + kx)) bytes, ky / kx
+ * the longest count of the row / column axis: int32 first and count of both axes, then the weights at the pitch of their axis.
+ * -1 for a refused shape.
+ *
+ * rcb_resize: src holds n signals of T frames (T = 1: images) of H_in x W_in positions and C channels.
+ *   strides  HOST int64[5]: ELEMENT strides of {signal, frame, row, column, channel}, all >= 0; `offset` (>= 0): the element of
+ *            signal 0, frame 0, row 0, column 0, channel 0 -- where the corner of a crop goes.  The addressing rule of
+ *            rcb_signal_patch, 64-bit offsets: channel-first storage, transposed axes, a window of a larger signal, a broadcast
+ *            channel and a clip's frame stride are all this one call; nothing need be contiguous.
+ *   src_elems  elements of the source buffer from `src`; the farthest element read, offset + (n - 1) s_0 + (T - 1) s_1 +
+ *            (H_in - 1) s_2 + (W_in - 1) s_3 + (C - 1) s_4, must lie below it (checked on the host): every read is inside.
+ *   dst      contiguous [n][T][H_out][W_out][C] of the source's type.
+ *   table    device buffer of rcb_resize_table_bytes(H_in, W_in, H_out, W_out) bytes, 8-byte aligned, the caller's to allocate.
+ *            The entry builds both tap tables through rcb_resize_taps, writes them there on `stream` and synchronises the stream
+ *            ONCE for that upload -- the rule of the entries of 413 and 415: an I/O end, NOT for graph capture.
+ * One workgroup per tile of 8 x 32 output positions of one frame; the row-filtered values live in LDS as fp64.  A frame's output
+ * is bitwise the same alone, in any batch and from run to run.  One input size per call; there is no list form.
+ * n = 0 succeeds and launches nothing.  Refused (RCB_ERR_*), nothing launched and nothing uploaded: a kind other than 0, 1, 2; a
+ * depth outside 9 .. 16 for kind 2 or non-zero for another kind; C outside 1 .. 32; a size (or T) below 1; n_in > 16 n_out on
+ * either axis; a negative stride or offset; a reach past src_elems; null src, dst, strides or table; a table that is too small or
+ * misaligned; more than 2^31 - 1 workgroups. */
+#define RCB_RESIZE_MAX_TAPS 33
+int rcb_resize_taps(int32_t n_in, int32_t n_out, int32_t* first, int32_t* count, double* w, int32_t max_taps);
+int64_t rcb_resize_table_bytes(int32_t H_in, int32_t W_in, int32_t H_out, int32_t W_out);
+int rcb_resize(const void* src, int64_t src_elems, int32_t kind, int32_t depth, int64_t n, int32_t T, int32_t H_in, int32_t W_in,
+               int32_t C, const int64_t* strides, int64_t offset, int32_t H_out, int32_t W_out, void* dst, void* table,
+               int64_t table_bytes, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -64,7 +64,7 @@ class LevelBwd(C.Structure):
 
 _lib = None
 # the header these mirrors were written against (include/rcb.h: RCB_VERSION) and the structures load() verifies by size
-ABI_VERSION = 415
+ABI_VERSION = 416
 _MIRRORS = {0: SirenDesc, 1: Level, 2: LevelBwd, 3: AdamCfg, 4: AdamTensor, 5: RecDesc}
 
 # The prototype of every entry point of include/rcb.h, in header order: name -> (restype, [argtypes]).  load() applies it, so
@@ -155,6 +155,9 @@ PROTOTYPES = {
     "rcb_ssim_list_plan": (_int, [_i64, _p, _i32, _i32, _p, _i64]),
     "rcb_ssim_list": (_int, [_p, _i64, _p, _i64, _i32, _i32, _i64, _p, _p, _p, _i32, _p, _f64, _f64, _i32, _p, _p, _i64, _p, _i64,
                              _p]),
+    "rcb_resize_taps": (_int, [_i32, _i32, _p, _p, _p, _i32]),
+    "rcb_resize_table_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "rcb_resize": (_int, [_p, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _i32, _p, _i64, _i32, _i32, _p, _p, _i64, _p]),
 }
 EXPORTS = list(PROTOTYPES)
 

@@ -327,6 +327,21 @@ def compress_signals(config, dataset, checkpoint, signals, x=None, channels_firs
     return compress(config, dataset, checkpoint, _default_x(x, config, device, y.shape[0]), y, sample_format=sample_format, **kw)
 
 
+def compress_resized(config, dataset, checkpoint, signals, crop=None, channels_first=False, sample_format=None, **kw):
+    """`compress_signals` on sources of any size, brought to the preset's grid on the device first (utils.resize_to_preset, which
+    documents crop / channels_first and the order of the steps: first frames, landscape swap, centre crop, one antialiased
+    resize with one rounding -- data/video.py:26-31 with crop=(240, 240) on the video preset).  -> what compress_signals returns,
+    plus the resized source [n, *grid, C] of the signals' dtype: the signal that was coded, hence the one the decoded integers are
+    scored against (report_signals, report_ssim, report_ssim_frames).  The stream is that of a signal at the preset's grid:
+    bitstream.decode_signal decodes it.  Every other argument is `compress`'s."""
+    from . import utils
+    device = kw.get("device", "cuda")
+    (moved,) = _signal_views("compress_resized", [signals], sample_format, device)
+    resized = utils.resize_to_preset(config, moved, crop=crop, channels_first=channels_first, sample_format=sample_format)
+    out = compress_signals(config, dataset, checkpoint, resized, landscape=False, sample_format=sample_format, **kw)
+    return (*out, resized)
+
+
 def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_first=False, bitstream_path=None,
                          sample_format=None, **kw):
     """`compress_signals` for signals of ANY size that the preset can be fitted to: `signals` is [n, *size, C] (or [n, C, *size]

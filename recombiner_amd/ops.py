@@ -1638,6 +1638,48 @@ def ssim_sums_frames(a, b, sample_format=None, scales=1):
     return sums.view(n, T, int(scales), Cc, 2)
 
 
+# ---------------------------------------------------------------------------------------------------
+# N4 (416): resize image and video sources (rcb_resize)
+# ---------------------------------------------------------------------------------------------------
+def resize(src, size, sample_format=None, out=None):
+    """Images [n, H, W, C] or clips [n, T, H, W, C] on the GPU -> the same at size = (H_out, W_out), a contiguous tensor of the
+    source's dtype (rcb_resize; the definition is include/rcb.h's: antialiased triangle filter, half-pixel centres, fp64, ONE
+    rounding at the end -- torch's interpolate(mode="bilinear", antialias=True) in fp64, rounded once).  src is uint8, fp32, or a
+    16-bit dtype with sample_format=utils.SampleFormat.u16(depth) (ValueError without it: the depth is not in the dtype; s16 is
+    refused by the library), with ANY strides and storage offset -- a utils.center_crop, a channel-first or transposed view, a
+    window of a larger tensor, an expanded channel, a clip's frame stride: the strides and the offset go to the kernel and
+    nothing is copied.  Reductions up to 16 : 1 per axis, any enlargement; one input size per call.
+    out: optional preallocated contiguous tensor of the result's shape and dtype.  The only host sync is the table upload."""
+    what = "resize"
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise RcbError(f"{what}: src must be a GPU tensor (the HIP path has no CPU fallback)")
+    if sample_format is None and src.dtype in (torch.uint16, torch.int16):
+        raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.u16(depth)): the depth is not in the dtype"
+                         % (what, src.dtype))
+    kind, depth, _ = _sample_rule(what, src.dtype, sample_format)
+    if src.dim() not in (4, 5) or len(size) != 2:
+        raise RcbError(f"{what}: src {tuple(src.shape)} must be [n, H, W, C] or [n, T, H, W, C], size (H_out, W_out)")
+    clip = src.dim() == 5
+    n, T = int(src.shape[0]), int(src.shape[1]) if clip else 1
+    H, W, Cc = (int(v) for v in src.shape[-3:])
+    Ho, Wo = int(size[0]), int(size[1])
+    st = [int(v) for v in src.stride()]
+    strides = (C.c_int64 * 5)(st[0], st[1] if clip else 0, *st[-3:])
+    lib = _lib.load()
+    n_tab = int(lib.rcb_resize_table_bytes(H, W, Ho, Wo)) if min(H, W, Cc) >= 1 and T >= 1 else -1
+    shape = (n, T, Ho, Wo, Cc) if clip else (n, Ho, Wo, Cc)
+    if out is None:                                          # (a refused shape: a one-element output, and the library says why)
+        out = torch.empty(shape if n_tab >= 0 else (1,), device=src.device, dtype=src.dtype)
+    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise RcbError(f"{what}: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {src.dtype} on the "
+                       "device of src")
+    table = torch.empty(max(n_tab, 8), device=src.device, dtype=torch.uint8)
+    store = src.untyped_storage()
+    _launch("rcb_resize", C.c_void_p(store.data_ptr()), store.nbytes() // src.element_size(), kind, depth, n, T, H, W, Cc, strides,
+            int(src.storage_offset()), Ho, Wo, C.c_void_p(out.data_ptr()), ptr(table), max(n_tab, 0))
+    return out
+
+
 def _win_geo(shape):
     nd = len(shape) - 2
     if nd < 1 or nd > 3 or shape[-1] % 8:

@@ -585,3 +585,75 @@ def ssim_frames_device(a, b, sample_format=None, multiscale=False):
     sums = ops.ssim_sums_frames(a, b, sample_format=sample_format, scales=5 if multiscale else 1)
     flat = sums.reshape(n * T, *sums.shape[2:])
     return (msssim_from_sums(flat, H, W) if multiscale else ssim_from_sums(flat, H, W)).reshape(n, T)
+
+
+# ---------------------------------------------------------------------------------------------
+# resizing sources to a preset's grid (include/rcb.h, N4 416; data/video.py:26-31)
+# ---------------------------------------------------------------------------------------------
+RESIZE_MAX_TAPS = 33                                         # RCB_RESIZE_MAX_TAPS
+
+
+def resize_taps(n_in, n_out):
+    """The tap tables of one axis of rcb_resize, from the C planner (rcb_resize_taps; no device needed): -> (first int32 [n_out],
+    count int32 [n_out], w float64 [n_out, 33], row i holding its count[i] normalised triangle weights and then +0.0).  A
+    refused pair (a size below 1, a reduction steeper than 16 : 1) is an RcbError."""
+    import ctypes
+    from . import _lib
+    lib = _lib.load()
+    rows = max(int(n_out), 1)
+    first, count = np.zeros(rows, dtype=np.int32), np.zeros(rows, dtype=np.int32)
+    w = np.zeros((rows, RESIZE_MAX_TAPS), dtype=np.float64)
+    rc = lib.rcb_resize_taps(int(n_in), int(n_out), ctypes.c_void_p(first.ctypes.data), ctypes.c_void_p(count.ctypes.data),
+                             ctypes.c_void_p(w.ctypes.data), RESIZE_MAX_TAPS)
+    if rc < 0:
+        _lib.check(rc, "rcb_resize_taps")
+    return first, count, w
+
+
+def center_crop(tensor, size, axes):
+    """A VIEW of `tensor` cropped about its centre to size[k] positions along axes[k]: the window starts at
+    int(round((n - size) / 2.0)) with Python's round (half to even) -- torchvision's CenterCrop rule.  Nothing is copied.
+    ValueError when an axis is shorter than the crop."""
+    size, axes = [int(v) for v in size], [int(a) for a in axes]
+    if len(size) != len(axes):
+        raise ValueError("center_crop: %d sizes for %d axes" % (len(size), len(axes)))
+    for s, a in zip(size, axes):
+        n = int(tensor.shape[a])
+        if s < 1 or s > n:
+            raise ValueError("center_crop: axis %d has %d positions, the crop asks for %d" % (a, n, s))
+        tensor = tensor.narrow(a, int(round((n - s) / 2.0)), s)
+    return tensor
+
+
+def resize_to_preset(config, signals, crop=None, channels_first=False, sample_format=None):
+    """Image or video sources of any size -> the preset's grid, on the GPU: the resized signals [n, *grid, C] of the source's
+    dtype, which are both what compress_signals / patch_signals cut and the SOURCE report_signals / report_ssim /
+    report_ssim_frames score against.  signals: [n, *spatial, C] (or [n, C, *spatial] with channels_first) for a preset of
+    data_dim 2 or 3, uint8, fp32 or a 16-bit dtype with sample_format=SampleFormat.u16(depth).  In order, all but the last step
+    views: the channel axis is moved last; 3-D: the first grid[0] frames are kept (a shorter clip is a ValueError); 2-D: the two
+    spatial axes are exchanged when the first is longer (signal_view's landscape rule); `crop` = (h, w): the centre crop of the
+    last two spatial axes (center_crop); ops.resize of those two axes to the grid's (one rounding; include/rcb.h).  With
+    crop=(240, 240) on the video preset this is data/video.py:27-31 -- the reference rounds twice there, see DESIGN 7."""
+    from . import ops
+    dd = config["data_dim"]
+    if dd not in (2, 3):
+        raise ValueError("resize_to_preset: presets of data_dim 2 and 3 have a size to resize to, not %d" % dd)
+    if signals.dim() != dd + 2:
+        raise ValueError("resize_to_preset: %d axes for a %d-D preset ([n, *spatial, C] expected)" % (signals.dim(), dd))
+    if channels_first:
+        signals = signals.movedim(1, -1)
+    if signals.shape[-1] != config["output_dim"]:
+        raise ValueError("resize_to_preset: %d channels, the preset has %d" % (signals.shape[-1], config["output_dim"]))
+    pn, ps = preset_grid(config)
+    grid = [pn[i] * ps[i] for i in range(dd)]
+    if dd == 3:
+        if signals.shape[1] < grid[0]:
+            raise ValueError("resize_to_preset: a clip of %d frames, the preset takes the first %d" % (signals.shape[1], grid[0]))
+        signals = signals.narrow(1, 0, grid[0])
+    elif signals.shape[1] > signals.shape[2]:
+        signals = signals.transpose(1, 2)
+    if crop is not None:
+        if len(crop) != 2:
+            raise ValueError("resize_to_preset: crop is (h, w) of the last two spatial axes")
+        signals = center_crop(signals, crop, (-3, -2))
+    return ops.resize(signals, grid[-2:], sample_format=sample_format)
