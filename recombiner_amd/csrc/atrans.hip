@@ -27,6 +27,7 @@
 // <= 7 column blocks: it reads its x fragment as fp32, forms hi / lo in registers (each row is converted once per
 // workgroup) and issues <= 28 MFMAs per chunk on <= 7 accumulator tiles; two waves per SIMD cover each other's LDS latency.
 // Workgroups sharing a row tile are mapped to one XCD (they re-read the same x rows through its L2).
+#include "kernel_stamps.h"
 #include "rcb_common.h"
 #include "prepare_bodies.h"
 
@@ -36,26 +37,20 @@
 
 using namespace rcb;
 
+// diagnostic builds: s_memtime stamps of workgroup 0's chunk loop, [wave][iteration][point] (-DRCB_STAMPS_ATRANS=1,
+// tools/atrans_stamps.py), and of EVERY logical workgroup of the last launch its s_memrealtime begin, end and its s_memtime begin,
+// end (-DRCB_STAMPS_ATRANS_WG=1, tools/atrans_wg_stamps.py)
+constexpr int WG_STAMPS = 8192;
+RCB_STAMPS_BUFFER(ATRANS, 8 * 40 * 6)
+RCB_STAMPS_BUFFER(ATRANS_WG, WG_STAMPS * 4)
+#define STAMP(it, pt) RCB_STAMP(ATRANS, blockIdx.x == 0 && (it) >= 0 && (it) < 40 && lane == 0, (wave * 40 + (it)) * 6 + (pt), memtime)
+
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// diagnostic builds only (python -m recombiner_amd.build --variant ... -DATRANS_DIAG=n): 1 = no output stores, 2 = every
-// chunk re-reads chunk 0 (cache-hot sources), 3 = no compute at all, 4 = fragment reads + conversion but no MFMAs, 6 = no DMAs
-// in the chunk loop; never defined in the library
-#ifndef ATRANS_DIAG
-#define ATRANS_DIAG 0
-#endif
-#ifndef ATRANS_STAMPS
-// diagnostic build: s_memtime stamps of workgroup 0's chunk loop (rcb_debug_atrans_stamps) and the begin / end of EVERY
-// workgroup of the last launch (rcb_debug_atrans_wg_stamps; tools/atrans_wg_stamps.py)
-#define ATRANS_STAMPS 0
-#endif
-#ifndef ATRANS_SPREAD_PIN
-#define ATRANS_SPREAD_PIN 1
-#endif
 constexpr int BM = 256, BK = 32, NT = 512, MAXL = RCB_ATRANS_MAX_LAYERS, MAXSEG = 7;
 constexpr int XT_BYTES = BM * BK * 4;              // fp32 image of the x tile (32 KB)
 
@@ -70,29 +65,10 @@ __device__ __forceinline__ void dma16(const void* g, char* l) {          // 64 l
   __builtin_amdgcn_global_load_lds(g, (lds_ptr_t)l, 16, 0, 0);
 }
 __device__ __forceinline__ f32x16 mma(bf16x8 a, bf16x8 b, f32x16 c) {
-#if ATRANS_DIAG == 4
-  asm volatile("" ::"v"(a), "v"(b));
-  return c;
-#else
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-#endif
 }
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#if ATRANS_STAMPS
-__device__ unsigned long long g_stamps[8][40][6];
-constexpr int WG_STAMPS = 8192;
-__device__ unsigned long long g_wg_stamps[WG_STAMPS][4];      // per logical workgroup: s_memrealtime begin, end; s_memtime begin, end
-#define STAMP(it, pt)                                                                 \
-  do {                                                                               \
-    if (blockIdx.x == 0 && (it) < 40) {                                              \
-      const unsigned long long t_ = __builtin_amdgcn_s_memtime();                    \
-      if (lane == 0) g_stamps[wave][it][pt] = t_;                                    \
-    }                                                                                \
-  } while (0)
-#else
-#define STAMP(it, pt)
-#endif
 
 struct AtArgs {
   const float* x;
@@ -192,7 +168,7 @@ __device__ __forceinline__ void run_segment(const AtArgs& a, const int4 sg, cons
   // DMA i (0 .. NDMA-1) of chunk kc: the wave's four x pieces, then its mapping pieces
   auto issue_one = [&](int kc_, int i) {
     char* __restrict__ st = lds + (kc_ % G::NSTAGE) * G::STAGE;
-    const int kc = ATRANS_DIAG == 2 ? 0 : kc0 + kc_;
+    const int kc = kc0 + kc_;
     if (i < 4) {
       // chunks past the end of the layer (its padding to a multiple of 32) meet zero rows of the mapping: any finite
       // values do, so they repeat the layer's last chunk instead of reading past the row
@@ -278,7 +254,7 @@ __device__ __forceinline__ void run_segment(const AtArgs& a, const int4 sg, cons
         acc[cb] = mma(xh[0], d0, acc[cb]);
         acc[cb] = mma(xh[1], d1, acc[cb]);
       }
-      if (ISSUE && ATRANS_DIAG != 6) {
+      if (ISSUE) {
 #pragma unroll
         for (int i = cb * G::NDMA / NCB; i < (cb + 1) * G::NDMA / NCB; ++i) issue_one(kn, i);
       }
@@ -290,9 +266,7 @@ __device__ __forceinline__ void run_segment(const AtArgs& a, const int4 sg, cons
           x_read(nxt);
         }
       }
-#if ATRANS_SPREAD_PIN
       __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     if (PREF) {
       STAMP(kn - 2, 4);
@@ -379,21 +353,20 @@ __device__ __forceinline__ void run_segment(const AtArgs& a, const int4 sg, cons
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       STAMP(kc, 2);
-      if (ATRANS_DIAG != 3) compute(lds + (kc % 3) * G::STAGE, lds + ((kc + 1) % 3) * G::STAGE, kc + 2, yes, yes);
-      else issue(kc + 2);
+      compute(lds + (kc % 3) * G::STAGE, lds + ((kc + 1) % 3) * G::STAGE, kc + 2, yes, yes);
       STAMP(kc, 5);
     }
     if (kc + 1 < nk) {
       wait_vm<G::NDMA>();
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
-      if (ATRANS_DIAG != 3) compute(lds + (kc % 3) * G::STAGE, lds + ((kc + 1) % 3) * G::STAGE, -1, no, yes);
+      compute(lds + (kc % 3) * G::STAGE, lds + ((kc + 1) % 3) * G::STAGE, -1, no, yes);
       ++kc;
     }
     wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    if (ATRANS_DIAG != 3) compute(lds + (kc % 3) * G::STAGE, lds, -1, no, no);
+    compute(lds + (kc % 3) * G::STAGE, lds, -1, no, no);
     __builtin_amdgcn_s_barrier();                            // (the next segment's first DMAs overwrite stages still being read)
   }
 
@@ -403,7 +376,7 @@ __device__ __forceinline__ void run_segment(const AtArgs& a, const int4 sg, cons
   const long long ldo = direct ? a.ld_out : a.ld_ws;
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) {
-    if (cb < ncb && (ATRANS_DIAG != 1 || a.rows < 0)) {
+    if (cb < ncb) {
       const int col = (cb0 + cb) * 32 + frow;
       if (col < K) {
 #pragma unroll
@@ -460,9 +433,7 @@ __global__ void __launch_bounds__(NT, 2) atrans_kernel(AtArgs a) {
   // workgroups that share a row tile (consecutive logical ids) onto one XCD: blocks b, b + 8, ... share an XCD
   int id = blockIdx.x;
   if ((a.n_wg & 7) == 0) id = (id & 7) * (a.n_wg >> 3) + (id >> 3);
-#if ATRANS_STAMPS
-  const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime(), ct0 = __builtin_amdgcn_s_memtime();
-#endif
+  RCB_STAMPS_ONLY(ATRANS_WG, const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime(), ct0 = __builtin_amdgcn_s_memtime();)
   const int s0 = a.seg_begin[id], s1 = a.seg_begin[id + 1];
   for (int s = s0; s < s1; ++s) {
     const int4 sg = a.segs[2 * s], sk = a.segs[2 * s + 1];
@@ -473,16 +444,15 @@ __global__ void __launch_bounds__(NT, 2) atrans_kernel(AtArgs a) {
       dispatch_segment<TERMS, false, PLANES>(a, sg, sk, lds);
     }
   }
-#if ATRANS_STAMPS
-  wait_vm<0>();                    // the output stores of every wave belong to the workgroup's time
-  __syncthreads();
-  if (threadIdx.x == 0 && id < WG_STAMPS) {
-    g_wg_stamps[id][0] = rt0;
-    g_wg_stamps[id][1] = __builtin_amdgcn_s_memrealtime();
-    g_wg_stamps[id][2] = ct0;
-    g_wg_stamps[id][3] = __builtin_amdgcn_s_memtime();
-  }
-#endif
+  RCB_STAMPS_ONLY(ATRANS_WG,
+                  wait_vm<0>();                    // the output stores of every wave belong to the workgroup's time
+                  __syncthreads();
+                  if (threadIdx.x == 0 && id < WG_STAMPS) {
+                    g_stamps_ATRANS_WG[4 * id + 0] = rt0;
+                    g_stamps_ATRANS_WG[4 * id + 1] = __builtin_amdgcn_s_memrealtime();
+                    g_stamps_ATRANS_WG[4 * id + 2] = ct0;
+                    g_stamps_ATRANS_WG[4 * id + 3] = __builtin_amdgcn_s_memtime();
+                  })
 }
 
 // ---- K-split launches: sum of the slabs in slab order (fixed: bitwise reproducible) ---------------------------------------
@@ -985,17 +955,3 @@ extern "C" int rcb_atrans_wgrad_narrow(const float* h, const void* h_hi, const v
   RCB_LAUNCH_CHECK();
   return RCB_OK;
 }
-
-#if ATRANS_STAMPS
-extern "C" int rcb_debug_atrans_stamps(unsigned long long* host, int32_t n) {
-  if (n > 8 * 40 * 6) n = 8 * 40 * 6;
-  hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * n);
-  return (int)e;
-}
-
-extern "C" int rcb_debug_atrans_wg_stamps(unsigned long long* host, int32_t n_wg) {
-  if (n_wg > WG_STAMPS) n_wg = WG_STAMPS;
-  hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_wg_stamps), sizeof(unsigned long long) * 4 * n_wg);
-  return (int)e;
-}
-#endif

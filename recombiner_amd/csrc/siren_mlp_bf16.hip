@@ -15,30 +15,15 @@
 //     transposed with ds_read_b64_tr_b16 (4 per operand), 2 MFMAs per layer per 32 pixels;
 //   * bias gradients: v_dot2c_f32_bf16 of the transposed dZ fragment against ones;
 //   * sin and cos are kept as packed bf16 (8 VGPRs per layer each).
+#include "kernel_stamps.h"
 #include "siren_op16.h"
 
 using namespace rcb;
 
-// Diagnostic build only (-DRCB_SIREN_STAMPS, tools/siren_stamps.py): wave 0 of every workgroup records s_memtime at its
-// phase boundaries into a device array read back through rcb_debug_read_stamps.  Nothing of this exists in the library.
-#ifdef RCB_SIREN_STAMPS
-__device__ unsigned long long g_siren_stamps[8192 * 16];
-#define RCB_STAMP(k)                                                                                      \
-  do {                                                                                                    \
-    if (threadIdx.x == 0 && blockIdx.x < 8192) g_siren_stamps[blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-extern "C" int rcb_debug_read_stamps(unsigned long long* dst, int n_entries) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_siren_stamps), sizeof(unsigned long long) * n_entries);
-}
-#else
-#define RCB_STAMP(k) do { } while (0)
-#endif
-#ifndef RCB_SIREN_DEFER_WGRAD
-#define RCB_SIREN_DEFER_WGRAD 1     // 0: write and read the weight-gradient images of a layer back to back (rounds 1-3; A/B builds)
-#endif
-#ifndef RCB_W32_DIRECT_FRAGS
-#define RCB_W32_DIRECT_FRAGS 0      // 1: gather the fragments straight from global memory (measured slower: 0.265 vs 0.254 ms; A/B builds)
-#endif
+// Diagnostic build only (-DRCB_STAMPS_SIREN=1, tools/siren_stamps.py): thread 0 of every workgroup records s_memtime at its
+// phase boundaries, 16 slots per workgroup.  Nothing of this exists in the library.
+RCB_STAMPS_BUFFER(SIREN, 8192 * 16)
+#define RCB_STAMP_WG(also, k) RCB_STAMP(SIREN, (also) && threadIdx.x == 0 && blockIdx.x < 8192, blockIdx.x * 16 + (k), memtime)
 
 namespace {
 using namespace rcb::op16;
@@ -77,11 +62,11 @@ struct Geo {
   static constexpr int TSA = 32;                   // bufA row stride (bf16 elements), XOR-swizzled 8-byte chunks
   static constexpr int TSBB = 32 * NB0;            // bufB row stride
   static constexpr int WAVE_TILE = 32 * (TSA + TSBB) * 2;   // bytes per wave and image set
-  // TWO image sets per wave (RCB_SIREN_DEFER_WGRAD): layer l's [pixel][feature] images are written while layer l + 1's are read
+  // TWO image sets per wave: layer l's [pixel][feature] images are written while layer l + 1's are read
   // back transposed for its weight gradient -- the write -> read round trip through LDS then has a whole layer of other work
   // in front of it instead of stalling the (in-order) wave twice per layer
   // (one input block only: with two -- 34 inputs, the video geometry -- the extra fragments spill)
-  static constexpr int NSET = (RCB_SIREN_DEFER_WGRAD && NB0 == 1) ? 2 : 1;
+  static constexpr int NSET = NB0 == 1 ? 2 : 1;
   static constexpr int LDS_MAIN = TILE_OFF + 4 * NSET * WAVE_TILE;
   // cross-wave reduction scratch: per wave, layer l stored [out][in] with row stride 33 (+ bias row)
   __host__ __device__ static constexpr int roff(int l) {
@@ -94,13 +79,10 @@ struct Geo {
 };
 
 // Waves per SIMD the register allocation aims at.  The loss / backward instances need their 231 registers: at three waves (<= 168)
-// they spill 142 of them and run 3.4 x slower (0.92 vs 0.27 ms; -DRCB_SIREN_WAVES=3 builds that variant).  The forward-only
+// they spill 142 of them and run 3.4 x slower (0.92 vs 0.27 ms).  The forward-only
 // instances (prediction, decoding) use ~130 and are 12 % faster when the allocator is TOLD three waves fit (0.136 -> 0.119 ms).
-#ifndef RCB_SIREN_WAVES
-#define RCB_SIREN_WAVES 2
-#endif
 template <typename T, int NH, int F, int E, int C, int MODE, bool IN16>
-__global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) siren_bf16_kernel(SirenArgs a) {
+__global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : 2) siren_bf16_kernel(SirenArgs a) {
   using G = Geo<NH, F, E, C>;
   using bf16x8 = typename Op16<T>::v8;
   using bf16x4 = typename Op16<T>::v4;
@@ -130,27 +112,11 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
     a.clock_probe[4 * blockIdx.x + 0] = __builtin_amdgcn_s_memtime();
     a.clock_probe[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
   }
-  RCB_STAMP(0);
+  RCB_STAMP_WG(true, 0);
   // ---- stage weights, build MFMA A-fragments, clear the zero padding of bufB ---------------------
   {
     const float* src = a.wvec + (long long)g * a.w_stride;
-#if RCB_W32_DIRECT_FRAGS
-    // The fragments are gathered straight from the row of wvec in global memory: every wave issues the 8 x (3 or 4) loads of
-    // its slots back to back -- ONE memory round trip -- instead of staging the row in LDS (a round trip and a barrier) and
-    // gathering from there (another 32 dependent LDS reads per lane).  The lines of the 13 KB row are fetched from L2 once and
-    // hit in L1 afterwards.  Only the biases live in LDS (wl keeps the layout of the parameter vector; nothing else of it
-    // is read).  The sine layers work in revolutions: w0 / 2 pi is folded into their forward fragments and biases.
-    const float* wsrc = src;
-#pragma unroll
-    for (int l = 0; l < NL; ++l)
-      if (tid < G::lout(l)) wl[G::off(l) + tid] = src[G::off(l) + tid] * (l < NH ? a.k_hi : 1.0f);
-    if (32 * NB0 > IN0) {
-      for (int p2 = 0; p2 < G::NSET; ++p2)
-        for (int i = lane; i < 32 * G::TSBB; i += 64) bufB_of(p2)[i] = (T)0.f;
-    }
-    RCB_STAMP(1);
-#else
-    const float* wsrc = wl;
+    const float* wsrc = wl;      // (gathering the fragments straight from global memory measured slower: 0.265 vs 0.254 ms)
     {
       // all loads first, then the LDS stores: written as `wl[i] = src[i]` in a loop the compiler waits for every load before
       // its store -- 13 serialized HBM round trips, 17 % of the whole kernel by the in-kernel stamps (tools/siren_stamps.py)
@@ -172,14 +138,13 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
         for (int i = lane; i < 32 * G::TSBB; i += 64) bufB_of(p2)[i] = (T)0.f;
     }
     __syncthreads();
-    RCB_STAMP(1);
+    RCB_STAMP_WG(true, 1);
     // the sine layers work in revolutions: w0 / 2 pi is folded into their forward fragments (below) and biases (here),
     // so the accumulator feeds v_sin / v_cos directly -- no scaling multiply per activation
     if (tid < HID) {
 #pragma unroll
       for (int l = 0; l < NH; ++l) wl[G::off(l) + tid] *= a.k_hi;
     }
-#endif
     // one fragment slot per wave and pass; `slot` is a compile-time constant inside the unrolled loop, so the layer
     // offsets and shapes below fold away and only the lane-dependent part of the gather address remains
 #pragma unroll
@@ -232,7 +197,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
     }
     __syncthreads();
   }
-  RCB_STAMP(2);
+  RCB_STAMP_WG(true, 2);
   auto FA = [&](int slot) -> bf16x8 {
     union { bf16x8 v; uint4 u; } fr;
     fr.u = frags[slot * 64 + lane];
@@ -405,10 +370,8 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
     fetch_targets(t0 + wave);
   }
   for (int t = t0 + wave; t < t1; t += 4) {
-#ifdef RCB_SIREN_STAMPS
-    if (t == t0 + wave) RCB_STAMP(14);
-    if (t == t0 + wave + 4) RCB_STAMP(15);
-#endif
+    RCB_STAMP_WG(t == t0 + wave, 14);
+    RCB_STAMP_WG(t == t0 + wave + 4, 15);
     const int p = t * 32 + q;
     const bool valid = p < P;
     const int pc = valid ? p : P - 1;                       // clamped: loads never leave the arrays
@@ -499,9 +462,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
       }
       continue;
     }
-#ifdef RCB_SIREN_STAMPS
-    if (t == t0 + wave) RCB_STAMP(8);
-#endif
+    RCB_STAMP_WG(t == t0 + wave, 8);
     // ---- output gradient (branch-free: selects on the prefetched targets) ---------------------------------
     f32x16 dz;
 #pragma unroll
@@ -524,9 +485,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
     bf16x8 av_d[2], bv_d[NB0][2];          // deferred form: the fragments of the layer ABOVE, read at the top of an iteration
 #pragma unroll
     for (int l = NL - 1; l >= 0; --l) {
-#ifdef RCB_SIREN_STAMPS
-      if (t == t0 + wave) RCB_STAMP(9 + (NL - 1 - l));
-#endif
+      RCB_STAMP_WG(t == t0 + wave, 9 + (NL - 1 - l));
       // the output layer's dz has C of its 32 rows set (registers r with rho(r, .) < C); packed straight from those, the other
       // entries as literal zeros: the generic pack8 of the tile made the compiler materialise the 13 zero registers of a
       // C = 3 tile and move them into place every tile (20 moves + 6 conversions of zeros per tile)
@@ -627,13 +586,13 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
     }
   }
   if (MODE == MODE_FWD) return;
-  RCB_STAMP(3);
+  RCB_STAMP_WG(true, 3);
 
   // ---- deterministic cross-wave reduction of the weight gradients -------------------------------------
   // per wave scratch: layer l as [out o][in i] rows of stride (32*NBl + 1) (conflict-free for the
   // lane = i writes and for the o-fastest reads below), followed by 32 bias slots
   __syncthreads();
-  RCB_STAMP(4);
+  RCB_STAMP_WG(true, 4);
   float* part = smem + wave * G::RED_WAVE;
 #pragma unroll
   for (int l = 0; l < NL; ++l) {
@@ -658,7 +617,7 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
     if (lane == 0) smem[4 * G::RED_WAVE + wave] = v;
   }
   __syncthreads();
-  RCB_STAMP(5);
+  RCB_STAMP_WG(true, 5);
   if (MODE == MODE_LOSS && tid == 0)
     a.sse[(long long)chunk * a.G + g] = ((smem[4 * G::RED_WAVE] + smem[4 * G::RED_WAVE + 1]) + smem[4 * G::RED_WAVE + 2]) + smem[4 * G::RED_WAVE + 3];
   {
@@ -686,8 +645,8 @@ __global__ void __launch_bounds__(256, MODE == MODE_FWD ? 3 : RCB_SIREN_WAVES) s
       }
     }
   }
-  RCB_STAMP(6);
-  RCB_STAMP(7);
+  RCB_STAMP_WG(true, 6);
+  RCB_STAMP_WG(true, 7);
   if (a.clock_probe != nullptr && blockIdx.x < 256 && tid == 0) {
     a.clock_probe[4 * blockIdx.x + 2] = __builtin_amdgcn_s_memtime();
     a.clock_probe[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memrealtime();

@@ -25,38 +25,23 @@
 // Matches prior_model.py:168-179,237 and test_model.py:347-355,625-627 like the kernels it stands beside.
 #include <type_traits>
 
+#include "kernel_stamps.h"
 #include "siren_op16.h"
 
 using namespace rcb;
+
+RCB_STAMPS_BUFFER(WAVE, 256)
 
 namespace {
 using namespace rcb::op16;
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 #define RCB_LDS(T) __attribute__((address_space(3))) T
-#ifndef RCB_WAVE_FSB
-#define RCB_WAVE_FSB 1       // scheduling barrier behind every forward layer (A/B builds)
-#endif
-#ifndef RCB_WAVE_PIPE_FWD
-#define RCB_WAVE_PIPE_FWD 1  // forward pass software-pipelined across the layers by hand (0: layer by layer, the compiler's order)
-#endif
-#ifndef RCB_WAVE_FAIR
-#define RCB_WAVE_FAIR 2     // issue priority between the two workgroups of a CU: 0 none (age decides), 1 time-sliced (measured: no gain), 2 swapped per row
-#endif
-#ifndef RCB_WAVE_FAIR_SHIFT
-#define RCB_WAVE_FAIR_SHIFT 14
-#endif
 #ifndef RCB_WAVE_PROBE_BLOCK0
 #define RCB_WAVE_PROBE_BLOCK0 0
 #endif
 #ifndef RCB_WAVE_PROBE_WAVE
 #define RCB_WAVE_PROBE_WAVE 0
-#endif
-#ifndef RCB_WAVE_ZPIPE
-#define RCB_WAVE_ZPIPE 1    // backward: the recomputed pre-activation one layer ahead (see compute_z)
-#endif
-#ifndef RCB_WAVE_BSB
-#define RCB_WAVE_BSB 1       // ... behind every backward layer
 #endif
 
 template <int NH, int F, int E, int C>
@@ -109,17 +94,9 @@ struct WGeo {
   static_assert(off(SPLIT) * 4 <= LFR_OFF && (DNET - off(SPLIT)) * 4 <= LFR_OFF, "a half of the row fits below the LDS fragments");
 };
 
-// Diagnostic build only (-DRCB_WAVE_STAMPS, tools/wave_stamps.py): wave 0 of workgroup 0 records s_memtime at the phase
-// boundaries of its first row into a device array read back through rcb_debug_wave_stamps.  Nothing of this is in the library.
-#ifdef RCB_WAVE_STAMPS
-__device__ unsigned long long g_wave_stamps[256];
-#define RCB_WSTAMP(k)                                                                                           \
-  do {                                                                                                          \
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (k) < 256) g_wave_stamps[(k)] = __builtin_amdgcn_s_memtime();     \
-  } while (0)
-#else
-#define RCB_WSTAMP(k) do { } while (0)
-#endif
+// Diagnostic build only (-DRCB_STAMPS_WAVE=1, tools/wave_stamps.py): thread 0 of workgroup 0 records s_memtime at the phase
+// boundaries of its last row (the buffer: RCB_STAMPS_BUFFER(WAVE, 256) above).  Nothing of this is in the library.
+#define RCB_STAMP_T0(k) RCB_STAMP(WAVE, blockIdx.x == 0 && threadIdx.x == 0 && (k) < 256, k, memtime)
 
 template <typename T>
 __device__ __forceinline__ f32x16 mfma_i4(const i32x4& a, const i32x4& b, const f32x16& c) {
@@ -253,31 +230,26 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
     a.clock_probe[4 * pblk + 0] = __builtin_amdgcn_s_memtime();
     a.clock_probe[4 * pblk + 1] = __builtin_amdgcn_s_memrealtime();
   }
-#if RCB_WAVE_FAIR
   const unsigned young = (blockIdx.x >= (gridDim.x >> 1)) ? 1u : 0u;      // the second workgroup of a CU (dispatch order)
-  unsigned long long fair_clk = __builtin_amdgcn_s_memtime();
+  __builtin_amdgcn_s_memtime();      // (the clock read of the retired time-sliced scheme: an instruction of the measured code)
   unsigned fair_row = 0;
-#endif
   for (int u = blockIdx.x * 4 + wave; u < nunits; u += gridDim.x * 4) {
-    RCB_WSTAMP(0);
-#if RCB_WAVE_FAIR == 2
-    // Mode 2 (shipped): the roles swap per ROW.  The SIMD arbitrates its two waves by priority, then age: left alone the wave of
+    RCB_STAMP_T0(0);
+    // Issue priority between the two workgroups of a CU: the roles swap per ROW.
+    // The SIMD arbitrates its two waves by priority, then age: left alone the wave of
     // the first-dispatched workgroup runs nearly unimpeded (88 us per row) and finishes its two rows at ~176 us, the other one
     // gets the leftover issue slots (106 us per row) and ends the kernel at ~212-222 us, its last 36 us alone on the SIMD
     // (rcb_siren_desc.clock_probe on both halves of the grid, tools/wave_spread.py).  Here the second workgroup of a CU takes the
     // higher priority on its odd rows: each workgroup is the pole for one row and the filler for the other, both halves finish
     // within 190-204 us and the kernel at ~210: 229.0 / 233.8 / 235.9 vs 237.6 / 237.8 / 237.5 us medians on one (slow) box.
-    // (Alternating the priority in time slices of 16 k cycles, mode 1, equalises the halves too -- at 200 / 210 us -- without
-    // moving the kernel's end: frequent flips cost what they gain.)
+    // (Alternating the priority in time slices of 16 k cycles equalises the halves too -- at 200 / 210 us -- without
+    // moving the kernel's end: frequent flips cost what they gain.  Measured: no gain.)
     if (young) {
       if (fair_row & 1u) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
     }
     ++fair_row;
-#endif
-#ifdef RCB_WAVE_STAMPS
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_wave_stamps[4] = __builtin_amdgcn_s_memrealtime();
-#endif
+    RCB_STAMP(WAVE, blockIdx.x == 0 && threadIdx.x == 0, 4, memrealtime);
     const int g = u % a.G, chunk = u / a.G;              // chunk-major: partial buffers are [chunk][g]
     const int n = g / a.S;
     const long long pe_row = (long long)g * a.P;          // pe / dpe as [G][P][E] (the stitched layouts stay with the workgroup kernel)
@@ -321,7 +293,7 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
         // it SEES them retired, drains vmcnt in front of every LDS access of the tile loop -- including the input prefetch)
         __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        RCB_WSTAMP(6 + 2 * half);
+        RCB_STAMP_T0(6 + 2 * half);
         auto W = [&](int idx) -> float { return wl[idx - f0]; };
 #pragma unroll
         for (int slot = 0; slot < NFA + NFB; ++slot) {
@@ -383,7 +355,7 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
           f8[1] = (h == 0) ? bl : (T)0.f;
           BFR[l] = as_i4(f8);
         }
-        RCB_WSTAMP(7 + 2 * half);
+        RCB_STAMP_T0(7 + 2 * half);
         if (half == 1) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
@@ -441,7 +413,7 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
       }
     };
     fetch(t0);
-    RCB_WSTAMP(1);
+    RCB_STAMP_T0(1);
     // The input gradient of tile t is stored at the top of iteration t + 1, right BEHIND the request for tile t + 2's inputs:
     // vmcnt retires in order, so a wait for loads also waits for every store issued before them -- and a store takes a few
     // thousand cycles to be acknowledged.  With the stores younger than the loads, and both in the loop's one block (the first
@@ -452,23 +424,8 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
     for (int g4 = 0; g4 < E / 8; ++g4) dpe_pend[g4] = typename Op16<__bf16>::v4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
 
     for (int t = t0; t < t1; ++t) {
-#ifdef RCB_WAVE_STAMPS
-      const int ts = 10 + 12 * (t - t0);          // stamps of the first tiles of the row
-      RCB_WSTAMP(ts);
-#endif
-#if RCB_WAVE_FAIR == 1
-      // The two waves of a SIMD are arbitrated by priority, then AGE: the wave of the workgroup that was dispatched first runs
-      // nearly unimpeded and finishes its two rows at ~176 us, the other one gets the leftover issue slots and finishes at ~212 us,
-      // the last 36 of them alone on its SIMD (rcb_siren_desc.clock_probe on both halves of the grid, tools/wave_spread.py).
-      // This switch hands the high priority to the two halves of the grid in alternating time slices of the shader clock
-      // (2^RCB_WAVE_FAIR_SHIFT cycles; the clock is read one tile ahead, so its wait is one that happens anyway).  Measured: the
-      // halves then finish at ~200 / ~210 us -- and the kernel still ends at 218-222 us: the pole-and-filler arrangement the
-      // hardware falls into is as productive as equal shares, and the end is set by the slowest XCD (their clocks differ by 5 %
-      // under this kernel: 1.93 ... 2.04 GHz).  Off.
-      if ((((unsigned)(fair_clk >> RCB_WAVE_FAIR_SHIFT)) & 1u) != young) __builtin_amdgcn_s_setprio(1);
-      else __builtin_amdgcn_s_setprio(0);
-      fair_clk = __builtin_amdgcn_s_memtime();
-#endif
+      RCB_STAMPS_ONLY(WAVE, const int ts = 10 + 12 * (t - t0);)          // stamps of the first tiles of the row
+      RCB_STAMP_T0(ts);
       bf16x8 xin[K0S];
       float yv[16];
 #pragma unroll
@@ -494,7 +451,6 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
       // ================= forward ==================================================================================================
       bf16x8 S[2];                           // sines of the layer just finished: the next layer's B operand
       bf16x8 dzb[2];                         // packed gradient of the layer being processed
-#if RCB_WAVE_PIPE_FWD
       // Software-pipelined across the layers: the sines of a layer are evaluated in two halves and each half's packed
       // fragment goes straight into the next layer's k-step, so that k-step 0 runs on the matrix pipe under the second half's
       // sines; the next layer's bias term (an MFMA that depends on nothing) is issued under the first half's.  Order pinned
@@ -522,9 +478,7 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
         }
         put_img(s_img(l), S);
         c = cn;
-#ifdef RCB_WAVE_STAMPS
-        RCB_WSTAMP(ts + 1 + l);
-#endif
+        RCB_STAMP_T0(ts + 1 + l);
       }
       {
         // output layer: loss gradient (or the upstream gradient) on the C rows that exist, packed with literal zeros
@@ -553,76 +507,14 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
             dzb[s][jj] = (rho(r, 0) < C || rho(r, 1) < C) ? (T)dzo[r] : (T)0.0f;
           }
         __builtin_amdgcn_sched_barrier(0);
-#ifdef RCB_WAVE_STAMPS
-        RCB_WSTAMP(ts + 1 + NH);
-#endif
+        RCB_STAMP_T0(ts + 1 + NH);
       }
-#else
-      put_x(xin);
-#pragma unroll
-      for (int l = 0; l < NL; ++l) {
-        f32x16 c;
-        if (l == 0) {
-          c = mfma_i4<T>(BFR[0], ONES, zero16());
-#pragma unroll
-          for (int s = 0; s < K0S; ++s) c = mfma_i4<T>(FR[s], as_i4(xin[s]), c);
-        } else if (l < NH) {
-          c = mfma_i4<T>(BFR[l], ONES, zero16());
-#pragma unroll
-          for (int s = 0; s < 2; ++s) c = mfma_i4<T>(FR[K0S + 2 * (l - 1) + s], as_i4(S[s]), c);
-        } else {
-          c = mfma_i4<T>(LFR(0), as_i4(S[0]), zero16());
-          c = mfma_i4<T>(LFR(1), as_i4(S[1]), c);
-        }
-        if (l < NH) {
-          f32x16 sv;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sv[r] = __builtin_amdgcn_sinf((WS == 1.0f) ? c[r] : c[r] * (1.0f / WS));
-          S[0] = pack8<T>(sv, 0);
-          S[1] = pack8<T>(sv, 1);
-          put_img(s_img(l), S);
-        } else {
-          // output layer: loss gradient (or the upstream gradient) on the C rows that exist, packed with literal zeros
-          f32x16 dzo;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            float v = 0.f;
-            if (rho(r, 0) < C || rho(r, 1) < C) {
-              const bool ok = valid && rho(r, h) < C;
-              if (MODE == MODE_LOSS) {
-                const float y = (WS != 1.0f) ? (c[r] * (1.0f / WS) + bout[r]) : (c[r] + bout[r]);
-                const float diff = ok ? (y - yv[r]) : 0.f;
-                sse_local += diff * diff;
-                v = (2.0f * GS) * a.dy_scale * diff;
-              } else {
-                v = ok ? yv[r] * GS : 0.f;
-              }
-            }
-            dzo[r] = v;
-          }
-#pragma unroll
-          for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int jj = 0; jj < 8; ++jj) {
-              const int r = 8 * s + jj;
-              dzb[s][jj] = (rho(r, 0) < C || rho(r, 1) < C) ? (T)dzo[r] : (T)0.0f;
-            }
-        }
-#if RCB_WAVE_FSB
-        __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifdef RCB_WAVE_STAMPS
-        RCB_WSTAMP(ts + 1 + l);
-#endif
-      }
-
-#endif
 
       // ================= backward ===============================================================================================
       // per layer: dz image written; data-gradient MFMAs; the pre-activation of layer l - 1 recomputed from its input rows (read
       // back from the tile's image) -> cosine x data gradient -> packed dz of the layer below; weight-gradient MFMAs on the
       // transposed reads of the dz image and of the layer's input image, one k-step in front of the vector work and one behind.
-      // (RCB_WAVE_ZPIPE) the recomputed pre-activation is taken one layer ahead: z of sine layer l - 2 is issued at the END of layer l
+      // The recomputed pre-activation is taken one layer ahead: z of sine layer l - 2 is issued at the END of layer l
       // (behind its cosine work, where d and the product are dead) and consumed by layer l - 1 -- its three MFMAs and its row
       // re-reads then sit beside vector work instead of in front of it, and the data-gradient chain d -> cos x d -> pack no
       // longer queues behind them in the matrix pipe
@@ -641,27 +533,12 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
         }
         return zz;
       };
-      f32x16 zc = zero16();
-      if (RCB_WAVE_ZPIPE) zc = compute_z(NL - 2);
+      f32x16 zc = compute_z(NL - 2);
 #pragma unroll
       for (int l = NL - 1; l >= 0; --l) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         put_img(dz_img, dzb);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        bf16x8 rin[cmax(K0S, 2)];
-        if (!RCB_WAVE_ZPIPE && l >= 1) {
-          if (l - 1 == 0) {
-            bf16x8 tx[K0S];
-            get_x(tx);
-#pragma unroll
-            for (int s = 0; s < K0S; ++s) rin[s] = tx[s];
-          } else {
-            bf16x8 ts[2];
-            get_img(s_img(l - 2), ts);
-            rin[0] = ts[0];
-            rin[1] = ts[1];
-          }
-        }
         f32x16 d = zero16();
         if (l == NL - 1) {
           d = mfma_i4<T>(LFR(2), as_i4(dzb[0]), d);
@@ -673,19 +550,7 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
 #pragma unroll
           for (int s = 0; s < 2; ++s) d = mfma_i4<T>(LFR(3 + s), as_i4(dzb[s]), d);
         }
-        f32x16 z;
-        if (RCB_WAVE_ZPIPE) {
-          z = zc;
-        } else if (l > 0) {
-          z = mfma_i4<T>(BFR[l - 1], ONES, zero16());
-          if (l - 1 == 0) {
-#pragma unroll
-            for (int s = 0; s < K0S; ++s) z = mfma_i4<T>(FR[s], as_i4(rin[s]), z);
-          } else {
-#pragma unroll
-            for (int s = 0; s < 2; ++s) z = mfma_i4<T>(FR[K0S + 2 * (l - 2) + s], as_i4(rin[s]), z);
-          }
-        }
+        const f32x16 z = zc;
         // weight gradient, first k-step: dW_l += dz^T x input over pixels 0 .. 15 of the tile; bias gradient from the dz fragment
         {
           const bf16x8 av = read_tr3(dz_img, G::TSA, 0, 0);
@@ -727,13 +592,9 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
           dzb[0] = dzn[0];
           dzb[1] = dzn[1];
         }
-        if (RCB_WAVE_ZPIPE && l >= 2) zc = compute_z(l - 2);
-#if RCB_WAVE_BSB
+        if (l >= 2) zc = compute_z(l - 2);
         __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifdef RCB_WAVE_STAMPS
-        RCB_WSTAMP(ts + 1 + NL + (NL - 1 - l));
-#endif
+        RCB_STAMP_T0(ts + 1 + NL + (NL - 1 - l));
       }
     }
     if (DPE) {
@@ -741,7 +602,7 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
 #pragma unroll
       for (int g4 = 0; g4 < E / 8; ++g4) *reinterpret_cast<typename Op16<__bf16>::v4*>(d16 + 8 * g4 + 4 * h) = dpe_pend[g4];
     }
-    RCB_WSTAMP(2);
+    RCB_STAMP_T0(2);
 
     // ---- the row's gradient, straight from the accumulators --------------------------------------------------------------------
     {
@@ -834,24 +695,14 @@ __global__ void __launch_bounds__(256, 2) siren_wave_kernel(SirenArgs a) {
       if (vec4 && dst != nullptr && d16 != nullptr && dlo == nullptr) emit(std::true_type{});
       else emit(std::false_type{});
     }
-    RCB_WSTAMP(3);
-#ifdef RCB_WAVE_STAMPS
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_wave_stamps[5] = __builtin_amdgcn_s_memrealtime();
-#endif
+    RCB_STAMP_T0(3);
+    RCB_STAMP(WAVE, blockIdx.x == 0 && threadIdx.x == 0, 5, memrealtime);
   }
   if (probing) {                                                                // (one wave of the workgroup: its own rows)
     a.clock_probe[4 * pblk + 2] = __builtin_amdgcn_s_memtime();
     a.clock_probe[4 * pblk + 3] = __builtin_amdgcn_s_memrealtime();
   }
 }
-
-#ifdef RCB_WAVE_STAMPS
-}  // namespace
-extern "C" int rcb_debug_wave_stamps(unsigned long long* dst, int n_entries) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wave_stamps), sizeof(unsigned long long) * n_entries);
-}
-namespace {
-#endif
 
 int launch_wave(void (*kernel)(SirenArgs), size_t lds_bytes, const SirenArgs& a, hipStream_t st, int n_cu) {
   const long long units = (long long)a.G * a.chunks;

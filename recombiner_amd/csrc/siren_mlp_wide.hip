@@ -13,38 +13,15 @@
 // wave contracts its tiles over the images of all four pixel tiles of a pass: complete sums, fixed order, no atomics.
 #include <type_traits>
 
+#include "kernel_stamps.h"
 #include "siren_op16.h"
 
 using namespace rcb;
 
-// Diagnostic build only (-DRCB_SIREN_STAMPS, tools/siren_stamps.py wide): see siren_mlp_bf16.hip
-#ifdef RCB_SIREN_STAMPS
-__device__ unsigned long long g_wide_stamps[8192 * 16];
-#define RCB_WSTAMP(k)                                                                                      \
-  do {                                                                                                    \
-    if (threadIdx.x == 0 && blockIdx.x < 8192) g_wide_stamps[blockIdx.x * 16 + (k)] = __builtin_amdgcn_s_memtime(); \
-  } while (0)
-extern "C" int rcb_debug_read_stamps_wide(unsigned long long* dst, int n_entries) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wide_stamps), sizeof(unsigned long long) * n_entries);
-}
-// barriers of the pass loop with the time wave 0 spends in them summed (stamp slot 5) and the passes' forward time (slot 4)
-#define RCB_WBARRIER()                                                        \
-  do {                                                                        \
-    const unsigned long long tb_ = __builtin_amdgcn_s_memtime();              \
-    __syncthreads();                                                          \
-    bar_acc += __builtin_amdgcn_s_memtime() - tb_;                            \
-  } while (0)
-#define RCB_WACC_DECL unsigned long long bar_acc = 0
-#define RCB_WACC_STORE()                                                      \
-  do {                                                                        \
-    if (threadIdx.x == 0 && blockIdx.x < 8192) g_wide_stamps[blockIdx.x * 16 + 5] = bar_acc; \
-  } while (0)
-#else
-#define RCB_WSTAMP(k) do { } while (0)
-#define RCB_WBARRIER() __syncthreads()
-#define RCB_WACC_DECL
-#define RCB_WACC_STORE() do { } while (0)
-#endif
+// Diagnostic build only (-DRCB_STAMPS_WIDE=1, tools/siren_stamps.py wide): see siren_mlp_bf16.hip.  Slot 5: the time thread 0
+// spends in the barriers of the pass loop, summed.
+RCB_STAMPS_BUFFER(WIDE, 8192 * 16)
+#define RCB_STAMP_WG(also, k) RCB_STAMP(WIDE, (also) && threadIdx.x == 0 && blockIdx.x < 8192, blockIdx.x * 16 + (k), memtime)
 
 namespace {
 using namespace rcb::op16;
@@ -155,7 +132,7 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
   T* bufB = bufA + 32 * G::TSA;
 
   // ---- stage the weights (in one or two parts through the image area), build the MFMA A-fragments --------------------
-  RCB_WSTAMP(0);
+  RCB_STAMP_WG(true, 0);
   {
     const float* src = a.wvec + (long long)g * a.w_stride;
     float* wst = reinterpret_cast<float*>(smem_raw + G::TILE_OFF);
@@ -276,7 +253,7 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
       part(LSc{}, LNc{}, stage_b, [] {});
     }
   }
-  RCB_WSTAMP(2);
+  RCB_STAMP_WG(true, 2);
 
   // this wave's weight-gradient tiles.  Two row blocks (width 48 / 64): hidden layer l (1 .. NH-1): tile (wave >> 1, wave & 1);
   // layer 0: the same with two input blocks, (wave, 0) on waves 0 / 1 with one; output layer: (0, wave - 2) on waves 2 / 3.
@@ -436,7 +413,7 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
   int lane_v = lane0;
   // one pass = four pixel tiles, one per wave.  FULL: every wave has a tile (all passes but possibly the chunk's last): no
   // wave-level conditionals in the hot loop
-  RCB_WACC_DECL;
+  RCB_STAMPS_ONLY(WIDE, unsigned long long bar_acc = 0;)
   auto pass = [&](int tb, auto full_c) {
     constexpr bool FULL = decltype(full_c)::value;
     // the remaining lane-dependent addresses (global rows, layer-0 image stores) are re-derived in every pass: hoisted out
@@ -459,8 +436,8 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
     const int p = t * 32 + q;
     const bool valid = active && p < P;
     const int pc = p < P ? p : P - 1;
-    if (tb == t0) RCB_WSTAMP(14);
-    if (tb == t0 + 4) RCB_WSTAMP(15);
+    if (tb == t0) RCB_STAMP_WG(true, 14);
+    if (tb == t0 + 4) RCB_STAMP_WG(true, 15);
     bf16x8 xin[K0S];
     bf16x8 S[NH][KSH], Cs[NH][KSH];
     bf16x8 dzb[2 * HB];
@@ -578,7 +555,7 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
         }
       } else {
         // ---- output gradient ----------------------------------------------------------------------------------------
-        if (tb == t0) RCB_WSTAMP(8);
+        if (tb == t0) RCB_STAMP_WG(true, 8);
         f32x16 dz;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -605,7 +582,7 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
 #pragma unroll
     for (int l = NL - 1; l >= 0; --l) {
       const int KSO = (l == NL - 1) ? 2 : KSH;            // k-steps over this layer's output features
-      if (tb == t0) RCB_WSTAMP(9 + (NL - 1 - l));
+      if (tb == t0) RCB_STAMP_WG(true, 9 + (NL - 1 - l));
       if (!FULL && !active && l == NL - 1) {
         // a wave without a pixel tile in the chunk's last pass: zero images, so that the owners contract four tiles always
         uint4* z = reinterpret_cast<uint4*>(bufA);
@@ -668,7 +645,7 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
       // (with 16-bit inputs and one input block the register budget allows it; the other instances read after the barrier)
       constexpr bool FB_EARLY = FB_EARLY_C;
       if (FB_EARLY && active) load_fb();
-      RCB_WBARRIER();
+      RCB_STAMPS_BARRIER(WIDE, bar_acc);
       // (1) data gradient of this wave's pixel tile
       if (active) {
         if (!FB_EARLY) load_fb();
@@ -798,7 +775,7 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
           }
         }
       }
-      RCB_WBARRIER();
+      RCB_STAMPS_BARRIER(WIDE, bar_acc);
     }
     if (t + 4 < t1) convert_inputs();
   };
@@ -806,8 +783,8 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
   for (; tb + 4 <= t1; tb += 4) pass(tb, std::true_type{});
   if (tb < t1) pass(tb, std::false_type{});
   if (MODE == MODE_FWD) return;
-  RCB_WSTAMP(3);
-  RCB_WACC_STORE();
+  RCB_STAMP_WG(true, 3);
+  RCB_STAMPS_ONLY(WIDE, if (threadIdx.x == 0 && blockIdx.x < 8192) g_stamps_WIDE[blockIdx.x * 16 + 5] = bar_acc;)
 
   // ---- every gradient tile is complete in its owner's registers: transpose through the wave's own image area and store --
   const int lane = lane0, q = lane & 31, h = lane >> 5;
@@ -902,8 +879,8 @@ __global__ void __launch_bounds__(256, (GeoW<NH, F, E, C, W>::WG_PER_CU)) siren_
       if constexpr (NL > 3) { if (wave == 3) store_tile(std::integral_constant<int, (NL > 3 ? 3 : 0)>{}, 0, 0, gT[0], bsumT, true); }
     }
   }
-  RCB_WSTAMP(6);
-  RCB_WSTAMP(7);
+  RCB_STAMP_WG(true, 6);
+  RCB_STAMP_WG(true, 7);
 }
 
 // the four instances of one geometry and operand type (siren_launch_mode)

@@ -14,9 +14,20 @@
 //   wgrad   : D[ci, co]  += A[ci, pos] * B[pos, co]                per-INR images staged in LDS, transposed reads
 // LeakyReLU(0.01) is fused: forward applies it on load (fp32 pre-activation input) or in the epilogue;
 // dgrad multiplies by its derivative taken from the sign of the stored activation.
+#include "kernel_stamps.h"
 #include "rcb_common.h"
 
 using namespace rcb;
+
+// Diagnostic builds (-DRCB_STAMPS_<SET>=1, each on its own; the library has none of them), workgroup 0 of the last launch:
+//   WC  s_memrealtime at kernel entry / loop start / loop end / kernel end of [0] upconv_wgrad_kernel, [1] upconv_fwd3_lds_kernel
+//   F2, D2, B3  per wave, s_memtime ticks per phase summed over the loop (tools/f2_stamps.py, d2_stamps.py, b3_stamps.py name the
+//       phases) and the 100 MHz wall clock of the prologue and the loop in the slots no phase uses
+RCB_STAMPS_BUFFER(WC, 2 * 4)
+RCB_STAMPS_BUFFER(F2, 8 * 8)
+RCB_STAMPS_BUFFER(D2, 8 * 8)
+RCB_STAMPS_BUFFER(B3, 8 * 8)
+#define WC_T(which, k) RCB_STAMP(WC, blockIdx.x == 0 && threadIdx.x == 0, (which) * 4 + (k), memrealtime)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -26,18 +37,6 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 constexpr int CIN = 64;
-#ifndef RCB_UP_HOT
-#define RCB_UP_HOT 0       // ablation builds (wrong results): the stage-2 forward / data gradient read one cache-resident INR
-#endif
-#ifndef RCB_UP_NOSTORE
-#define RCB_UP_NOSTORE 0   // ablation builds (wrong results): 1 stage-2 forward, 2 stage-2 data gradient, 3 stage-3 forward without their stores
-#endif
-#ifndef RCB_B3_PF
-#define RCB_B3_PF 2          // taps whose LDS reads are in flight ahead of their MFMAs in the stage-3 backward's data gradient
-#endif
-#ifndef RCB_UP_PF
-#define RCB_UP_PF 3          // image gathers in flight ahead of their MFMAs in the register-fragment kernels
-#endif
 constexpr int XRS = 72;   // row stride (elements) of a staged 64-channel image: 144-byte rows spread 128-byte-strided
                           // gathers (consecutive positions, one channel chunk) over all LDS banks
 constexpr float SLOPE = 0.01f;
@@ -60,19 +59,6 @@ union Frag {
 // the value must exist in registers here: stops the compiler from sinking a prologue's conversions into the main loop
 // (where their operands would stay live, and spill, across it)
 __device__ __forceinline__ void pin(uint4& u) { asm volatile("" : "+v"(u.x), "+v"(u.y), "+v"(u.z), "+v"(u.w)); }
-
-#ifndef RCB_WC_STAMPS
-#define RCB_WC_STAMPS 0    // diagnostic build: s_memrealtime (100 MHz) of workgroup 0 at kernel entry / loop start / loop end / kernel end
-#endif
-#if RCB_WC_STAMPS
-__device__ unsigned long long g_wc_stamps[2][4];      // [0]: upconv_wgrad_kernel, [1]: upconv_fwd3_lds_kernel (last launch of each)
-#define WC_T(which, k)                                                                            \
-  do {                                                                                            \
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_wc_stamps[which][k] = __builtin_amdgcn_s_memrealtime(); \
-  } while (0)
-#else
-#define WC_T(which, k) do { } while (0)
-#endif
 
 // raw (unconverted) 8-channel loads: the next INR's image is requested into registers while the current one is
 // consumed, and converted (mode 1/3: with LeakyReLU) only when it is committed to LDS
@@ -179,7 +165,7 @@ __device__ __forceinline__ void fwd3_body(const __bf16* img, const uint4 (&fr)[2
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[ph][pb][r] = 0.f;
     const __bf16* base = img + ((i0 + pa) * HG + j) * RS;
-    constexpr int NG = 24, PF = RCB_UP_PF;
+    constexpr int NG = 24, PF = 3;      // PF: image gathers in flight ahead of their MFMAs
     uint4 ring[PF + 1];
     auto gather = [&](int g) {                    // g = ((ty * 3 + dxi) * 2 + kb2) * 2 + ph
       const int ph = g & 1, kb2 = (g >> 1) & 1, td = g >> 2, ty = td / 3, dxi = td - 3 * ty;
@@ -225,8 +211,7 @@ __device__ __forceinline__ void fwd3_body(const __bf16* img, const uint4 (&fr)[2
           o.v[k] = (__bf16)lo[k];
           o.v[4 + k] = (__bf16)hi[k];
         }
-        if (RCB_UP_NOSTORE != 3 || a.batch < 0)
-          *reinterpret_cast<uint4*>(reinterpret_cast<__bf16*>(a.y) + opix * COUT + 8 * (kg >> 1)) = o.u;
+        *reinterpret_cast<uint4*>(reinterpret_cast<__bf16*>(a.y) + opix * COUT + 8 * (kg >> 1)) = o.u;
       } else {
         float4* dst = reinterpret_cast<float4*>(reinterpret_cast<float*>(a.y) + opix * COUT + 8 * (kg >> 1));
         dst[0] = make_float4(lo[0], lo[1], lo[2], lo[3]);
@@ -451,26 +436,10 @@ __global__ void __launch_bounds__(512) upconv_dgrad3_lds_kernel(DgradArgs a) {
 // halves of the 64 output channels: 32 fragments in registers, 16 image reads feed 32 MFMAs per tile.  Two INRs per
 // pass halve the barriers per INR; LeakyReLU of the pre-activation input is applied once, when the image is staged.
 // ------------------------------------------------------------------------------------------------
-#ifndef RCB_F2_STAMPS
-#define RCB_F2_STAMPS 0    // diagnostic build: ticks per phase of workgroup 0's waves (rcb_debug_f2_stamps, tools/f2_stamps.py)
-#endif
-#if RCB_F2_STAMPS
-__device__ unsigned long long g_f2_stamps[8 * 8];
-#define F2_T(k)                                                     \
-  do {                                                              \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
-    ph_[k] += now_ - last_;                                         \
-    last_ = now_;                                                   \
-  } while (0)
-#else
-#define F2_T(k) do { } while (0)
-#endif
 template <int IN_MODE>   // 1: fp32 pre-activation, 3: bf16 pre-activation
 __global__ void __launch_bounds__(512) upconv_fwd2_reg_kernel(FwdArgs a) {
   constexpr int G = 8, HG = 10, RS = 72, COUT = 64, IMG = HG * HG * RS;
-#if RCB_F2_STAMPS
-  const unsigned long long t_entry_ = __builtin_amdgcn_s_memrealtime();
-#endif
+  RCB_STAMPS_ONLY(F2, const unsigned long long t_entry_ = __builtin_amdgcn_s_memrealtime();)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int NI = 4;                                               // INRs per pass
   __bf16* img = reinterpret_cast<__bf16*>(smem_raw);                  // [NI][IMG]
@@ -515,18 +484,16 @@ __global__ void __launch_bounds__(512) upconv_fwd2_reg_kernel(FwdArgs a) {
     const int e_ = tid + 512 * k;                                                          \
     int b_ = NI * (pp) + (e_ >> 9);                                                        \
     if (b_ >= a.batch) b_ = a.batch - 1;                                                   \
-    pre[k] = raw_load<IN_MODE>(a.x, (long long)(RCB_UP_HOT ? (int)(blockIdx.x & 1023) : b_) * G * G * CIN + 8 * (e_ & 511));         \
+    pre[k] = raw_load<IN_MODE>(a.x, (long long)b_ * G * G * CIN + 8 * (e_ & 511)); \
   }
   const int gs = gridDim.x;
   int p = blockIdx.x;
   if (p < npair) RCB_FETCH2(p)
-#if RCB_F2_STAMPS
-  unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memtime();
-  ph_[5] = __builtin_amdgcn_s_memrealtime();      // 100 MHz wall clock: loop start / end in slots 5, 6, kernel entry in 7
-#endif
+  RCB_STAMPS_PHASES(F2);
+  RCB_STAMPS_ONLY(F2, ph_[5] = __builtin_amdgcn_s_memrealtime();)      // 100 MHz wall clock: loop start / end in slots 5, 6, kernel entry in 7
   for (; p < npair; p += gs) {
     __syncthreads();
-    F2_T(0);
+    RCB_STAMPS_PHASE(F2, 0);
 #pragma unroll
     for (int k = 0; k < NI; ++k) {
       const int e_ = tid + 512 * k, pix = (e_ >> 3) & 63, c8 = e_ & 7;
@@ -534,9 +501,9 @@ __global__ void __launch_bounds__(512) upconv_fwd2_reg_kernel(FwdArgs a) {
       f.v = raw_frag<IN_MODE>(pre[k], true);
       *reinterpret_cast<uint4*>(img + (e_ >> 9) * IMG + (((pix >> 3) + 1) * HG + ((pix & 7) + 1)) * RS + 8 * c8) = f.u;
     }
-    F2_T(1);
+    RCB_STAMPS_PHASE(F2, 1);
     __syncthreads();
-    F2_T(2);
+    RCB_STAMPS_PHASE(F2, 2);
     if (p + gs < npair) RCB_FETCH2(p + gs)
 #pragma unroll 1
     for (int it = 0; it < 4; ++it) {         // (INR of this wave, tile) pairs, one after the other
@@ -566,7 +533,7 @@ __global__ void __launch_bounds__(512) upconv_fwd2_reg_kernel(FwdArgs a) {
               }
             }
         __builtin_amdgcn_sched_barrier(0);
-        F2_T(3);
+        RCB_STAMPS_PHASE(F2, 3);
         // bias + LeakyReLU on the original channels, then the lane halves swap so that lane (q, h) owns the 16
         // consecutive channels 32 mt + 16 h .. + 15 of its pixel
         const long long opix = ((long long)b * (2 * G) + 2 * i + pa) * (2 * G) + 2 * j + pb;
@@ -595,22 +562,16 @@ __global__ void __launch_bounds__(512) upconv_fwd2_reg_kernel(FwdArgs a) {
             o1.v[k] = (__bf16)xa[4 + k]; o1.v[4 + k] = (__bf16)ya[4 + k];
           }
           uint4* dst = reinterpret_cast<uint4*>(reinterpret_cast<__bf16*>(a.y) + opix * COUT + 32 * mt + 16 * h);
-          if (RCB_UP_NOSTORE != 1 || a.batch < 0) {
-            dst[0] = o0.u;
-            dst[1] = o1.u;
-          }
+          dst[0] = o0.u;
+          dst[1] = o1.u;
         }
         __builtin_amdgcn_sched_barrier(0);
-        F2_T(4);
+        RCB_STAMPS_PHASE(F2, 4);
       }
     }
   }
-#if RCB_F2_STAMPS
-  ph_[6] = __builtin_amdgcn_s_memrealtime();
-  ph_[7] = t_entry_;
-  if (blockIdx.x == 0 && lane == 0)
-    for (int k = 0; k < 8; ++k) g_f2_stamps[wave * 8 + k] = ph_[k];
-#endif
+  RCB_STAMPS_ONLY(F2, ph_[6] = __builtin_amdgcn_s_memrealtime(); ph_[7] = t_entry_;)
+  RCB_STAMPS_PHASES_STORE(F2, blockIdx.x == 0 && lane == 0, wave * 8);
 #undef RCB_FETCH2
 }
 
@@ -817,29 +778,13 @@ __global__ void __launch_bounds__(512) upconv_fwd23_kernel(Fwd23Args a) {
 // not fit one wave, so wave w = (ci half w & 1, tile (w >> 1) & 1, combo half w >> 2) keeps 32 of them and the two
 // combo halves are added through LDS.  The epilogue (combo-half 0 waves) multiplies by LeakyReLU'(x), swaps lane halves
 // for 32-byte stores and accumulates the per-channel sums of dx (the bias gradient of the stage before) per workgroup.
-#ifndef RCB_D2_STAMPS
-#define RCB_D2_STAMPS 0    // diagnostic build: cycles per phase of workgroup 0's waves (rcb_debug_d2_stamps, tools/d2_stamps.py)
-#endif
-#if RCB_D2_STAMPS
-__device__ unsigned long long g_d2_stamps[8 * 8];
-#define D2_T(k)                                                     \
-  do {                                                              \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
-    ph_[k] += now_ - last_;                                         \
-    last_ = now_;                                                   \
-  } while (0)
-#else
-#define D2_T(k) do { } while (0)
-#endif
 template <int X_F32>   // sign source / dx type: 1 fp32, 0 bf16
 __global__ void __launch_bounds__(512) upconv_dgrad2_reg_kernel(DgradArgs a, float* __restrict__ dbias_partial) {
   // dy image [18][18][64] in LDS: 128-byte pixels, rows padded by 64 B, and the 16-byte chunk c of pixel column x stored at
   // c ^ ((x >> 1) & 7): every gather below (lane = output position, pixels two apart, one chunk per instruction) then covers
   // all 64 banks once per ds_read_b128 lane group (tools/lds_banks.py; the plain padded image cost 4 cycles per group)
   constexpr int G = 8, OG = 16, HO = 18, RS = 64, ROWS = HO * RS + 32, COUT = 64, IMG = HO * ROWS;
-#if RCB_D2_STAMPS
-  const unsigned long long t_entry_ = __builtin_amdgcn_s_memrealtime();
-#endif
+  RCB_STAMPS_ONLY(D2, const unsigned long long t_entry_ = __builtin_amdgcn_s_memrealtime();)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   // Two image buffers and two exchange buffers (118 KB): INR n + 1 is staged into the other image while INR n is contracted,
   // and ONE barrier per INR remains -- between the exchange write of the kh = 1 waves and its read by the kh = 0 waves, which
@@ -888,7 +833,7 @@ __global__ void __launch_bounds__(512) upconv_dgrad2_reg_kernel(DgradArgs a, flo
   for (int k = 0; k < 4; ++k) pre[k] = make_uint4(0, 0, 0, 0);
 #define RCB_FETCHD2(bb)                                                                                           \
   {                                                                                                               \
-    const uint4* src_ = reinterpret_cast<const uint4*>(reinterpret_cast<const __bf16*>(a.dy) + (long long)(RCB_UP_HOT ? (int)blockIdx.x : (bb)) * OG * OG * COUT); \
+    const uint4* src_ = reinterpret_cast<const uint4*>(reinterpret_cast<const __bf16*>(a.dy) + (long long)(bb) * OG * OG * COUT); \
     _Pragma("unroll") for (int k = 0; k < 4; ++k) pre[k] = src_[tid + 512 * k];                                   \
   }
   const int gs = gridDim.x;
@@ -896,10 +841,8 @@ __global__ void __launch_bounds__(512) upconv_dgrad2_reg_kernel(DgradArgs a, flo
   __syncthreads();   // also a scheduling boundary: the prefetch registers must not overlap the prologue's register peak
   if (b < a.batch) RCB_FETCHD2(b)
   const int pos = tile * 32 + q, u = pos >> 3, v = pos & 7;
-#if RCB_D2_STAMPS
-  unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memtime();
-  const unsigned long long t_loop_ = __builtin_amdgcn_s_memrealtime();
-#endif
+  RCB_STAMPS_PHASES(D2);
+  RCB_STAMPS_ONLY(D2, const unsigned long long t_loop_ = __builtin_amdgcn_s_memrealtime();)
 #define RCB_STAGED2(dst)                                                                                                   \
   _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                                          \
     const int e_ = tid + 512 * k, pix = e_ >> 3, c8 = e_ & 7, xx = (pix & 15) + 1;                                          \
@@ -913,7 +856,7 @@ __global__ void __launch_bounds__(512) upconv_dgrad2_reg_kernel(DgradArgs a, flo
   int cur = 0;
   for (; b < a.batch; b += gs, cur ^= 1) {
     const __bf16* im = img + cur * (IMGB / 2);
-    D2_T(0);
+    RCB_STAMPS_PHASE(D2, 0);
     // INR n + 1 into the other buffer (every wave is past the barrier of INR n - 1, i.e. past its reads of that buffer), then
     // the rows of INR n + 2 are requested: in flight during the MFMA loop
     if (b + gs < a.batch) {
@@ -921,7 +864,7 @@ __global__ void __launch_bounds__(512) upconv_dgrad2_reg_kernel(DgradArgs a, flo
       RCB_STAGED2(nx)
       if (b + 2 * gs < a.batch) RCB_FETCHD2(b + 2 * gs)
     }
-    D2_T(1);
+    RCB_STAMPS_PHASE(D2, 1);
     // sign source of this lane's 16 output channels, requested before the MFMA loop
     const long long xoff = ((long long)b * G * G + pos) * CIN + 32 * mt + 16 * h;
     float xf[16];     // fp32 sign source
@@ -960,16 +903,16 @@ __global__ void __launch_bounds__(512) upconv_dgrad2_reg_kernel(DgradArgs a, flo
       }
       __builtin_amdgcn_sched_barrier(0);     // one combo at a time (the other wave of the SIMD covers the LDS latency)
     }
-    D2_T(3);
+    RCB_STAMPS_PHASE(D2, 3);
     // add the two combo halves (register-major layout: conflict-free)
     float* rw = red + (cur * 4 + (wave & 3)) * 16 * 64;
     if (kh == 1) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) rw[r * 64 + lane] = acc[r];
     }
-    D2_T(4);
+    RCB_STAMPS_PHASE(D2, 4);
     __syncthreads();
-    D2_T(5);
+    RCB_STAMPS_PHASE(D2, 5);
     if (kh == 0) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] += rw[r * 64 + lane];
@@ -1001,18 +944,15 @@ __global__ void __launch_bounds__(512) upconv_dgrad2_reg_kernel(DgradArgs a, flo
             oo.v[k] = (__bf16)(o[k] * ((float)xb[hf].v[k] > 0.f ? 1.0f : SLOPE));
             dbsum[8 * hf + k] += (float)oo.v[k];     // sums of the values as stored
           }
-          if (RCB_UP_NOSTORE != 2 || a.batch < 0) reinterpret_cast<uint4*>(reinterpret_cast<__bf16*>(a.dx) + xoff)[hf] = oo.u;
+          reinterpret_cast<uint4*>(reinterpret_cast<__bf16*>(a.dx) + xoff)[hf] = oo.u;
         }
       }
     }
-    D2_T(6);
+    RCB_STAMPS_PHASE(D2, 6);
   }
-#if RCB_D2_STAMPS
-  ph_[7] = __builtin_amdgcn_s_memrealtime() - t_loop_;      // wall clock (100 MHz) of the INR loop; slot 2 (unused): the prologue
-  ph_[2] = t_loop_ - t_entry_;
-  if (blockIdx.x == 0 && lane == 0)
-    for (int k = 0; k < 8; ++k) g_d2_stamps[wave * 8 + k] = ph_[k];
-#endif
+  // wall clock (100 MHz) of the INR loop; slot 2 (unused): the prologue
+  RCB_STAMPS_ONLY(D2, ph_[7] = __builtin_amdgcn_s_memrealtime() - t_loop_; ph_[2] = t_loop_ - t_entry_;)
+  RCB_STAMPS_PHASES_STORE(D2, blockIdx.x == 0 && lane == 0, wave * 8);
 #undef RCB_FETCHD2
 #undef RCB_STAGED2
   if (dbias_partial) {   // fixed-order reduction over the 32 pixels of a lane half, then over the two tiles
@@ -1210,29 +1150,7 @@ __global__ void __launch_bounds__(512) upconv_wgrad_kernel(WgradArgs a) {
 //                    (row stride 24 elements instead of 16) and the x operand from the staged zero-halo x image
 // bf16 dy / x / dx, COUT = 16.  Sums go to per-workgroup slabs (upconv_wgrad_reduce_kernel finishes them).
 // ------------------------------------------------------------------------------------------------
-// Diagnostic build only (-DRCB_B3_STAMPS=1, tools/b3_stamps.py): cycles each wave of workgroup 0 spends per phase, summed
-// over its INRs: 0 first barrier, 1 staging, 2 second barrier, 3 data gradient (incl. prefetch issue), 4 weight gradient
-#ifndef RCB_B3_STAMPS
-#define RCB_B3_STAMPS 0
-#endif
-#ifndef RCB_B3_WG16
-#define RCB_B3_WG16 1        // weight-gradient part on v_mfma_f32_16x16x32_bf16 (0: the 32 x 32 x 16 form of the separate kernel)
-#endif
-#ifndef RCB_B3_DIAG
-#define RCB_B3_DIAG 0      // ablations (wrong results): 1 no dx stores, 2 one fragment read per tap pair, 3 one dy read for all taps,
-                           // 4 dx stores land in the workgroup's first INR (L2-resident target)
-#endif
-#if RCB_B3_STAMPS
-__device__ unsigned long long g_b3_stamps[8 * 8];
-#define B3_T(k)                                                     \
-  do {                                                              \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();   \
-    ph_[k] += now_ - last_;                                         \
-    last_ = now_;                                                   \
-  } while (0)
-#else
-#define B3_T(k) do { } while (0)
-#endif
+// (B3 stamps, tools/b3_stamps.py: 0 first barrier, 1 staging, 2 second barrier, 3 data gradient (incl. prefetch issue), 4 weight gradient)
 
 struct Bwd3Args {
   const void* dy;
@@ -1246,11 +1164,8 @@ struct Bwd3Args {
 
 __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
   constexpr int COUT = 16, G = 16, OG = 32, HO = 34, RS = 24, HG = 18, NF = 32;
-#if RCB_B3_STAMPS
-  const unsigned long long t_entry_ = __builtin_amdgcn_s_memrealtime();
-#endif
+  RCB_STAMPS_ONLY(B3, const unsigned long long t_entry_ = __builtin_amdgcn_s_memrealtime();)
   constexpr int WSZ = 1024 * COUT, ROW = WSZ + COUT;
-#if RCB_B3_WG16
   // x image of THIS kernel: 128-byte pixel rows, the 32-byte block cb of 16 channels stored at block cb ^ xkey(column) with
   // xkey = column bit 1 | column bit 3 << 1.  The transposed reads of the weight gradient take, per 32 lanes, four adjacent
   // columns and the four columns eight further on: with this key (and the bank half that the column parity selects) their 32
@@ -1259,10 +1174,6 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
   // cycles per read; staging stores 8 -> 6, the data gradient's eight sign reads per INR 4 -> 8)
   constexpr int XR3 = 64;
 #define B3_XKEY(col) ((((col) >> 1) & 1) | ((((col) >> 3) & 1) << 1))
-#else
-  constexpr int XR3 = XRS;
-#define B3_XKEY(col) 0
-#endif
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   uint4* frags = reinterpret_cast<uint4*>(smem_raw);                              // [16 combos][2 mt][64 lanes]
   __bf16* dyimg = reinterpret_cast<__bf16*>(smem_raw + NF * 1024);                // [34][34][24]
@@ -1291,7 +1202,6 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
     frags[e] = f.u;
   }
   for (int e = tid; e < (HO * HO * RS + HG * HG * XR3) / 8; e += 512) reinterpret_cast<uint4*>(dyimg)[e] = make_uint4(0, 0, 0, 0);
-#if RCB_B3_WG16
   // weight gradient on v_mfma_f32_16x16x32_bf16: [combo slot][16-channel block of cin] tiles of 16 cin x 16 cout (the 32 x 32 x 16
   // form has 32 columns for the 16 output channels: half of every MFMA, and this phase ran at 90 % of the matrix pipe)
   f32x4v wacc[2][4];
@@ -1301,15 +1211,6 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
       for (int r = 0; r < 4; ++r) wacc[c][cb][r] = 0.f;
-#else
-  f32x16 wacc[2][2];   // weight gradient: [combo slot][mt]
-#pragma unroll
-  for (int c = 0; c < 2; ++c)
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) wacc[c][mt][r] = 0.f;
-#endif
   float dbsum[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) dbsum[j] = 0.f;
@@ -1328,13 +1229,11 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
   __syncthreads();
   if (b < a.batch) RCB_FETCH_B3(b)
   const int u = (wave * 32 + q) >> 4, v = (wave * 32 + q) & 15;      // data gradient: this lane's output position
-#if RCB_B3_STAMPS
-  unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memtime();
-  ph_[5] = __builtin_amdgcn_s_memrealtime();      // 100 MHz wall clock at the loop's start / end: slots 5, 6
-#endif
+  RCB_STAMPS_PHASES(B3);
+  RCB_STAMPS_ONLY(B3, ph_[5] = __builtin_amdgcn_s_memrealtime();)      // 100 MHz wall clock at the loop's start / end: slots 5, 6
   for (; b < a.batch; b += gs) {
     __syncthreads();
-    B3_T(0);
+    RCB_STAMPS_PHASE(B3, 0);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int e = tid + 512 * k;
@@ -1351,9 +1250,9 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
         *reinterpret_cast<uint4*>(ximg + (((pix >> 4) + 1) * HG + ((pix & 15) + 1)) * XR3 + 16 * ((c8 >> 1) ^ B3_XKEY((pix & 15) + 1)) + 8 * (c8 & 1)) = px[k];
       }
     }
-    B3_T(1);
+    RCB_STAMPS_PHASE(B3, 1);
     __syncthreads();
-    B3_T(2);
+    RCB_STAMPS_PHASE(B3, 2);
     if (b + gs < a.batch) RCB_FETCH_B3(b + gs)
     // ---- data gradient --------------------------------------------------------------------------------------
     {
@@ -1366,13 +1265,13 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
       // the MFMAs of tap n (register ring, order pinned by scheduling barriers): the compiler's own schedule re-used one
       // register set and waited for every read in front of its MFMA, and this phase -- a third of the kernel's matrix work --
       // took 45 % of its time
-      constexpr int B3_PF = RCB_B3_PF;
+      constexpr int B3_PF = 2;      // taps whose LDS reads are in flight ahead of their MFMAs
       uint4 rg[B3_PF + 1][3];
       auto tap_reads = [&](int n, uint4 (&dst)[3]) {
         const int ry = (n >> 2) - 1, rx = (n & 3) - 1;
-        dst[0] = *reinterpret_cast<const uint4*>(dyimg + ((2 * u + ((RCB_B3_DIAG == 3) ? 0 : ry) + 1) * HO + (2 * v + ((RCB_B3_DIAG == 3) ? 0 : rx) + 1)) * RS + 8 * h);
-        dst[1] = frags[((RCB_B3_DIAG == 2 ? 0 : n) * 2 + 0) * 64 + lane];
-        dst[2] = frags[((RCB_B3_DIAG == 2 ? 0 : n) * 2 + 1) * 64 + lane];
+        dst[0] = *reinterpret_cast<const uint4*>(dyimg + ((2 * u + ry + 1) * HO + (2 * v + rx + 1)) * RS + 8 * h);
+        dst[1] = frags[(n * 2 + 0) * 64 + lane];
+        dst[2] = frags[(n * 2 + 1) * 64 + lane];
       };
 #pragma unroll
       for (int n = 0; n < B3_PF; ++n) tap_reads(n, rg[n]);
@@ -1396,7 +1295,7 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
       const __bf16* xs = ximg + ((u + 1) * HG + (v + 1)) * XR3;
       const int xk16 = 16 * B3_XKEY(v + 1);
       __bf16* scr = dxscr + wave * (32 * SCR_RS);
-      __bf16* dxw = reinterpret_cast<__bf16*>(a.dx) + ((long long)(RCB_B3_DIAG == 4 ? (int)blockIdx.x : b) * G * G + wave * 32) * CIN;
+      __bf16* dxw = reinterpret_cast<__bf16*>(a.dx) + ((long long)b * G * G + wave * 32) * CIN;
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
 #pragma unroll
@@ -1413,7 +1312,7 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
         for (int ps = 0; ps < 2; ++ps) {
           const int pl = 16 * ps + (lane >> 2), ch = lane & 3;
           const uint4 o = *reinterpret_cast<const uint4*>(scr + pl * SCR_RS + 8 * ch);
-          if (RCB_B3_DIAG != 1 || a.batch < 0) *reinterpret_cast<uint4*>(dxw + pl * CIN + 32 * mt + 8 * ch) = o;
+          *reinterpret_cast<uint4*>(dxw + pl * CIN + 32 * mt + 8 * ch) = o;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       }
@@ -1422,8 +1321,7 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
     // 16 combos (phase p, tap t) over 8 waves: wave w takes t = 2 (w & 1) + c, c = 0 / 1, of phase p = w >> 1.  The dy operand
     // depends on the phase only: one transposed read feeds both combos (10 reads per 4 MFMAs instead of 12)
     __builtin_amdgcn_sched_barrier(0);
-    B3_T(3);
-#if RCB_B3_WG16
+    RCB_STAMPS_PHASE(B3, 3);
     {
       // per 32 positions (two rows of the 16 x 16 grid) and combo: four MFMAs of K = 32, one per 16-channel block of cin; a lane
       // group g = lane >> 4 supplies positions 8 g .. 8 g + 7 of both operands (two transposed 8-byte reads each)
@@ -1471,41 +1369,10 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
         }
       }
     }
-#else
-    {
-      const int p = wave >> 1, pa = p >> 1, pb = p & 1, ty = wave & 1;
-#pragma unroll 2
-      for (int pt = 0; pt < G * G / 32; ++pt) {       // partly unrolled: the prefetch registers must stay in registers
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          union { s16x4 s[2]; bf16x8 v; } av[2][2], bv;
-#pragma unroll
-          for (int w2 = 0; w2 < 2; ++w2) {
-            const int pos = 32 * pt + 16 * ks + 8 * h + 4 * w2 + q4;
-            const int i = pos >> 4, j = pos & 15;
-            const __bf16* xr = ximg + ((i + pa + ty) * HG + (j + pb)) * XRS + 16 * fb + 4 * p4;
-#pragma unroll
-            for (int c = 0; c < 2; ++c)               // tx = c: the neighbouring column
-#pragma unroll
-              for (int mt = 0; mt < 2; ++mt) av[c][mt].s[w2] = tr_read(xr + c * XRS + 32 * mt);
-            bv.s[w2] = tr_read(dyimg + ((2 * i + pa + 1) * HO + (2 * j + pb + 1)) * RS + 4 * p4);
-          }
-#pragma unroll
-          for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) wacc[c][mt] = mfma16(av[c][mt].v, bv.v, wacc[c][mt]);
-        }
-      }
-    }
-#endif
-    B3_T(4);
+    RCB_STAMPS_PHASE(B3, 4);
   }
-#if RCB_B3_STAMPS
-  ph_[6] = __builtin_amdgcn_s_memrealtime();
-  ph_[7] = t_entry_;
-  if (blockIdx.x == 0 && lane == 0)
-    for (int k = 0; k < 8; ++k) g_b3_stamps[wave * 8 + k] = ph_[k];
-#endif
+  RCB_STAMPS_ONLY(B3, ph_[6] = __builtin_amdgcn_s_memrealtime(); ph_[7] = t_entry_;)
+  RCB_STAMPS_PHASES_STORE(B3, blockIdx.x == 0 && lane == 0, wave * 8);
 #undef RCB_FETCH_B3
 #undef B3_XKEY
   float* slab = a.partial + (long long)blockIdx.x * ROW;
@@ -1514,54 +1381,14 @@ __global__ void __launch_bounds__(512) upconv_bwd3_fused_kernel(Bwd3Args a) {
   for (int c = 0; c < 2; ++c) {
     const int combo = 2 * wave + c;
     const int p = combo >> 2, t = combo & 3;
-#if RCB_B3_WG16
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
       for (int r = 0; r < 4; ++r)       // 16 x 16 accumulator: column (cout) = lane & 15, rows (cin) 4 (lane >> 4) + r
         slab[weff_index(t >> 1, t & 1, 16 * cb + 4 * (lane >> 4) + r, p >> 1, p & 1, lane & 15, COUT)] = wacc[c][cb][r];
-#else
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-      const int co = lane & 31;
-      if (co < COUT) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int ci = 32 * mt + rho(r, h);
-          slab[weff_index(t >> 1, t & 1, ci, p >> 1, p & 1, co, COUT)] = wacc[c][mt][r];
-        }
-      }
-    }
-#endif
   }
-#if RCB_B3_STAMPS
-  if (blockIdx.x == 0 && lane == 0) g_b3_stamps[wave * 8 + 4 + 60 - 60] = g_b3_stamps[wave * 8 + 4];   // (keeps slot 4)
-  if (blockIdx.x == 0 && lane == 0 && wave == 0) g_b3_stamps[63] = __builtin_amdgcn_s_memrealtime();   // kernel end of workgroup 0 (slot 7 of wave 7)
-#endif
+  RCB_STAMP(B3, blockIdx.x == 0 && lane == 0 && wave == 0, 63, memrealtime);   // kernel end of workgroup 0 (slot 7 of wave 7)
 }
-
-#if RCB_B3_STAMPS
-}  // namespace
-#if RCB_D2_STAMPS
-extern "C" int rcb_debug_d2_stamps(unsigned long long* dst, int n) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_d2_stamps), sizeof(unsigned long long) * n);
-}
-#endif
-#if RCB_WC_STAMPS
-extern "C" int rcb_debug_wc_stamps(unsigned long long* dst, int n) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wc_stamps), sizeof(unsigned long long) * n);
-}
-#endif
-#if RCB_F2_STAMPS
-extern "C" int rcb_debug_f2_stamps(unsigned long long* dst, int n) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_f2_stamps), sizeof(unsigned long long) * n);
-}
-#endif
-extern "C" int rcb_debug_b3_stamps(unsigned long long* dst, int n) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_b3_stamps), sizeof(unsigned long long) * n);
-}
-namespace {
-#endif
 
 // fixed-order sum of the workgroup slabs: out[j] = sum_w partial[w][j]
 __global__ void __launch_bounds__(256) upconv_wgrad_reduce_kernel(const float* __restrict__ partial, int nblk, int row,
@@ -1615,8 +1442,7 @@ __global__ void __launch_bounds__(256) upconv_wgrad_reduce_kernel(const float* _
 }
 
 template <typename K, typename A>
-int launch(K kfn, const A& args, int grid, size_t smem, hipStream_t st, bool& /*unused: the attribute is set per launch*/,
-           int threads = 512) {
+int launch(K kfn, const A& args, int grid, size_t smem, hipStream_t st, int threads = 512) {
   // (the attribute belongs to the (function, device) pair and a process may drive several devices: set it every time)
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   if (e != hipSuccess) return fail((int)e, "upconv: hipFuncSetAttribute: %s", hipGetErrorString(e));
@@ -1645,22 +1471,18 @@ extern "C" int rcb_upconv_fwd(const void* x, int32_t x_is_f32_preact, const floa
   constexpr int kFwd2Smem = 4 * 10 * 10 * 72 * 2 + 64 * 4;
   const int npair = (batch + 3) / 4;
   if (grid == 8 && cout == 64 && x_is_f32_preact == 1 && !y_is_f32_linear) {
-    static bool done = false;
-    return launch(upconv_fwd2_reg_kernel<1>, a, npair < 256 ? npair : 256, kFwd2Smem, st, done);
+    return launch(upconv_fwd2_reg_kernel<1>, a, npair < 256 ? npair : 256, kFwd2Smem, st);
   }
   if (grid == 16 && cout == 16 && !x_is_f32_preact && y_is_f32_linear == 1) {
-    static bool done = false;
-    if (half_wg(batch)) return launch(upconv_fwd3_lds_kernel<16, 0, 4>, a, 768, 18 * 18 * 64 * 2, st, done, 256);
-    return launch(upconv_fwd3_lds_kernel<16, 0, 8>, a, batch < 256 ? batch : 256, 18 * 18 * 64 * 2, st, done);
+    if (half_wg(batch)) return launch(upconv_fwd3_lds_kernel<16, 0, 4>, a, 768, 18 * 18 * 64 * 2, st, 256);
+    return launch(upconv_fwd3_lds_kernel<16, 0, 8>, a, batch < 256 ? batch : 256, 18 * 18 * 64 * 2, st);
   }
   if (grid == 16 && cout == 16 && !x_is_f32_preact && y_is_f32_linear == 2) {   // bf16 output, no activation
-    static bool done = false;
-    if (half_wg(batch)) return launch(upconv_fwd3_lds_kernel<16, 1, 4>, a, 768, 18 * 18 * 64 * 2, st, done, 256);
-    return launch(upconv_fwd3_lds_kernel<16, 1, 8>, a, batch < 256 ? batch : 256, 18 * 18 * 64 * 2, st, done);
+    if (half_wg(batch)) return launch(upconv_fwd3_lds_kernel<16, 1, 4>, a, 768, 18 * 18 * 64 * 2, st, 256);
+    return launch(upconv_fwd3_lds_kernel<16, 1, 8>, a, batch < 256 ? batch : 256, 18 * 18 * 64 * 2, st);
   }
   if (grid == 8 && cout == 64 && x_is_f32_preact == 2 && !y_is_f32_linear) {   // bf16 pre-activation input
-    static bool done = false;
-    return launch(upconv_fwd2_reg_kernel<3>, a, npair < 256 ? npair : 256, kFwd2Smem, st, done);
+    return launch(upconv_fwd2_reg_kernel<3>, a, npair < 256 ? npair : 256, kFwd2Smem, st);
   }
   return fail(RCB_ERR_UNSUPPORTED, "upconv_fwd: grid=%d cout=%d in_mode=%d out_f32=%d not instantiated", grid, cout,
               x_is_f32_preact, y_is_f32_linear);
@@ -1694,12 +1516,10 @@ extern "C" int rcb_upconv_dgrad(const void* dy, int32_t dy_is_f32, const float* 
   if (grid == 8 && cout == 64 && !dy_is_f32 && x_is_f32_preact == 2) return launch_dgrad2<0>(a, dbias_partial, st);
   RCB_REQUIRE(dbias_partial == nullptr, RCB_ERR_UNSUPPORTED, "upconv_dgrad: channel sums of dx only for the stage-2 kernels");
   if (grid == 16 && cout == 16 && dy_is_f32 && !x_is_f32_preact) {
-    static bool done = false;
-    return launch(upconv_dgrad3_lds_kernel<16, 0>, a, batch < 256 ? batch : 256, 32 * 1024 + 34 * 34 * 24 * 2, st, done);
+    return launch(upconv_dgrad3_lds_kernel<16, 0>, a, batch < 256 ? batch : 256, 32 * 1024 + 34 * 34 * 24 * 2, st);
   }
   if (grid == 16 && cout == 16 && !dy_is_f32 && !x_is_f32_preact) {
-    static bool done = false;
-    return launch(upconv_dgrad3_lds_kernel<16, 1>, a, batch < 256 ? batch : 256, 32 * 1024 + 34 * 34 * 24 * 2, st, done);
+    return launch(upconv_dgrad3_lds_kernel<16, 1>, a, batch < 256 ? batch : 256, 32 * 1024 + 34 * 34 * 24 * 2, st);
   }
   return fail(RCB_ERR_UNSUPPORTED, "upconv_dgrad: grid=%d cout=%d not instantiated", grid, cout);
 }
@@ -1726,9 +1546,8 @@ extern "C" int rcb_upconv_wgrad(const void* x, int32_t x_is_f32_preact, const vo
   bool hit = false;
 #define RCB_WGRAD_CASE(cond, COUTv, Gv, XM, DF, SMEM)                                        \
   if (!hit && (cond)) {                                                                      \
-    static bool done = false;                                                                \
     hit = true;                                                                              \
-    rc = launch(upconv_wgrad_kernel<COUTv, Gv, XM, DF>, a, g, SMEM, st, done);               \
+    rc = launch(upconv_wgrad_kernel<COUTv, Gv, XM, DF>, a, g, SMEM, st);                     \
   }
   RCB_WGRAD_CASE(grid == 16 && cout == 16 && !x_is_f32_preact && dy_is_f32, 16, 16, 0, 1, (18 * 18 * XRS + 32 * 32 * 16) * 2)
   RCB_WGRAD_CASE(grid == 16 && cout == 16 && !x_is_f32_preact && !dy_is_f32, 16, 16, 0, 0, (18 * 18 * XRS + 32 * 32 * 16) * 2)
@@ -1757,8 +1576,7 @@ extern "C" int rcb_upconv_bwd_fused(const void* dy, const float* weff, const voi
   Bwd3Args a{dy, weff, x, dx, workspace, batch, reinterpret_cast<const uint4*>(frag_pack)};
   hipStream_t st = (hipStream_t)stream;
   const int g = wgrad_blocks(batch);
-  static bool done = false;
-  int rc = launch(upconv_bwd3_fused_kernel, a, g, 32 * 1024 + (34 * 34 * 24 + 18 * 18 * (RCB_B3_WG16 ? 64 : XRS)) * 2 + 8 * 32 * 40 * 2, st, done);
+  int rc = launch(upconv_bwd3_fused_kernel, a, g, 32 * 1024 + (34 * 34 * 24 + 18 * 18 * 64) * 2 + 8 * 32 * 40 * 2, st);
   if (rc) return rc;
   const int row = 1024 * cout + cout;
   upconv_wgrad_reduce_kernel<<<(row + 63) / 64, 256, 0, st>>>(workspace, g, row, 1024 * cout, dweff, dbias);
@@ -1779,7 +1597,6 @@ extern "C" int rcb_upconv_fwd23(const void* z1, int32_t z1_is_f32_preact, const 
               z1_is_f32_preact, pe_is_f32_linear, frag_pack ? 1 : 0);
   RCB_REQUIRE(!half_wg(batch), RCB_ERR_UNSUPPORTED, "upconv_fwd23: RCB_UPCONV_HALF_WG=1 keeps the two launches");
   Fwd23Args a{z1, b2, b3, h2, pe, batch, reinterpret_cast<const uint4*>(frag_pack)};
-  static bool done = false;
   constexpr int kSmem = 2 * 18 * 18 * 64 * 2 + 2 * 10 * 10 * 72 * 2 + 64 * 4;
-  return launch(upconv_fwd23_kernel, a, batch < 256 ? batch : 256, kSmem, (hipStream_t)stream, done);
+  return launch(upconv_fwd23_kernel, a, batch < 256 ? batch : 256, kSmem, (hipStream_t)stream);
 }

@@ -1,13 +1,13 @@
-"""In-kernel timeline of the A-transform chunk loop (diagnostic build -DATRANS_STAMPS=1, selected with RCB_LIB).
+"""In-kernel timeline of the A-transform chunk loop (diagnostic build):
+    python -m recombiner_amd.build --variant atstamps --only atrans.hip -DRCB_STAMPS_ATRANS=1 ;  python tools/atrans_stamps.py
 Stamps of workgroup 0: 0 top of iteration, 1 after the vmcnt wait, 2 after the barrier, 3 at the middle block (before the
 wait for the next x pieces), 4 after the last block's MFMAs were issued, 5 end of iteration (after the conversion)."""
-import ctypes as C
-import os
 import sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+import kernel_stamps
+kernel_stamps.select("ATRANS")
 import torch
-from recombiner_amd import ops, _lib
+from recombiner_amd import ops
 
 rows = 4096
 sizes = [1056, 1056, 1056, 99]
@@ -24,10 +24,7 @@ tr.prepare(A)
 for _ in range(20):
     tr.forward(x, out)
 torch.cuda.synchronize()
-lib = _lib.load()
-buf = (C.c_uint64 * (8 * 40 * 6))()
-assert lib.rcb_debug_atrans_stamps(buf, 8 * 40 * 6) == 0
-st = np.array(buf, dtype=np.int64).reshape(8, 40, 6)
+st = kernel_stamps.read("ATRANS", (8, 40, 6))
 t0 = st[:, 0, 0].min()
 np.set_printoptions(linewidth=200)
 print("per-wave iteration length (stamp 0 to next stamp 0), iterations 5..25, mean per wave:", np.diff(st[:, 5:26, 0], axis=1).mean(1).round())

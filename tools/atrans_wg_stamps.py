@@ -1,7 +1,7 @@
-"""Per-workgroup timeline of an A-transform launch (diagnostic build -DATRANS_STAMPS=1, selected with RCB_LIB):
+"""Per-workgroup timeline of an A-transform launch (diagnostic build):
 
-    python -m recombiner_amd.build --variant atstamps --only atrans.hip -DATRANS_STAMPS=1
-    RCB_LIB=recombiner_amd/lib/librcb_atstamps.so python tools/atrans_wg_stamps.py [rows] [terms] [nofit]
+    python -m recombiner_amd.build --variant atwgstamps --only atrans.hip -DRCB_STAMPS_ATRANS_WG=1
+    python tools/atrans_wg_stamps.py [rows] [terms] [nofit]
 
 Every workgroup of the launch stamps its begin and end (s_memrealtime, 100 MHz, one clock for the whole chip; s_memtime for
 the shader clock).  Printed:
@@ -12,19 +12,18 @@ the shader clock).  Printed:
      layer: the difference is 16 chunk iterations, the rest the segment's prologue + epilogue; least-squares fit of the
      iteration time t(w) = a + b w and the planner's constants F = a / b, E = rest / b (block-chunk units)."""
 import ctypes as C
-import os
 import sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+import kernel_stamps
+kernel_stamps.select("ATRANS_WG")
 import torch
-from recombiner_amd import ops, _lib
+from recombiner_amd import ops
 
 REALTIME_MHZ = 100.0
 HEAD = 12
 rows = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 terms = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 dev = "cuda"
-lib = _lib.load()
 torch.manual_seed(0)
 
 
@@ -68,13 +67,11 @@ def stamps(tr, x, out, n_wg, reps=9):
     for _ in range(20):
         tr.forward(x, out)
     res = []
-    buf = (C.c_uint64 * (4 * n_wg))()
     for _ in range(reps):
         torch.cuda.synchronize()
         tr.forward(x, out)
         torch.cuda.synchronize()
-        assert lib.rcb_debug_atrans_wg_stamps(buf, n_wg) == 0
-        res.append(np.array(buf, dtype=np.int64).reshape(n_wg, 4))
+        res.append(kernel_stamps.read("ATRANS_WG", (n_wg, 4)))
     return np.stack(res)
 
 

@@ -1,15 +1,12 @@
 """Where the stage-2 data-gradient kernel spends its cycles (diagnostic build):
-   python -m recombiner_amd.build --variant d2 --only upconv.hip -DRCB_B3_STAMPS=1 -DRCB_D2_STAMPS=1
-   RCB_LIB=.../librcb_d2.so python tools/d2_stamps.py
+   python -m recombiner_amd.build --variant d2 --only upconv.hip -DRCB_STAMPS_D2=1 ;  python tools/d2_stamps.py
 Per wave of workgroup 0, s_memtime ticks summed over its 16 INRs: barrier A, staging, barrier B, MFMA loop (incl. prefetch
 issue), exchange write, barrier C, epilogue."""
-import ctypes as C
-import os
-import sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+import kernel_stamps
+kernel_stamps.select("D2")
 import torch
-from recombiner_amd import ops, _lib
+from recombiner_amd import ops
 
 B = 4096
 dy = (torch.randn(B, 16, 16, 64, device="cuda") * 1e-3).bfloat16()
@@ -30,14 +27,7 @@ for _ in range(10):
 e1.record()
 torch.cuda.synchronize()
 print("avg us per launch:", e0.elapsed_time(e1) * 100)
-lib = _lib.load()
-try:
-    f = lib.rcb_debug_d2_stamps
-except AttributeError:
-    sys.exit("not a stamps build")
-buf = (C.c_uint64 * 64)()
-assert f(buf, 64) == 0
-raw = np.array(buf, dtype=np.int64).reshape(8, 8)
+raw = kernel_stamps.read("D2", (8, 8))
 st = raw[:, :7].copy()
 prologue_us, loop_us = raw[:, 2].mean() / 100.0, raw[:, 7].mean() / 100.0       # s_memrealtime: 100 MHz (slot 2: no barrier B any more)
 st[:, 2] = 0

@@ -1,15 +1,12 @@
 """Where the stage-2 forward kernel spends its time (diagnostic build):
-   python -m recombiner_amd.build --variant f2 --only upconv.hip -DRCB_B3_STAMPS=1 -DRCB_F2_STAMPS=1
-   RCB_LIB=.../librcb_f2.so python tools/f2_stamps.py
+   python -m recombiner_amd.build --variant f2 --only upconv.hip -DRCB_STAMPS_F2=1 ;  python tools/f2_stamps.py
 Per wave of workgroup 0, s_memtime ticks summed over its passes (4 INRs each): first barrier, staging, second barrier,
 gathers + MFMAs of its four (INR, tile) pairs, their epilogues (bias, LeakyReLU, lane swap, stores)."""
-import ctypes as C
-import os
-import sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+import kernel_stamps
+kernel_stamps.select("F2")
 import torch
-from recombiner_amd import ops, _lib
+from recombiner_amd import ops
 
 B = 4096
 x = torch.randn(B, 8, 8, 64, device="cuda").bfloat16()
@@ -30,14 +27,7 @@ for _ in range(10):
 e1.record()
 torch.cuda.synchronize()
 print("avg us per launch:", e0.elapsed_time(e1) * 100)
-lib = _lib.load()
-try:
-    f = lib.rcb_debug_f2_stamps
-except AttributeError:
-    sys.exit("not a stamps build")
-buf = (C.c_uint64 * 64)()
-assert f(buf, 64) == 0
-raw = np.array(buf, dtype=np.int64).reshape(8, 8)
+raw = kernel_stamps.read("F2", (8, 8))
 st = raw[:, :5]
 wall_us = (raw[:, 6] - raw[:, 5]) / 100.0        # s_memrealtime: 100 MHz
 print("workgroup 0: prologue (weights, LDS clear, first fetch issued) %.1f us;" % ((raw[:, 5] - raw[:, 7]).mean() / 100.0), end=" ")

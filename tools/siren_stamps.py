@@ -1,30 +1,21 @@
-"""Phase breakdown of the fused bf16 SIREN kernel from in-kernel s_memtime stamps (DIAGNOSTIC build, -DRCB_SIREN_STAMPS:
-built here into gpurun_out/librcb_stamps.so, loaded through RCB_LIB; the shipped library carries no stamps).
-    python tools/siren_stamps.py            (on the GPU box)"""
-import ctypes as C
-import os
-import subprocess
+"""Phase breakdown of the fused bf16 SIREN kernel from in-kernel s_memtime stamps (diagnostic builds; the shipped library
+carries no stamps):
+    python -m recombiner_amd.build --variant stamps --only siren_mlp_bf16.hip -DRCB_STAMPS_SIREN=1 ;  python tools/siren_stamps.py [n]
+    python -m recombiner_amd.build --variant widestamps --only siren_mlp_wide.hip -DRCB_STAMPS_WIDE=1 ;  python tools/siren_stamps.py wide 64 [n]"""
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-out_dir = os.path.join(ROOT, "gpurun_out")
-os.makedirs(out_dir, exist_ok=True)
-lib = os.path.join(out_dir, "librcb_stamps.so")
-from recombiner_amd import build as B  # noqa: E402
-cmd = [B.hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-DRCB_SIREN_STAMPS", "-Wno-unused-result"] + \
-      [os.path.join(B.CSRC, s) for s in B.SOURCES] + ["-o", lib]
-subprocess.check_call(cmd)
-os.environ["RCB_LIB"] = lib
-import torch  # noqa: E402
-from recombiner_amd import _lib, ops, utils  # noqa: E402
-from recombiner_amd.ops import SirenMeta  # noqa: E402
+import kernel_stamps
 
-WIDE = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[1] == "wide" else 0      # python tools/siren_stamps.py wide 64 [n]
+WIDE = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[1] == "wide" else 0
 if WIDE:
     del sys.argv[1:3]
+kernel_stamps.select("WIDE" if WIDE else "SIREN")
+import torch  # noqa: E402
+from recombiner_amd import ops, utils  # noqa: E402
+from recombiner_amd.ops import SirenMeta  # noqa: E402
+
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 X, Y = utils.synthetic_inputs([32, 32], 16, n, 3, seed=0)
 meta = SirenMeta(1, 1024, 16, 16, 3, WIDE or 32, 3, precision=1)
@@ -34,12 +25,8 @@ wv = (torch.rand(n, meta.d_net, device="cuda") * 2 - 1) * 0.02
 for _ in range(5):
     ops.siren_loss_bwd(Xd, pe, wv, Yd, 1.0 / 3072, meta)
 torch.cuda.synchronize()
-L = _lib.load()
 nb = min(n, 8192)
-buf = (C.c_uint64 * (nb * 16))()
-rc = (L.rcb_debug_read_stamps_wide if WIDE else L.rcb_debug_read_stamps)(buf, nb * 16)
-assert rc == 0, rc
-st = np.frombuffer(buf, dtype=np.uint64).reshape(nb, 16).astype(np.int64)
+st = kernel_stamps.read("WIDE" if WIDE else "SIREN", (nb, 16))
 # persistent kernel: the stamps of a workgroup's LAST row survive.  1 = row start (its weights were requested during the row
 # before), 2 = fragments stored (+sync), 3 = wave 0 done with its tiles, 4 = all waves done, 5 = partials in LDS and the next
 # row's weights requested (+sync), 6 = gradients summed and stored, 7 = row end (+sync)
