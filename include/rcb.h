@@ -27,9 +27,9 @@ extern "C" {
  * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop; 412: rcb_signal_patch_fmt,
  * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged; 414: rcb_ssim_workspace_bytes, rcb_ssim;
  * 415: rcb_ssim_list_table_bytes, rcb_ssim_list_workspace_bytes, rcb_ssim_list_plan, rcb_ssim_list;
- * 416: rcb_resize_taps, rcb_resize_table_bytes, rcb_resize).  A binding compares
+ * 416: rcb_resize_taps, rcb_resize_table_bytes, rcb_resize; 417: rcb_recon_regions_workspace_bytes, rcb_recon_regions).  A binding compares
  * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 416
+#define RCB_VERSION 417
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -824,6 +824,47 @@ int rcb_recon_finish_ragged(const float* y, const float* target, int64_t n_rows,
                             const int32_t* patch_nums, const int32_t* patch_size, const int32_t* sizes, const int64_t* spans,
                             int64_t out_elems, int32_t mode, int32_t depth, void* q_out, float* whole, double* sse, int32_t* n_bad,
                             void* workspace, int64_t workspace_bytes, void* table, int64_t table_bytes, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (417): the distortion figure by REGION -- per frame of a clip, per patch, per tile of a distortion map -- where the entries
+ * above give one sum per datapoint.  rcb_recon_regions reads what rcb_recon_finish_fmt reads: y and `target` (nullable)
+ * [n_rows][n_pix][channels] fp32, nd = 1..3 with patch_nums / patch_size, a nullable `size` (the extent sz; null: the grid G), mode
+ * 0 .. 3 and depth; and `region`, a HOST array of nd entries, the box per axis, each >= 1 (a box may exceed the extent).  It writes
+ * nothing but sums.
+ *   Region grid: regions tile the EXTENT, not the grid: nr[i] = ceil(sz[i] / region[i]) boxes per axis, n_regions = prod nr[i], the
+ *     region index row-major over (r_0 .. r_nd-1); region r is the box [r_i * region[i], min((r_i + 1) * region[i], sz[i])) -- a region
+ *     on the far edge is a smaller box.  Padding (grid positions outside the extent) belongs to no region: it adds nothing, is never
+ *     counted, is never read, and its values -- a NaN included -- cannot change any output bit.
+ *   Elements of a region: the box's positions row-major with the channels innermost, n_r = prod(box_i) * channels of them: the order
+ *     of the whole signal, NOT the patch order of y.  The value at an element is what rcb_recon_finish_fmt forms there for the same
+ *     mode and depth: v, d = t - v in fp32, the term (double)d * (double)d.
+ *   Sum: the additions rcb_recon_finish performs on a datapoint of n_r elements -- chunks of 8192 elements, thread t of 256 owning
+ *     the quads t, t + 256, ... in element order, the xor butterfly over the lanes, the waves in wave order, then the chunk partials
+ *     (thread t: partials t, t + 256, ..., the same butterfly).  So sse_r[d][r] is BITWISE the sse that rcb_recon_finish_fmt (nd = 0,
+ *     n_pix = n_r / channels, same mode and depth) returns for that region's values copied out contiguously in that order; and
+ *     bitwise the same alone, in any batch, in any batch order, from run to run, and on the 16-byte and the element-wise memory
+ *     path (16-byte loads: min(region, sz)[nd-1] * channels, sz[nd-1] * channels and patch_size[nd-1] * channels multiples of 4,
+ *     y and target 16-byte aligned; the entry decides).
+ *   What does NOT hold: sum_r sse_r[d][r] is the datapoint's sse (rcb_recon_finish_fmt with the same size) only to within
+ *     reordering -- the same terms, other additions -- not bitwise.  The one exception: a single region covering an unpatched signal
+ *     (patch_nums of ones, size null), where the two orders coincide and so do the bits.
+ *   n_bad_r [n_data][n_regions] int32: the non-finite y and target elements of the region (an element with both counts twice).  A
+ *     region with n_bad_r > 0 has sse_r = NaN; no other region does.
+ *   sse_r [n_data][n_regions] fp64; needs `target`.  Each output is nullable, not both.
+ * `workspace`: rcb_recon_regions_workspace_bytes(n_data, n_regions, max_region_elems) bytes, 8-byte aligned, max_region_elems =
+ * prod(min(region[i], sz[i])) * channels, the elements of the largest box; callable without a device; -1 for a shape it refuses: a
+ * non-positive argument, more than 2^31 - 1 regions or elements, more than 2^31 - 1 workgroups = n_data * n_regions *
+ * ceil(max_region_elems / 8192).  (A box of few elements still occupies a workgroup of 256 threads: tiles of 8 x 8 leave most lanes
+ * idle.  The entry is exact there, not efficient.)
+ * Nothing is uploaded and the stream is not synchronised: unlike the per-signal entries of 413, this one can be graph-captured.
+ * Refused (RCB_ERR_*), nothing launched: null y / workspace / patch geometry / region, both outputs null, nd outside 1..3, a
+ * region[i] < 1, channels outside 1..32, n_pix != prod(patch_size), n_rows no multiple of prod(patch_nums), a size[i] outside
+ * [1, G_i], the mode and depth rules of rcb_recon_finish_fmt, sse_r without target, more than 2^31 - 1 elements per datapoint or
+ * workgroups, a workspace that is too small or misaligned. */
+int64_t rcb_recon_regions_workspace_bytes(int64_t n_data, int64_t n_regions, int64_t max_region_elems);
+int rcb_recon_regions(const float* y, const float* target, int64_t n_rows, int32_t n_pix, int32_t channels, int32_t nd,
+                      const int32_t* patch_nums, const int32_t* patch_size, const int32_t* size, const int32_t* region, int32_t mode,
+                      int32_t depth, double* sse_r, int32_t* n_bad_r, void* workspace, int64_t workspace_bytes, rcb_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * N4 (414): SSIM and the sums of MS-SSIM (Wang et al. 2004, the usual constants) of decoded images against their sources, on the

@@ -64,7 +64,7 @@ class LevelBwd(C.Structure):
 
 _lib = None
 # the header these mirrors were written against (include/rcb.h: RCB_VERSION) and the structures load() verifies by size
-ABI_VERSION = 416
+ABI_VERSION = 417
 _MIRRORS = {0: SirenDesc, 1: Level, 2: LevelBwd, 3: AdamCfg, 4: AdamTensor, 5: RecDesc}
 
 # The prototype of every entry point of include/rcb.h, in header order: name -> (restype, [argtypes]).  load() applies it, so
@@ -148,6 +148,8 @@ PROTOTYPES = {
     "rcb_signal_patch_ragged": (_int, [_p, _i64, _i32, _i32, _i64, _i32, _p, _p, _p, _p, _i32, _i64, _p, _p, _i64, _p]),
     "rcb_recon_finish_ragged": (_int, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _i64, _i32, _i32, _p, _p, _p, _p, _p, _i64, _p,
                                        _i64, _p]),
+    "rcb_recon_regions_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "rcb_recon_regions": (_int, [_p, _p, _i64, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _i64, _p]),
     "rcb_ssim_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
     "rcb_ssim": (_int, [_p, _p, _i32, _i32, _i64, _i32, _i32, _i32, _p, _p, _p, _f64, _f64, _i32, _p, _p, _p, _i64, _p]),
     "rcb_ssim_list_table_bytes": (_i64, [_i64, _i32]),

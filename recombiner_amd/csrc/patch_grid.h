@@ -1,5 +1,6 @@
 // N4: the one index rule of the whole-signal entries (recon.hip: rcb_recon_finish and its _crop / _fmt / _ragged forms; signal.hip:
-// rcb_signal_patch and its _pad / _fmt / _ragged forms).  A signal lies on the grid G_i = pn[i] * ps[i]; its y [per][P][C] holds patch after patch
+// rcb_signal_patch and its _pad / _fmt / _ragged forms; recon_regions.hip: rcb_recon_regions, which goes the other way, from a grid
+// position to its run).  A signal lies on the grid G_i = pn[i] * ps[i]; its y [per][P][C] holds patch after patch
 // (b0 b1 b2 row-major), each patch pixel after pixel (p0 p1 p2 row-major), so the R = ps[2] * C elements of a patch row are
 // contiguous: a run.  Run number r of a signal counts (b0, b1, b2, p0, p1) row-major and lies at grid position g_i = b_i * ps_i + p_i,
 // its element `off` at e = b2 * R + off of the grid row (g0, g1).  Both files cut a signal into chunks of kChunk elements, one
@@ -40,6 +41,15 @@ __device__ __forceinline__ void decode_run(const PatchGeo& g, int run, int& g0, 
     g0 = min(g0, g.sz[0] - 1);
     g1 = min(g1, g.sz[1] - 1);
   }
+}
+
+// The inverse (recon_regions.hip, which walks boxes of the signal and gathers from y): the grid row (g0, g1) and the patch b2
+// along the last axis -> the run that decode_run<false> maps there.  Element e = b2 * R + off of that grid row lies at
+// encode_run(g, g0, g1, e / R) * R + e % R of the signal's y; a run number is below E / R, so it fits an int.
+__device__ __forceinline__ int encode_run(const PatchGeo& g, int g0, int g1, int b2) {
+  const int b0 = g0 / g.ps[0], p0 = g0 % g.ps[0];
+  const int b1 = g1 / g.ps[1], p1 = g1 % g.ps[1];
+  return (((b0 * g.pn[1] + b1) * g.pn[2] + b2) * g.ps[0] + p0) * g.ps[1] + p1;
 }
 
 inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }

@@ -27,7 +27,8 @@
 //
 // rcb_recon_finish_crop is the same kernel (template parameter CROP) for datapoints of which only a leading extent is real.
 // Where a run lies in the stitched signal, the chunking and the validation of the patch grid are patch_grid.h's, shared with
-// signal.hip, which cuts the signals the other way.
+// signal.hip, which cuts the signals the other way.  What an element becomes (finish, finish16), the term it adds and block_sum are
+// recon_elem.h's, shared with recon_regions.hip, which sums the same terms per box of the signal.
 //
 // rcb_recon_finish_ragged (template parameter RAG) is the crop form with one extent and one
 // output span PER SIGNAL, read from row d of a device table the host entry writes (patch_grid.h: RaggedRow): each signal's outputs
@@ -36,7 +37,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "patch_grid.h"
+#include "recon_elem.h"                                  // the per-element arithmetic and block_sum, shared with recon_regions.hip
 
 #pragma clang fp contract(off)
 
@@ -84,62 +85,6 @@ __device__ __forceinline__ long long ragged_row(const PatchGeo& g, const RaggedR
 // element e = pos * C + c of a grid row inside the span: e itself where the last axis is the innermost (kRaggedDense)
 __device__ __forceinline__ long long ragged_elem(const PatchGeo& g, const RaggedRow& r, int e) {
   return (r.flags & kRaggedDense) ? (long long)e : (e / g.C) * r.as[2] + e % g.C;
-}
-
-struct Elem {
-  float v;
-  unsigned q;
-  bool bad;
-};
-
-__device__ __forceinline__ Elem finish(float x, int mode) {
-  Elem e;
-  e.bad = !(fabsf(x) < __builtin_inff());
-  if (mode == 0) {
-    const float c = (x != x) ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f);
-    const float q = rintf(c * 255.0f);
-    e.q = (unsigned)q;
-    e.v = q / 255.0f;
-  } else {
-    e.q = 0;
-    e.v = x;
-  }
-  return e;
-}
-
-// modes 2 and 3: v is formed from the INTEGER (q = 0 gives +0.0 whatever the sign of x); for s16 (float)(int)u = u and the division
-// by 65536 is exact, for u16 it is the one IEEE fp32 division by M.  e.q: the 16-bit word to store.
-__device__ __forceinline__ Elem finish16(float x, const ReconGeo& r) {
-  Elem e;
-  e.bad = !(fabsf(x) < __builtin_inff());
-  const float c = (x != x) ? 0.0f : fminf(fmaxf(x, 0.0f), 1.0f);
-  const int u = (int)fminf(rintf(c * r.scale), r.cap);
-  e.q = (unsigned)(u - r.bias) & 0xffffu;
-  e.v = (float)u / r.scale;
-  return e;
-}
-
-// The workgroup's sum of (acc, bad), valid in thread 0 (-> true there): the 64 lanes of a wave by the xor butterfly, the waves in
-// wave order -- the same additions whatever the launch.
-__device__ __forceinline__ bool block_sum(double& acc, int& bad) {
-  __shared__ double s_acc[kThreads / kWave];
-  __shared__ int s_bad[kThreads / kWave];
-  acc = wave_sum(acc);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off, 64);
-  if ((threadIdx.x & 63) == 0) {
-    s_acc[threadIdx.x >> 6] = acc;
-    s_bad[threadIdx.x >> 6] = bad;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return false;
-  acc = s_acc[0];
-  bad = s_bad[0];
-  for (int w = 1; w < kThreads / kWave; ++w) {
-    acc += s_acc[w];
-    bad += s_bad[w];
-  }
-  return true;
 }
 
 // the integer output at element offset o: bytes, or (W16) 16-bit words, a quad of which is one 8-byte store
@@ -244,15 +189,8 @@ __global__ void __launch_bounds__(kThreads) recon_kernel(const float* __restrict
     Elem e[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      e[k] = W16 ? finish16(xs[k], x) : finish(xs[k], x.mode);
-      if (k < n) {
-        const bool in = !CROP || co[k] >= 0;
-        const bool b = e[k].bad || !(fabsf(t[k]) < __builtin_inff());
-        bad += in ? (int)e[k].bad + (int)!(fabsf(t[k]) < __builtin_inff()) : 0;
-        const float df = t[k] - e[k].v;
-        const double dd = (double)df;
-        acc += (b || !in) ? 0.0 : dd * dd;               // (a bad element makes the datapoint's sse NaN in the second kernel)
-      }
+      e[k] = W16 ? finish16(xs[k], x.scale, x.cap, x.bias) : finish(xs[k], x.mode);
+      if (k < n) RCB_RECON_ADD_TERM(e[k], t[k], !CROP || co[k] >= 0, acc, bad);
     }
     if (CROP) {
       if (u8 || whole) {
@@ -390,9 +328,7 @@ static int finish_entry(const char* who, bool fmt, const float* y, const float* 
   }
   RCB_REQUIRE(y && workspace, RCB_ERR_ARG, "%s: null y or workspace", who);
   if (fmt) {
-    RCB_REQUIRE(mode >= 0 && mode <= 3, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw, 2 = u16, 3 = s16)", who, mode);
-    RCB_REQUIRE(mode == 2 ? (depth >= 9 && depth <= 16) : depth == 0, RCB_ERR_ARG,
-                "%s: depth %d for mode %d (9 .. 16 for u16, 0 for the others)", who, depth, mode);
+    if (const int err = check_mode_fmt(who, mode, depth)) return err;
   } else {
     RCB_REQUIRE(mode == 0 || mode == 1, RCB_ERR_ARG, "%s: mode %d (0 = 8-bit, 1 = raw)", who, mode);
   }
@@ -424,9 +360,8 @@ static int finish_entry(const char* who, bool fmt, const float* y, const float* 
   grid_elems(g, channels, E);
   x.mode = mode;
   const bool w16 = mode >= 2;
-  x.scale = mode == 2 ? (float)((1 << depth) - 1) : 65536.0f;
-  x.cap = mode == 2 ? x.scale : 65535.0f;
-  x.bias = mode == 3 ? 32768 : 0;
+  const SampleRule16 rule = sample_rule16(mode, depth);
+  x.scale = rule.scale, x.cap = rule.cap, x.bias = rule.bias;
   const uintptr_t q_align = w16 ? 8 : 4;                     // a quad of the integer output
   const long long blocks = n_data * g.n_chunks;
   double* part_sse = static_cast<double*>(workspace);

@@ -327,23 +327,30 @@ def compress_signals(config, dataset, checkpoint, signals, x=None, channels_firs
     return compress(config, dataset, checkpoint, _default_x(x, config, device, y.shape[0]), y, sample_format=sample_format, **kw)
 
 
-def compress_resized(config, dataset, checkpoint, signals, crop=None, channels_first=False, sample_format=None, **kw):
+def compress_resized(config, dataset, checkpoint, signals, crop=None, channels_first=False, sample_format=None, regions=None, **kw):
     """`compress_signals` on sources of any size, brought to the preset's grid on the device first (utils.resize_to_preset, which
     documents crop / channels_first and the order of the steps: first frames, landscape swap, centre crop, one antialiased
     resize with one rounding -- data/video.py:26-31 with crop=(240, 240) on the video preset).  -> what compress_signals returns,
     plus the resized source [n, *grid, C] of the signals' dtype: the signal that was coded, hence the one the decoded integers are
     scored against (report_signals, report_ssim, report_ssim_frames).  The stream is that of a signal at the preset's grid:
-    bitstream.decode_signal decodes it.  Every other argument is `compress`'s."""
+    bitstream.decode_signal decodes it.  Every other argument is `compress`'s.
+    regions ("patch", "frame", "row" or a box of one int per axis: utils.region_of; None: nothing changes): one more element is
+    appended, the distortion figure per region of every resized signal, fp64 [n, *nr] (the model's report_regions_signals)."""
     from . import utils
     device = kw.get("device", "cuda")
     (moved,) = _signal_views("compress_resized", [signals], sample_format, device)
     resized = utils.resize_to_preset(config, moved, crop=crop, channels_first=channels_first, sample_format=sample_format)
     out = compress_signals(config, dataset, checkpoint, resized, landscape=False, sample_format=sample_format, **kw)
-    return (*out, resized)
+    if regions is None:
+        return (*out, resized)
+    n_rows = resized.shape[0] * int(np.prod(utils.preset_grid(config)[0]))
+    by_region = out[1].report_regions_signals(_default_x(kw.get("x"), config, device, n_rows), resized, region=regions,
+                                              sample_format=sample_format)
+    return (*out, resized, by_region)
 
 
 def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_first=False, bitstream_path=None,
-                         sample_format=None, **kw):
+                         sample_format=None, regions=None, **kw):
     """`compress_signals` for signals of ANY size that the preset can be fitted to: `signals` is [n, *size, C] (or [n, C, *size]
     with channels_first), uint8 or fp32, one size per call (a list of signals of mixed sizes: compress_signal_list).
     The config is fitted (utils.fit_config: patched presets get the
@@ -361,7 +368,10 @@ def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_
     sample_format (utils.SampleFormat; required for uint16 / int16 signals, ValueError without it): how the samples are stored.
     `distortion` is then formed on the format's lattice -- the figure of the signal decode_signal_any delivers.  For s16 audio
     that is the distortion of the delivered PCM, NOT the reference's figure, which scores the unrounded reconstruction
-    (utils.metric, round=False).  A format other than the preset's implied one makes the stream version 3, which carries it."""
+    (utils.metric, round=False).  A format other than the preset's implied one makes the stream version 3, which carries it.
+    regions ("patch", "frame", "row" or a box of one int per axis: utils.region_of; None: nothing changes): one more element is
+    appended to the result, the distortion figure per region over the REAL samples, fp64 [n, *nr] (the model's report_regions
+    with size=): the regions tile `size`, so the patches on the far edges show what the padding fitted at full weight costs."""
     from . import bitstream, utils
     device = kw.get("device", "cuda")
     (view,) = _signal_views("compress_signals_any", [signals], sample_format, device, config, channels_first)
@@ -373,6 +383,8 @@ def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_
     distortion = model.report(x, y, size=size, sample_format=sample_format)
     if bitstream_path is not None:
         _write_stream(bitstream_path, bitstream.encode(model, extent=size, sample_format=sample_format))
+    if regions is not None:
+        return distortion, model, fitted, model.report_regions(x, y, region=regions, size=size, sample_format=sample_format)
     return distortion, model, fitted
 
 

@@ -1280,6 +1280,57 @@ def _recon_workspace(n_data, elems, dev):
     return torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8), max(n_ws, 8)
 
 
+def recon_regions(y, target, layout, region, mode=RECON_8BIT, size=None, sample_format=None, out=None):
+    """The squared error of a reconstruction y [N, P, C] against `target` BY REGION (rcb_recon_regions, include/rcb.h N4 417):
+    the extent of every signal -- `size`, or the grid of `layout` (a PeLayout of 1 to 3 axes; patch_nums of ones for an unpatched
+    preset) -- is tiled by boxes of `region` positions per axis (one int per axis, each >= 1; a box may exceed the extent, a box on
+    the far edge is smaller, padding belongs to none), nr[i] = ceil(extent[i] / region[i]) of them per axis.
+    -> (sse_r fp64 [n_data, *nr] (None without a target): per box the sum of squared errors of the values recon_finish forms for
+        the same mode / sample_format; NaN for a box with a non-finite element,
+        n_bad_r int32 [n_data, *nr]: the box's non-finite elements of y and target).
+    sse_r[d][r] is bitwise recon_finish(layout=None)'s sse on that box's values gathered contiguous, alone or in any batch.  The sum
+    over the boxes is the datapoint's sse only to within reordering.  Nothing is read back: no host sync, no table upload.
+    mode / sample_format: as recon_finish (a format overrides the mode).  out: optional preallocated (sse_r, n_bad_r)."""
+    mode, depth, _ = _sample_rule(sample_format=sample_format, mode=mode)
+    N, P, Cc = _recon_inputs("recon_regions", y, target)
+    nd, pn, ps, per, _, grid = _grid_args(layout)
+    if layout is None or nd > 3 or len(layout.patch_size) != nd:
+        raise RcbError(f"recon_regions: {nd} grid dimensions (a PeLayout of 1 to 3 axes)")
+    region = [int(v) for v in region]
+    if len(region) != nd:
+        raise RcbError(f"recon_regions: region of {len(region)} entries for a layout of {nd} axes")
+    extent, crop = list(grid), None
+    if size is not None:
+        size = [int(v) for v in size]
+        if len(size) != nd:
+            raise RcbError(f"recon_regions: size of {len(size)} entries for a layout of {nd} axes")
+        if all(1 <= s <= g for s, g in zip(size, grid)):       # (else: the library says why)
+            extent = size
+        crop = (C.c_int32 * 3)(*(size + [0] * (3 - nd)))
+    n_data = N // max(per, 1)
+    dev = y.device
+    # (a region below 1, rows that are no whole datapoints: shapes of one box here, the library says why)
+    nr = tuple(-(-e // r) if r >= 1 else 1 for e, r in zip(extent, region))
+    n_regions = int(np.prod(nr))
+    max_elems = int(np.prod([min(e, r) if r >= 1 else e for e, r in zip(extent, region)])) * Cc
+    shape = (n_data, *nr)
+    sse_r, n_bad_r = out if out is not None else (None, None)
+    if target is not None and sse_r is None:
+        sse_r = torch.empty(shape, device=dev, dtype=f64)
+    if n_bad_r is None:
+        n_bad_r = torch.empty(shape, device=dev, dtype=i32)
+    for t_, dt in ((sse_r, f64), (n_bad_r, i32)):
+        if t_ is not None and (tuple(t_.shape) != shape or t_.dtype != dt or t_.device != dev or not t_.is_contiguous()):
+            raise RcbError(f"recon_regions: output of shape {tuple(t_.shape)} {t_.dtype}, expected contiguous {shape} {dt} on the "
+                           "device of y")
+    n_ws = int(_lib.load().rcb_recon_regions_workspace_bytes(max(n_data, 1), n_regions, max_elems)) if N else -1
+    ws = torch.empty(max(n_ws, 8), device=dev, dtype=torch.uint8)
+    # (a box larger than any extent is the same box at 2^31 - 1; a value below -2^31: "below 1" is all the library need hear)
+    reg = (C.c_int32 * 3)(*([min(max(r, -1), 0x7fffffff) for r in region] + [0] * (3 - nd)))
+    _launch("rcb_recon_regions", ptr(y, f32), ptr(target, f32, True), N, P, Cc, nd, pn, ps, crop, reg, int(mode), depth, ptr(sse_r, f64, True), ptr(n_bad_r, i32), ptr(ws), max(n_ws, 8))
+    return sse_r, n_bad_r
+
+
 # ---------------------------------------------------------------------------------------------------
 # N4: the encoder's first step, whole signals -> patch targets (rcb_signal_patch)
 # ---------------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@ from .ops import LevelSpec, SirenMeta
 from .upsample_fast import (hip_path_supported, tiled_2d_preferred, phase_form_preferred, phase_module,
                             stitched2d_module, upsample_cifar_hip)
 from .utils import SampleFormat, count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs, metric_device, ssim_device, ssim_frames_device
+from .utils import metric_regions_device, region_of
 from .utils import map_hierarchical_model_to_int_weights  # noqa: F401  (module-level name, as upstream imports it)
 
 
@@ -167,6 +168,39 @@ class InrGeometry:
         """`report` against whole signals instead of patch targets (sizes: a list of signals, as patch_signals takes it)"""
         return self.report(x, self.patch_signals(signals, size, sample_format, sizes=sizes), size=size, sample_format=sample_format,
                            sizes=sizes)
+
+    def report_regions(self, x, y, region="patch", size=None, sample_format=None):
+        """The distortion figure of `report` BY REGION of every signal, fp64 [n, *nr] (the model with `predict` and `dataset`, as
+        `report`): predict, then one pass of rcb_recon_regions (utils.metric_regions_device); only the per-region sums come back.
+        Every region gets its own figure -- PSNR (RMSD for protein) over its own elements -- whatever the dataset's batch convention.
+        region: "patch" (one figure per patch of the codec: which patch is worst), "frame" (3-D presets: one per frame), "row", or
+        a box of one int per axis, e.g. (16, 16) tiles for a distortion map (utils.region_of).  The regions tile the signal's extent
+        -- `size` (y = patch_signals(signals, size)), or the model's grid -- so a region on the far edge is smaller, and edge padding
+        belongs to none: with size= the figures count real samples only.  sample_format: as `report`.
+        This is NOT the video convention by itself: that is the mean over the frames of report_frames."""
+        layout = self.signal_layout()
+        box = region_of(layout, region)
+        with torch.no_grad():
+            y_pred = self.predict(x.to(self.loc.device))
+        return metric_regions_device(y, y_pred, self.dataset, layout, box, size=size, sample_format=sample_format)
+
+    def report_regions_signals(self, x, signals, region="patch", size=None, sample_format=None):
+        """`report_regions` against whole signals instead of patch targets (as report_signals)"""
+        return self.report_regions(x, self.patch_signals(signals, size, sample_format), region=region, size=size,
+                                   sample_format=sample_format)
+
+    def report_frames(self, x, y_or_signals, size=None, sample_format=None):
+        """Per-frame PSNR of the clips this model delivers, fp64 [n, T] -- the PSNR twin of report_ssim_frames, for the 3-D presets,
+        axis 0 of the grid being the frame axis.  The video convention is the MEAN of these per-frame PSNRs (and the curve over
+        time); the caller averages.  `report` gives the other figure, one PSNR of the whole batch's mean squared error, which
+        weights a bad frame more.  y_or_signals: patch targets [N, P, C] (fp32, what the model was fitted to) or whole clips
+        [n, T, H, W, C] (of extent `size` when given), which are cut on the device first.  ValueError for a preset that is not
+        3-D."""
+        if self.data_dim != 3:
+            raise ValueError("report_frames: frames are axis 0 of a 3-D preset, this one has %d axes" % self.data_dim)
+        report = self.report_regions if y_or_signals.dim() == 3 else self.report_regions_signals
+        by_frame = report(x, y_or_signals, region="frame", size=size, sample_format=sample_format)      # [n, T, 1, 1]
+        return by_frame.reshape(by_frame.shape[:2])
 
     @staticmethod
     def _ssim_format(who, sigs, sample_format):

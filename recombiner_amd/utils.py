@@ -461,6 +461,91 @@ def metric_device(y_true, y_pred, dataset, layout=None, size=None, sample_format
 
 
 # ---------------------------------------------------------------------------------------------
+# the same figures by region -- per frame, per patch, per tile (rcb_recon_regions, include/rcb.h N4 417)
+# ---------------------------------------------------------------------------------------------
+def region_grid(extent, region):
+    """boxes per axis when `extent` is tiled by boxes of `region` positions: nr[i] = ceil(extent[i] / region[i]); the boxes on the
+    far edge are smaller.  ValueError for axes that do not match or an entry below 1."""
+    extent, region = [int(v) for v in extent], [int(v) for v in region]
+    if len(extent) != len(region) or not extent or min(extent) < 1 or min(region) < 1:
+        raise ValueError("region_grid: extent %r and region %r (as many positive entries each)" % (extent, region))
+    return tuple(-(-e // r) for e, r in zip(extent, region))
+
+
+def region_counts(extent, region, channels):
+    """int64 [*nr]: the elements of every box, prod(box_i) * channels -- what a region's sum is divided by.  Host arithmetic."""
+    nr = region_grid(extent, region)
+    counts = np.full(nr, int(channels), dtype=np.int64)
+    for i, (e, r, n) in enumerate(zip(extent, region, nr)):
+        e, r = int(e), int(r)
+        box = np.minimum(r, e - np.arange(n, dtype=np.int64) * r)
+        counts = counts * box.reshape([-1 if j == i else 1 for j in range(len(nr))])
+    return counts
+
+
+def region_of(config_or_layout, by):
+    """The box of the usual regions of a preset (a config dict) or an ops.PeLayout, one entry per spatial axis:
+      "patch"   patch_size: one figure per patch of the codec;
+      "frame"   (1, G1, G2), 3-D only: one figure per frame of a clip -- the video convention is the mean of these per-frame PSNRs;
+      "row"     one position of axis 0 and the whole of the others;
+      a tuple of ints is taken as it is (one entry per axis, each >= 1)."""
+    if isinstance(config_or_layout, dict):
+        pn, ps = preset_grid(config_or_layout)
+    else:
+        pn, ps = list(config_or_layout.patch_nums), list(config_or_layout.patch_size)
+    grid = [a * b for a, b in zip(pn, ps)]
+    if isinstance(by, str):
+        if by == "patch":
+            return tuple(ps)
+        if by == "frame":
+            if len(grid) != 3:
+                raise ValueError("region_of: frames are the positions of axis 0 of a 3-D signal, this one has %d axes" % len(grid))
+            return (1, grid[1], grid[2])
+        if by == "row":
+            return (1, *grid[1:])
+        raise ValueError("region_of: %r ('patch', 'frame', 'row' or a tuple of ints)" % (by,))
+    box = tuple(int(v) for v in by)
+    if len(box) != len(grid) or min(box) < 1:
+        raise ValueError("region_of: a box of %r for a signal of %d axes (one entry >= 1 per axis)" % (box, len(grid)))
+    return box
+
+
+def metric_regions_from_sse(sse_r, counts, dataset):
+    """Per-region figures [n_data, *nr] in fp64 from the sums `sse_r` [n_data, *nr] (ops.recon_regions) and the element counts
+    [*nr] (region_counts): PSNR = -10 log10(sse / n) for cifar / kodak / video / audio, RMSD = 25 sqrt(3 sse / n) for protein.
+    Every region gets its own figure, whatever the dataset's batch convention.  NaN passes through; a zero error gives inf."""
+    if dataset not in METRIC_ROUNDS:
+        raise ValueError(dataset)
+    sse_r = np.asarray(sse_r, dtype=np.float64)
+    counts = np.asarray(counts, dtype=np.float64)
+    if sse_r.ndim < 1 or tuple(sse_r.shape[1:]) != tuple(counts.shape):
+        raise ValueError("metric_regions_from_sse: sums of shape %r, counts of shape %r" % (sse_r.shape, counts.shape))
+    mse = sse_r / counts[None]
+    if dataset == "protein":
+        return 25.0 * np.sqrt(3.0 * mse)
+    with np.errstate(divide="ignore"):
+        return -10.0 * np.log10(mse)
+
+
+def metric_regions_device(y_true, y_pred, dataset, layout, region, size=None, sample_format=None):
+    """The dataset's figure per region of every signal, fp64 [n_data, *nr], for GPU tensors [N, P, C] without copying them to the
+    host: one pass of rcb_recon_regions (rounding to 8 bits where the dataset's metric does, as metric_device), then only the
+    per-region sums are read back.  layout: the signals' ops.PeLayout (patch_nums of ones when unpatched); region: one int per
+    axis (region_of); size: the signals' real extent inside the grid -- the regions tile it, and padding belongs to none;
+    sample_format: the lattice the reconstruction is rounded to instead of the dataset's choice."""
+    from . import ops
+    if dataset not in METRIC_ROUNDS:
+        raise ValueError(dataset)
+    mode = ops.RECON_8BIT if METRIC_ROUNDS[dataset] else ops.RECON_RAW
+    y_pred = y_pred.detach().to(torch.float32).contiguous()
+    y_true = y_true.detach().to(device=y_pred.device, dtype=torch.float32).contiguous()
+    extent = [int(v) for v in size] if size is not None else [a * b for a, b in zip(layout.patch_nums, layout.patch_size)]
+    counts = region_counts(extent, region, y_pred.shape[-1])
+    sse_r, _n_bad_r = ops.recon_regions(y_pred, y_true, layout, region, mode=mode, size=size, sample_format=sample_format)
+    return metric_regions_from_sse(sse_r.cpu().numpy(), counts, dataset)
+
+
+# ---------------------------------------------------------------------------------------------
 # SSIM / MS-SSIM of delivered integers against the source's, from the exact fixed-point sums of rcb_ssim (include/rcb.h, N4 414)
 # ---------------------------------------------------------------------------------------------
 SSIM_TAPS = 11

@@ -333,3 +333,25 @@ case("refusal recon_finish_ragged_into buffer",
 case("refusal recon_finish_ragged_into overlap",
      lambda: ops.recon_finish_ragged_into(yz, None, lay, [(8, 8), (8, 8)], [(0, 24, 3), (100, 24, 3)], 384, ops.RECON_8BIT, 0,
                                           q_buf=torch.empty(384, device=DEV, dtype=torch.uint8)))
+
+# ---- N4 (417), the squared error by region: recon_regions ---------------------------------------------------------------------
+# the quad path (runs, box rows and origins on 4-element boundaries: C = 4) and the element path (C = 3), with and without a
+# size, a box that straddles patches, one that exceeds the extent, every format, by mode, no target, into `out`
+for cname, Cc in (("quad", 4), ("elem", 3)):
+    rng = np.random.RandomState(60 + Cc)
+    yr = torch.from_numpy(rng.rand(8, 16, Cc).astype(np.float32)).to(DEV)
+    recr = n4_recon(rng, yr)
+    for fname, fmt in N4_FORMATS:
+        case(f"recon_regions {cname} patch {fname}", lambda: ops.recon_regions(recr, yr, lay, (4, 4), sample_format=fmt))
+        case(f"recon_regions {cname} 3x2 size 5x7 {fname}", lambda: ops.recon_regions(recr, yr, lay, (3, 2), size=(5, 7), sample_format=fmt))
+    case(f"recon_regions {cname} 2x2 8bit by mode", lambda: ops.recon_regions(recr, yr, lay, (2, 2)))
+    case(f"recon_regions {cname} row raw by mode", lambda: ops.recon_regions(recr, yr, lay, (1, 100), mode=ops.RECON_RAW))
+    case(f"recon_regions {cname} no target", lambda: ops.recon_regions(recr, None, lay, (4, 4), size=(5, 7)))
+    case(f"recon_regions {cname} into out",
+         lambda: ops.recon_regions(recr, yr, lay, (4, 4), out=(torch.zeros(2, 2, 2, device=DEV, dtype=torch.float64),
+                                                               torch.zeros(2, 2, 2, device=DEV, dtype=torch.int32))))
+case("refusal recon_regions no layout", lambda: ops.recon_regions(yz, yz, None, (4, 4)))
+case("refusal recon_regions region axes", lambda: ops.recon_regions(yz, yz, lay, (4,)))
+case("refusal recon_regions region 0", lambda: ops.recon_regions(yz, yz, lay, (4, 0)))
+case("refusal recon_regions size above the grid", lambda: ops.recon_regions(yz, yz, lay, (4, 4), size=(9, 8)))
+case("refusal recon_regions out", lambda: ops.recon_regions(yz, yz, lay, (4, 4), out=(torch.empty(2, 2, device=DEV, dtype=torch.float64), None)))
