@@ -27,9 +27,9 @@ extern "C" {
  * 409: rcb_recon_finish; 410: rcb_signal_patch; 411: rcb_signal_patch_pad, rcb_recon_finish_crop; 412: rcb_signal_patch_fmt,
  * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged; 414: rcb_ssim_workspace_bytes, rcb_ssim;
  * 415: rcb_ssim_list_table_bytes, rcb_ssim_list_workspace_bytes, rcb_ssim_list_plan, rcb_ssim_list;
- * 416: rcb_resize_taps, rcb_resize_table_bytes, rcb_resize; 417: rcb_recon_regions_workspace_bytes, rcb_recon_regions).  A binding compares
- * rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 417
+ * 416: rcb_resize_taps, rcb_resize_table_bytes, rcb_resize; 417: rcb_recon_regions_workspace_bytes, rcb_recon_regions;
+ * 418: rcb_ycc_to_rgb, rcb_rgb_to_ycc, rcb_ycc_sse).  A binding compares rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
+#define RCB_VERSION 418
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -1006,6 +1006,69 @@ int64_t rcb_resize_table_bytes(int32_t H_in, int32_t W_in, int32_t H_out, int32_
 int rcb_resize(const void* src, int64_t src_elems, int32_t kind, int32_t depth, int64_t n, int32_t T, int32_t H_in, int32_t W_in,
                int32_t C, const int64_t* strides, int64_t offset, int32_t H_out, int32_t W_out, void* dst, void* table,
                int64_t table_bytes, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (418): Y'CbCr on the device.  Raw video is planar Y'CbCr 4:2:0 at 8 or 10 bits, and codec comparisons report PSNR per plane
+ * (PSNR-Y, and (6 Y + Cb + Cr) / 8 on 4:2:0 planes) and SSIM on luma; the entries above read and score interleaved RGB only.
+ * rcb_ycc_to_rgb turns planes into the [..][H][W][3] signals rcb_resize / rcb_signal_patch / rcb_ssim take; rcb_rgb_to_ycc forms the
+ * planes of an RGB signal; rcb_ycc_sse gives the squared error of two RGB signals per plane, only the sums leaving the device.
+ *
+ * Samples: kind 0 (uint8, depth 0, L = 255) or kind 2 (16-bit unsigned words at `depth` b, 9 <= b <= 16, L = 2^b - 1; a stored
+ * value above L goes in as it is), as rcb_ssim.  Kinds 1 and 3 are refused.
+ * Subsampling `ss`: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0.  A frame has H x W luma positions, any H, W >= 1 (odd sizes are legal), and
+ * chroma planes of Hc x Wc with Hc = ss == 2 ? (H + 1) / 2 : H, Wc = ss ? (W + 1) / 2 : W.
+ * The device evaluates no colour constant: the caller passes the matrix (HOST double[9], row-major) and the offsets (HOST
+ * double[3]); utils.ycc_matrix forms them for BT.601 / 709 / 2020 at full or limited range, as win, c1, c2 are formed for rcb_ssim.
+ * Every product and sum below is ONE IEEE fp64 operation, no contraction, in the order the parentheses give.
+ *   Q(v) = (int)rint(fmin(fmax(v, 0), L)), half to even.  The clamp is to [0, L] only: the foot- and headroom of a limited range
+ *          are not clamped away.
+ * Forward (RGB -> Y'CbCr), r, g, b the samples of a position as exact fp64 values, plane k = 0 (Y), 1 (Cb), 2 (Cr):
+ *   p_k(y, x) = (m[k][0] r + m[k][1] g) + m[k][2] b
+ *   Y(y, x)      = Q(p_0(y, x) + off[0])
+ *   4:4:4  C_k(y, x) = Q(p_k(y, x) + off[k])
+ *   4:2:2  C_k(y, j) = Q((p_k(y, min(2j, W-1)) + p_k(y, min(2j+1, W-1))) * 0.5 + off[k])
+ *   4:2:0  C_k(i, j) = Q(((p00 + p01) + (p10 + p11)) * 0.25 + off[k]),  p_ab = p_k(min(2i+a, H-1), min(2j+b, W-1))
+ *   -- the mean is taken over UNROUNDED fp64 values, rows and columns clipped to the extent (edge replication on the far side),
+ *   and the result is rounded ONCE.
+ * Inverse (Y'CbCr -> RGB), channel k = 0 (R), 1 (G), 2 (B), Y, Cb, Cr the samples as exact fp64 values:
+ *   v_k = (n[k][0] (Y - o[0]) + n[k][1] (Cb - o[1])) + n[k][2] (Cr - o[2]),  q_k = Q(v_k)
+ *   -- the subtractions are exact; a zero coefficient is multiplied like any other.  Position (y, x) reads the chroma sample
+ *   (ss == 2 ? y >> 1 : y, ss ? x >> 1 : x): replication.  A smoother chroma upsampling is rcb_resize of the chroma planes followed
+ *   by this entry at 4:4:4 (utils.ycc_to_rgb_device, chroma="bilinear").
+ *
+ * rcb_ycc_to_rgb: py, pcb, pcr are the first samples of the three planes of n signals of T frames (T = 1: images); each plane has
+ *   its own ELEMENT strides {signal, frame, row, column} (HOST int64[4], >= 0) and its own element count elems[k] (HOST int64[3],
+ *   counted from the plane's pointer): the farthest element read, (n - 1) s_0 + (T - 1) s_1 + (rows - 1) s_2 + (columns - 1) s_3,
+ *   must lie below it (checked on the host, as rcb_resize does): every read is inside.  One rule covers I420 / YV12 in one buffer
+ *   (three views), NV12 / P010-style interleaved chroma (column stride 2) and a window of a larger frame.  `inv` is n, `o` is o.
+ *   dst: contiguous [n][T][H][W][3] of the source's type.
+ * rcb_rgb_to_ycc: src holds RGB through ELEMENT strides {signal, frame, row, column, channel} (HOST int64[5], >= 0), `offset`
+ *   (>= 0) and src_elems -- the rule of rcb_resize: channel-first, transposed, windowed and broadcast sources; the farthest element
+ *   read lies below src_elems.  oy [n][T][H][W] and ocb, ocr [n][T][Hc][Wc], contiguous, of the source's type; each is nullable, at
+ *   least one is not.  oy alone is the luma plane rcb_ssim scores with C = 1.
+ * rcb_ycc_sse: a, b are two RGB operands of the same n, T, H, W, each with its own strides, offset and element count as above.
+ *   sse [n][T][3] int64, WRITTEN (not accumulated into): per frame and plane the sum of (qa - qb)^2 over the integers
+ *   rcb_rgb_to_ycc delivers for a and for b -- H W terms for Y, Hc Wc for Cb and for Cr.  A frame has at most 2^26 positions and
+ *   a term is < 2^32: a sum is < 2^58.  64-bit integer atomics after a memset of `sse` on the stream, one atomic per workgroup and
+ *   plane; integer sums have no order, so a frame's row is bitwise the same alone, in any batch, in any batch order and from run
+ *   to run.  utils.psnr_ycc_from_sse forms the figures.
+ * A thread owns 2 x 4 positions (whole chroma blocks), a workgroup of 256 threads 16 x 128 positions of one frame.  uint8 RGB with
+ * channel stride 1, column stride 3 and every row on a 4-byte boundary is read as three dwords per tile row (and dst / oy written
+ * as dwords when W is a multiple of 4); any other layout goes element by element, with the same bits.  The entry decides.
+ * No table, no workspace, nothing uploaded and no synchronisation: all three entries can be graph-captured.  n = 0 succeeds and
+ * launches nothing.  Refused (RCB_ERR_*), nothing launched: a kind other than 0 / 2, a depth outside 9 .. 16 for kind 2 or non-zero
+ * for kind 0; ss outside 0 .. 2; H, W or T below 1; more than 2^26 positions per frame; a negative stride or offset; a reach past an
+ * element count; a null operand, matrix, offsets, strides or element-count array; rcb_rgb_to_ycc with all three outputs null;
+ * more than 2^31 - 1 workgroups. */
+int rcb_ycc_to_rgb(const void* py, const void* pcb, const void* pcr, const int64_t* elems, const int64_t* y_strides,
+                   const int64_t* cb_strides, const int64_t* cr_strides, int32_t kind, int32_t depth, int32_t ss, int64_t n, int32_t T,
+                   int32_t H, int32_t W, const double* inv, const double* o, void* dst, rcb_stream_t stream);
+int rcb_rgb_to_ycc(const void* src, int64_t src_elems, const int64_t* strides, int64_t offset, int32_t kind, int32_t depth, int32_t ss,
+                   int64_t n, int32_t T, int32_t H, int32_t W, const double* m, const double* off, void* oy, void* ocb, void* ocr,
+                   rcb_stream_t stream);
+int rcb_ycc_sse(const void* a, int64_t a_elems, const int64_t* a_strides, int64_t a_offset, const void* b, int64_t b_elems,
+                const int64_t* b_strides, int64_t b_offset, int32_t kind, int32_t depth, int32_t ss, int64_t n, int32_t T, int32_t H,
+                int32_t W, const double* m, const double* off, int64_t* sse, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -349,6 +349,44 @@ def compress_resized(config, dataset, checkpoint, signals, crop=None, channels_f
     return (*out, resized, by_region)
 
 
+def compress_ycc(config, dataset, checkpoint, planes, layout_or_subsampling, matrix, crop=None, chroma="replicate", sample_format=None,
+                 **kw):
+    """`compress_resized` on Y'CbCr sources -- raw video and image planes as decoders and .yuv files deliver them -- converted to
+    RGB on the device first (utils.ycc_to_rgb_device; rcb_ycc_to_rgb), for the 2-D and 3-D presets of three channels.
+    planes: (y, cb, cr) tensors [n, (T,) H, W] / [n, (T,) Hc, Wc] of any strides with layout_or_subsampling = 0 / 1 / 2 (4:4:4,
+    4:2:2, 4:2:0), or ONE flat tensor of raw frames with a layout name of utils.yuv_planes ("i420", "yv12", "nv12", "yuv422p",
+    "yuv444p") and size=(n, T, H, W) among the keywords (T = 1 for a 2-D preset).  matrix: utils.ycc_matrix(...); chroma:
+    "replicate" or "bilinear" (utils.ycc_to_rgb_device); crop: compress_resized's.
+    -> what compress_resized returns (the resized RGB source last), plus one more element: the per-plane PSNR of the decoded
+    integers against that source in Y'CbCr at the source's subsampling -- the model's report_ycc, fp64 [n, 4] (2-D), or
+    report_ycc_frames, fp64 [n, T, 4] (3-D).  Every other argument is `compress`'s."""
+    from . import utils
+    device = kw.get("device", "cuda")
+    dd = config["data_dim"]
+    if dd not in (2, 3):
+        raise ValueError("compress_ycc: presets of data_dim 2 and 3 take Y'CbCr sources, not %d" % dd)
+    size = kw.pop("size", None)
+    if isinstance(layout_or_subsampling, str):
+        if size is None or len(size) != 4:
+            raise ValueError("compress_ycc: a flat buffer of %r frames needs size=(n, T, H, W)" % (layout_or_subsampling,))
+        (flat,) = _signal_views("compress_ycc", [planes], sample_format, device)
+        views, ss = utils.yuv_planes(flat, *size, layout_or_subsampling, sample_format=sample_format)
+        if dd == 2:
+            if int(size[1]) != 1:
+                raise ValueError("compress_ycc: a 2-D preset takes images: T = 1 in size, got %d" % int(size[1]))
+            views = tuple(v[:, 0] for v in views)
+    else:
+        if size is not None:
+            raise ValueError("compress_ycc: size= goes with a layout name; three planes carry their own shape")
+        views, ss = tuple(_signal_views("compress_ycc", list(planes), sample_format, device)), int(layout_or_subsampling)
+    rgb = utils.ycc_to_rgb_device(views, matrix, ss, chroma=chroma, sample_format=sample_format)
+    out = compress_resized(config, dataset, checkpoint, rgb, crop=crop, sample_format=sample_format, **kw)
+    model, resized = out[1], out[-1] if kw.get("regions") is None else out[-2]
+    n_rows = resized.shape[0] * int(np.prod(utils.preset_grid(config)[0]))
+    report = model.report_ycc if dd == 2 else model.report_ycc_frames
+    return (*out, report(_default_x(kw.get("x"), config, device, n_rows), resized, matrix, subsampling=ss, sample_format=sample_format))
+
+
 def compress_signals_any(config, dataset, checkpoint, signals, x=None, channels_first=False, bitstream_path=None,
                          sample_format=None, regions=None, **kw):
     """`compress_signals` for signals of ANY size that the preset can be fitted to: `signals` is [n, *size, C] (or [n, C, *size]

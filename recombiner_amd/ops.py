@@ -1731,6 +1731,137 @@ def resize(src, size, sample_format=None, out=None):
     return out
 
 
+
+# ---------------------------------------------------------------------------------------------------
+# N4 (418): Y'CbCr on the device (rcb_ycc_to_rgb, rcb_rgb_to_ycc, rcb_ycc_sse)
+# ---------------------------------------------------------------------------------------------------
+YCC_MAX_POSITIONS = 1 << 26
+
+
+def _ycc_rule(what, tensors, matrix, subsampling, sample_format):
+    """the checks the three Y'CbCr wrappers make of their operands and of the matrix -> (kind, depth, ss)"""
+    kind, depth = _ssim_operand_rule(what, tensors, sample_format)
+    if not all(hasattr(matrix, k) for k in ("m", "off", "n", "o")):
+        raise ValueError(f"{what}: matrix must be what utils.ycc_matrix returns (m, off, n, o)")
+    fmt = getattr(matrix, "sample_format", None)
+    if fmt is not None and kind in (SampleFormat.U8, SampleFormat.U16) and fmt != SampleFormat(kind, depth):
+        raise ValueError(f"{what}: the matrix was formed for {fmt!r}, the samples are {SampleFormat(kind, depth)!r}")
+    return kind, depth, int(subsampling)
+
+
+def _ycc_chroma_size(H, W, ss):
+    return ((H + 1) // 2 if ss == 2 else H), ((W + 1) // 2 if ss else W)
+
+
+def _ycc_fits(ss, n, T, H, W):
+    """whether outputs of this shape can be allocated at all (a refused shape: one-element outputs, and the library says why)"""
+    return 0 <= ss <= 2 and n >= 0 and min(T, H, W) >= 1 and H * W <= YCC_MAX_POSITIONS
+
+
+def _f64_ptr(values, count):
+    a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    if a.size != count:
+        raise ValueError(f"{count} fp64 values expected, got {a.size}")
+    return a, _np_ptr(a)
+
+
+def _rgb_operand(what, name, t):
+    """an RGB operand [n, H, W, 3] or [n, T, H, W, 3] with any strides -> (storage address, elements, strides int64[5], offset,
+    (n, T, H, W), clip)"""
+    if t.dim() not in (4, 5) or t.shape[-1] != 3:
+        raise RcbError(f"{what}: {name} {tuple(t.shape)} must be [n, H, W, 3] or [n, T, H, W, 3]: three channels needed")
+    clip = t.dim() == 5
+    st = [int(v) for v in t.stride()]
+    strides = (C.c_int64 * 5)(st[0], st[1] if clip else 0, *st[-3:])
+    store = t.untyped_storage()
+    shape = (int(t.shape[0]), int(t.shape[1]) if clip else 1, int(t.shape[-3]), int(t.shape[-2]))
+    return C.c_void_p(store.data_ptr()), store.nbytes() // t.element_size(), strides, int(t.storage_offset()), shape, clip
+
+
+def ycc_to_rgb(y, cb, cr, matrix, subsampling, sample_format=None, out=None):
+    """Planar Y'CbCr on the GPU -> interleaved RGB [n, H, W, 3] (or [n, T, H, W, 3] for clips), a contiguous tensor of the source's
+    dtype: what ops.resize, signal_patch and ssim_sums take (rcb_ycc_to_rgb; the definition is include/rcb.h's: fp64, no
+    contraction, ONE rounding, chroma replicated).  y: [n, H, W] or [n, T, H, W]; cb, cr: the same with the chroma size of
+    `subsampling` (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0; Hc = (H + 1) // 2, Wc = (W + 1) // 2 where halved; odd sizes are legal).  The
+    planes are uint8, or a 16-bit dtype with sample_format=utils.SampleFormat.u16(depth), with ANY strides: three views of one
+    I420 buffer, interleaved NV12 chroma (column stride 2), a window of a larger frame (utils.yuv_planes); nothing is copied.
+    matrix: utils.ycc_matrix(...); its inverse n, o is used.  out: optional preallocated contiguous result."""
+    what = "ycc_to_rgb"
+    kind, depth, ss = _ycc_rule(what, [y, cb, cr], matrix, subsampling, sample_format)
+    if y.dim() not in (3, 4) or cb.dim() != y.dim() or cr.dim() != y.dim():
+        raise RcbError(f"{what}: planes {tuple(y.shape)}, {tuple(cb.shape)}, {tuple(cr.shape)} must be [n, H, W] or [n, T, H, W]")
+    clip = y.dim() == 4
+    n, T = int(y.shape[0]), int(y.shape[1]) if clip else 1
+    H, W = int(y.shape[-2]), int(y.shape[-1])
+    fits = _ycc_fits(ss, n, T, H, W)
+    if fits:
+        want = tuple(y.shape[:-2]) + _ycc_chroma_size(H, W, ss)
+        if tuple(cb.shape) != want or tuple(cr.shape) != want:
+            raise RcbError(f"{what}: chroma planes {tuple(cb.shape)}, {tuple(cr.shape)}; {want} expected for Y {tuple(y.shape)} at "
+                           f"subsampling {ss}")
+    shape = (n, T, H, W, 3) if clip else (n, H, W, 3)
+    if out is None:
+        out = torch.empty(shape if fits else (1,), device=y.device, dtype=y.dtype)
+    elif tuple(out.shape) != shape or out.dtype != y.dtype or out.device != y.device or not out.is_contiguous():
+        raise RcbError(f"{what}: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {y.dtype} on the "
+                       "device of y")
+    elems, strides = [], []
+    for t in (y, cb, cr):
+        store = t.untyped_storage()
+        elems.append((store.data_ptr() + store.nbytes() - t.data_ptr()) // t.element_size())
+        st = [int(v) for v in t.stride()]
+        strides.append((C.c_int64 * 4)(st[0], st[1] if clip else 0, st[-2], st[-1]))
+    _n, n_ptr = _f64_ptr(matrix.n, 9)
+    _o, o_ptr = _f64_ptr(matrix.o, 3)
+    _launch("rcb_ycc_to_rgb", C.c_void_p(y.data_ptr()), C.c_void_p(cb.data_ptr()), C.c_void_p(cr.data_ptr()), (C.c_int64 * 3)(*elems),
+            *strides, kind, depth, ss, n, T, H, W, n_ptr, o_ptr, C.c_void_p(out.data_ptr()))
+    return out
+
+
+def rgb_to_ycc(rgb, matrix, subsampling, sample_format=None, want=("y", "cb", "cr")):
+    """Interleaved RGB on the GPU -> the planes named in `want`, in that order, as a tuple of contiguous tensors of the source's
+    dtype: "y" [n, (T,) H, W], "cb" / "cr" [n, (T,) Hc, Wc] (rcb_rgb_to_ycc; include/rcb.h: fp64, no contraction, the chroma mean
+    over UNROUNDED values with the far edge replicated, ONE rounding).  rgb: [n, H, W, 3] or [n, T, H, W, 3], uint8 or 16-bit with
+    sample_format=, ANY strides and storage offset (channel-first, transposed, windowed, broadcast: ops.resize's rule).
+    want=("y",) is the luma plane ssim_sums scores as [n, H, W, 1]."""
+    what = "rgb_to_ycc"
+    kind, depth, ss = _ycc_rule(what, [rgb], matrix, subsampling, sample_format)
+    want = tuple(want)
+    if not want or any(w not in ("y", "cb", "cr") for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"{what}: want {want!r} names planes among 'y', 'cb', 'cr', each once, at least one")
+    base, elems, strides, offset, (n, T, H, W), clip = _rgb_operand(what, "rgb", rgb)
+    fits = _ycc_fits(ss, n, T, H, W)
+    lead = (n, T) if clip else (n,)
+    sizes = {"y": (H, W), "cb": _ycc_chroma_size(H, W, ss), "cr": _ycc_chroma_size(H, W, ss)}
+    planes = {w: torch.empty(lead + sizes[w] if fits else (1,), device=rgb.device, dtype=rgb.dtype) for w in want}
+    _m, m_ptr = _f64_ptr(matrix.m, 9)
+    _off, off_ptr = _f64_ptr(matrix.off, 3)
+    _launch("rcb_rgb_to_ycc", base, elems, strides, offset, kind, depth, ss, n, T, H, W, m_ptr, off_ptr,
+            *(C.c_void_p(planes[w].data_ptr()) if w in planes else C.c_void_p(0) for w in ("y", "cb", "cr")))
+    return tuple(planes[w] for w in want)
+
+
+def ycc_sse(a, b, matrix, subsampling, sample_format=None):
+    """The squared error of two RGB signals PER PLANE of their Y'CbCr form, on the GPU: int64 [n, T, 3] = {Y, Cb, Cr} per frame for
+    clips a, b [n, T, H, W, 3], [n, 3] for images [n, H, W, 3] (rcb_ycc_sse): the sum of (qa - qb)^2 over the integers rgb_to_ycc
+    delivers for a and for b -- H W terms for Y, Hc Wc per chroma plane.  Integer sums: bitwise the same for a frame alone, in any
+    batch and from run to run; no workspace and no synchronisation (graph capture works).  a, b: any strides, each its own.
+    utils.psnr_ycc_from_sse turns the sums into PSNR-Y / Cb / Cr and (6 Y + Cb + Cr) / 8."""
+    what = "ycc_sse"
+    kind, depth, ss = _ycc_rule(what, [a, b], matrix, subsampling, sample_format)
+    if tuple(a.shape) != tuple(b.shape):
+        raise RcbError(f"{what}: a {tuple(a.shape)} and b {tuple(b.shape)} must have one shape")
+    a_base, a_elems, a_st, a_off, (n, T, H, W), clip = _rgb_operand(what, "a", a)
+    b_base, b_elems, b_st, b_off, _, _ = _rgb_operand(what, "b", b)
+    fits = _ycc_fits(ss, n, T, H, W)
+    sse = torch.empty((n, T, 3) if fits else (1,), device=a.device, dtype=torch.int64)
+    _m, m_ptr = _f64_ptr(matrix.m, 9)
+    _off, off_ptr = _f64_ptr(matrix.off, 3)
+    _launch("rcb_ycc_sse", a_base, a_elems, a_st, a_off, b_base, b_elems, b_st, b_off, kind, depth, ss, n, T, H, W, m_ptr, off_ptr,
+            ptr(sse, torch.int64))
+    return sse if clip else sse.view(n, 3)
+
+
 def _win_geo(shape):
     nd = len(shape) - 2
     if nd < 1 or nd > 3 or shape[-1] % 8:

@@ -22,7 +22,7 @@ from .ops import LevelSpec, SirenMeta
 from .upsample_fast import (hip_path_supported, tiled_2d_preferred, phase_form_preferred, phase_module,
                             stitched2d_module, upsample_cifar_hip)
 from .utils import SampleFormat, count_net_params, hierarchy_row_maps, map_lpe_to_inr_inputs, metric_device, ssim_device, ssim_frames_device
-from .utils import metric_regions_device, region_of
+from .utils import metric_regions_device, region_of, ycc_device, ycc_frames_device
 from .utils import map_hierarchical_model_to_int_weights  # noqa: F401  (module-level name, as upstream imports it)
 
 
@@ -290,6 +290,60 @@ class InrGeometry:
             y_pred = self.predict(x.to(dev)).detach().to(torch.float32).contiguous()
         q, _, _, _ = ops.recon_finish(y_pred, layout=layout, size=size, sample_format=fmt, want_int=True)
         return ssim_frames_device(q, signals.to(dev), sample_format=fmt, multiscale=multiscale)
+
+
+    def _ycc_integers(self, who, x, signals, size, sample_format, frames):
+        """what the Y'CbCr reports share: the refusals of report_ssim plus "three channels needed", then predict and round to the
+        format's integers at the signals' size -> (the delivered integers, the source on the device, the format)"""
+        dd = 3 if frames else 2
+        if self.data_dim != dd:
+            raise ValueError("%s: defined for %d-D presets, this one has %d axes" % (who, dd, self.data_dim))
+        fmt = self._ssim_format(who, [signals], sample_format)
+        if self.dims[-1] != 3:
+            raise ValueError("%s: three channels needed (R, G, B), this preset has %d" % (who, self.dims[-1]))
+        layout = self.signal_layout()
+        grid = tuple(n * s for n, s in zip(layout.patch_nums, layout.patch_size))
+        extent = tuple(int(v) for v in size) if size is not None else grid
+        want = extent + (3,)
+        if len(extent) != dd or tuple(signals.shape[1:]) != want:
+            raise ValueError("%s: signals of shape %r, expected %r" % (who, tuple(signals.shape[1:]), want))
+        dev = self.loc.device
+        with torch.no_grad():
+            y_pred = self.predict(x.to(dev)).detach().to(torch.float32).contiguous()
+        q, _, _, _ = ops.recon_finish(y_pred, layout=layout, size=size, sample_format=fmt, want_int=True)
+        return q, signals.to(dev), fmt
+
+    def report_ycc(self, x, signals, matrix, subsampling=2, size=None, sample_format=None):
+        """PSNR per plane of the Y'CbCr form of the images this model delivers against the whole source `signals`, fp64 [n, 4] =
+        {PSNR-Y, PSNR-Cb, PSNR-Cr, (6 Y + Cb + Cr) / 8} -- the figures of the video and image codec comparisons (the model with
+        `predict`, as `report`; 2-D presets of three channels): predict, round to the format's integers
+        (ops.recon_finish(want_int=True, size=)), then ONE rcb_ycc_sse call against the source's integers (utils.ycc_device; the
+        definition is include/rcb.h's); only the sums leave the device.
+        signals: [n, H, W, 3] integer RGB images on the model's grid (size None) or of extent `size` inside it, any strides.
+        matrix: utils.ycc_matrix(...); subsampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (the planes both sides are brought to).
+        ValueError, with the reason: what report_ssim refuses of its sources, a preset that is not 2-D, three channels needed."""
+        q, src, fmt = self._ycc_integers("report_ycc", x, signals, size, sample_format, frames=False)
+        return ycc_device(q, src, matrix, subsampling, sample_format=fmt)
+
+    def report_ycc_frames(self, x, signals, matrix, subsampling=2, size=None, sample_format=None):
+        """`report_ycc` per FRAME of the clips a 3-D preset delivers, fp64 [n, T, 4]; the caller averages (the video convention
+        is the mean over the frames).  signals: [n, T, H, W, 3] integer clips on the model's grid or of extent `size` = (T, H, W)."""
+        q, src, fmt = self._ycc_integers("report_ycc_frames", x, signals, size, sample_format, frames=True)
+        return ycc_frames_device(q, src, matrix, subsampling, sample_format=fmt)
+
+    def report_ssim_luma(self, x, signals, matrix, size=None, sample_format=None, multiscale=False):
+        """SSIM (with `multiscale`: MS-SSIM) on LUMA -- what Wang et al. define it on -- of the images this model delivers against
+        the source, fp64 [n]: both sides go through ops.rgb_to_ycc(want=("y",)) and the existing utils.ssim_device scores the
+        planes as [n, H, W, 1].  Arguments and refusals: report_ycc's and report_ssim's size rule (11, multiscale 176, per side)."""
+        q, src, fmt = self._ycc_integers("report_ssim_luma", x, signals, size, sample_format, frames=False)
+        (ya,), (yb,) = (ops.rgb_to_ycc(t, matrix, 0, sample_format=fmt, want=("y",)) for t in (q, src))
+        return ssim_device(ya.unsqueeze(-1), yb.unsqueeze(-1), sample_format=fmt, multiscale=multiscale)
+
+    def report_ssim_luma_frames(self, x, signals, matrix, size=None, sample_format=None, multiscale=False):
+        """`report_ssim_luma` per FRAME of the clips a 3-D preset delivers, fp64 [n, T] (utils.ssim_frames_device on the luma planes)."""
+        q, src, fmt = self._ycc_integers("report_ssim_luma_frames", x, signals, size, sample_format, frames=True)
+        (ya,), (yb,) = (ops.rgb_to_ycc(t, matrix, 0, sample_format=fmt, want=("y",)) for t in (q, src))
+        return ssim_frames_device(ya.unsqueeze(-1), yb.unsqueeze(-1), sample_format=fmt, multiscale=multiscale)
 
 
 class PriorBNNmodel(nn.Module, InrGeometry):

@@ -742,3 +742,181 @@ def resize_to_preset(config, signals, crop=None, channels_first=False, sample_fo
             raise ValueError("resize_to_preset: crop is (h, w) of the last two spatial axes")
         signals = center_crop(signals, crop, (-3, -2))
     return ops.resize(signals, grid[-2:], sample_format=sample_format)
+
+
+# ---------------------------------------------------------------------------------------------
+# Y'CbCr sources and per-plane scores (include/rcb.h, N4 418)
+# ---------------------------------------------------------------------------------------------
+YCC_STANDARDS = {"bt601": ("0.299", "0.114"), "bt709": ("0.2126", "0.0722"), "bt2020": ("0.2627", "0.0593")}   # (kr, kb)
+YUV_LAYOUTS = {"i420": 2, "yv12": 2, "nv12": 2, "yuv422p": 1, "yuv444p": 0}                                     # -> subsampling
+
+
+class YccMatrix:
+    """What rcb_rgb_to_ycc (m [3, 3], off [3]) and rcb_ycc_to_rgb (n [3, 3], o [3]) take, numpy fp64, with what they were formed
+    for: kr, kb (fractions.Fraction), full_range, sample_format."""
+
+    def __init__(self, m, off, n, o, kr, kb, full_range, sample_format):
+        self.m, self.off, self.n, self.o = m, off, n, o
+        self.kr, self.kb, self.full_range, self.sample_format = kr, kb, full_range, sample_format
+
+    def __repr__(self):
+        return "YccMatrix(kr=%s, kb=%s, %s range, %r)" % (self.kr, self.kb, "full" if self.full_range else "limited", self.sample_format)
+
+
+def _ycc_peak(sample_format, who):
+    fmt = sample_format if sample_format is not None else SampleFormat.u8()
+    if fmt.kind not in (SampleFormat.U8, SampleFormat.U16):
+        raise ValueError("%s: Y'CbCr is defined here for u8 and u16 samples, not %r" % (who, fmt))
+    d = 8 if fmt.kind == SampleFormat.U8 else fmt.depth
+    return fmt, d, (1 << d) - 1
+
+
+def ycc_matrix(standard, full_range=True, sample_format=None):
+    """THE colour constants of the Y'CbCr entries, formed here and nowhere else (the device evaluates none) -> YccMatrix.
+    standard: "bt601", "bt709", "bt2020" (kr, kb the decimal fractions of the recommendations), or a (kr, kb) pair of numbers
+    (a float stands for its exact value), Fractions or decimal strings.  kg = (1 - kr) - kb.  With d the bit depth, L = 2^d - 1:
+      full range     sy = sc = 1,                                     off = o = {0, 2^(d-1), 2^(d-1)}
+      limited range  sy = 219 * 2^(d-8) / L,  sc = 224 * 2^(d-8) / L,  off = o = {16, 128, 128} * 2^(d-8)
+      m = [[kr, kg, kb] * sy,
+           [-kr / (2 (1 - kb)), -kg / (2 (1 - kb)), 1 / 2] * sc,
+           [1 / 2, -kg / (2 (1 - kr)), -kb / (2 (1 - kr))] * sc]
+      n = [[1 / sy, 0, 2 (1 - kr) / sc],                              (the closed forms R = y + 2 (1 - kr) cr, B = y + 2 (1 - kb) cb,
+           [1 / sy, -2 kb (1 - kb) / (kg sc), -2 kr (1 - kr) / (kg sc)],   G = (y - kr R - kb B) / kg; no numeric matrix inverse)
+           [1 / sy, 2 (1 - kb) / sc, 0]]
+    Every coefficient is evaluated in exact rational arithmetic (fractions.Fraction) and rounded to fp64 ONCE, so it is the
+    correctly rounded value of its formula whatever the order of the operations (tests/test_ycc_emul_cpu.py restates them)."""
+    from fractions import Fraction as F
+    fmt, d, L = _ycc_peak(sample_format, "ycc_matrix")
+    if isinstance(standard, str):
+        if standard not in YCC_STANDARDS:
+            raise ValueError("ycc_matrix: standard %r (one of %s, or a (kr, kb) pair)" % (standard, ", ".join(sorted(YCC_STANDARDS))))
+        kr, kb = (F(v) for v in YCC_STANDARDS[standard])
+    else:
+        kr, kb = (F(v) for v in standard)
+    kg = (1 - kr) - kb
+    if not (0 < kr < 1 and 0 < kb < 1 and 0 < kg < 1):
+        raise ValueError("ycc_matrix: kr = %s, kb = %s leave kg = %s (all three lie strictly between 0 and 1)" % (kr, kb, kg))
+    if full_range:
+        sy = sc = F(1)
+        off = [F(0), F(1 << (d - 1)), F(1 << (d - 1))]
+    else:
+        sy, sc = F(219 << (d - 8), L), F(224 << (d - 8), L)
+        off = [F(16 << (d - 8)), F(128 << (d - 8)), F(128 << (d - 8))]
+    half = F(1, 2)
+    m = [[kr * sy, kg * sy, kb * sy],
+         [-kr / (2 * (1 - kb)) * sc, -kg / (2 * (1 - kb)) * sc, half * sc],
+         [half * sc, -kg / (2 * (1 - kr)) * sc, -kb / (2 * (1 - kr)) * sc]]
+    n = [[1 / sy, F(0), 2 * (1 - kr) / sc],
+         [1 / sy, -2 * kb * (1 - kb) / (kg * sc), -2 * kr * (1 - kr) / (kg * sc)],
+         [1 / sy, 2 * (1 - kb) / sc, F(0)]]
+    as64 = lambda rows: np.asarray([[float(v) for v in r] for r in rows], dtype=np.float64)
+    offs = np.asarray([float(v) for v in off], dtype=np.float64)
+    return YccMatrix(as64(m), offs, as64(n), offs.copy(), kr, kb, bool(full_range), fmt)
+
+
+def ycc_chroma_size(H, W, subsampling):
+    """(Hc, Wc) of the chroma planes of an H x W frame: 0 = 4:4:4, 1 = 4:2:2 (Wc = (W + 1) // 2), 2 = 4:2:0 (Hc = (H + 1) // 2 too)"""
+    if subsampling not in (0, 1, 2):
+        raise ValueError("subsampling %r (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0)" % (subsampling,))
+    return ((H + 1) // 2 if subsampling == 2 else H), ((W + 1) // 2 if subsampling else W)
+
+
+def yuv_planes(buffer, n, T, H, W, layout, sample_format=None):
+    """The three planes of n clips of T raw frames in ONE flat tensor, as strided VIEWS (nothing is copied) -> ((y [n, T, H, W],
+    cb, cr [n, T, Hc, Wc]), subsampling): what ops.ycc_to_rgb takes.  A frame holds H W luma samples and then its chroma:
+      "i420"     4:2:0, the Cb plane and then the Cr plane          "yv12"  4:2:0, Cr and then Cb
+      "nv12"     4:2:0, one plane of interleaved Cb Cr pairs (column stride 2; P010-style with SampleFormat.u16)
+      "yuv422p"  4:2:2 planar, Cb and then Cr                        "yuv444p"  4:4:4 planar, Cb and then Cr
+    Frames follow each other without padding, H W + 2 Hc Wc samples each; odd sizes are legal (Hc, Wc round up).  buffer: a 1-D
+    tensor of uint8 samples, or of a 16-bit dtype with sample_format=SampleFormat.u16(depth)."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError("yuv_planes: layout %r (one of %s)" % (layout, ", ".join(sorted(YUV_LAYOUTS))))
+    fmt, _, _ = _ycc_peak(sample_format, "yuv_planes")
+    if buffer.dim() != 1 or not fmt.accepts(buffer.dtype):
+        raise ValueError("yuv_planes: a 1-D tensor of %r samples is needed, got %s %r" % (fmt, buffer.dtype, tuple(buffer.shape)))
+    n, T, H, W = int(n), int(T), int(H), int(W)
+    if min(n, T, H, W) < 1:
+        raise ValueError("yuv_planes: %d clips of %d frames of %d x %d" % (n, T, H, W))
+    ss = YUV_LAYOUTS[layout]
+    Hc, Wc = ycc_chroma_size(H, W, ss)
+    frame = H * W + 2 * Hc * Wc
+    if buffer.numel() < n * T * frame:
+        raise ValueError("yuv_planes: %d samples, %d clips of %d %s frames of %d x %d need %d"
+                         % (buffer.numel(), n, T, layout, H, W, n * T * frame))
+    base = buffer.storage_offset()
+    y = buffer.as_strided((n, T, H, W), (T * frame, frame, W, 1), base)
+    if layout == "nv12":
+        first, second, row, col = H * W, H * W + 1, 2 * Wc, 2
+    else:
+        first, second, row, col = H * W, H * W + Hc * Wc, Wc, 1
+    if layout == "yv12":
+        first, second = second, first
+    cb = buffer.as_strided((n, T, Hc, Wc), (T * frame, frame, row, col), base + first)
+    cr = buffer.as_strided((n, T, Hc, Wc), (T * frame, frame, row, col), base + second)
+    return (y, cb, cr), ss
+
+
+def ycc_to_rgb_device(planes, matrix, subsampling, chroma="replicate", sample_format=None):
+    """Planes (y, cb, cr) on the GPU (ops.ycc_to_rgb's; e.g. yuv_planes's views) -> RGB [n, (T,) H, W, 3] of the source's dtype.
+    chroma: "replicate" -- the entry's own rule, every chroma sample repeated over its block -- or "bilinear": ops.resize of the
+    two chroma planes to H x W (fp64 triangle filter, half-pixel centres: chroma sited at the CENTRE of its block; rounded to the
+    sample lattice once) followed by the entry at 4:4:4.  Other sitings are not offered."""
+    from . import ops
+    y, cb, cr = planes
+    if chroma == "replicate" or subsampling == 0:
+        if chroma not in ("replicate", "bilinear"):
+            raise ValueError("ycc_to_rgb_device: chroma %r ('replicate' or 'bilinear')" % (chroma,))
+        return ops.ycc_to_rgb(y, cb, cr, matrix, subsampling, sample_format=sample_format)
+    if chroma != "bilinear":
+        raise ValueError("ycc_to_rgb_device: chroma %r ('replicate' or 'bilinear')" % (chroma,))
+    size = (int(y.shape[-2]), int(y.shape[-1]))
+    cb, cr = (ops.resize(c.unsqueeze(-1), size, sample_format=sample_format).squeeze(-1) for c in (cb, cr))
+    return ops.ycc_to_rgb(y, cb, cr, matrix, 0, sample_format=sample_format)
+
+
+def psnr_ycc_from_sse(sse, H, W, subsampling, sample_format=None):
+    """rcb_ycc_sse's sums [..., 3] (int64 tensor or array) of H x W frames -> fp64 [..., 4] = {PSNR-Y, PSNR-Cb, PSNR-Cr,
+    (6 Y + Cb + Cr) / 8}, the combined figure of the HM / JVET reports.  Each PSNR is 10 log10(L^2 count / sse), count = H W for Y
+    and Hc Wc for a chroma plane; the numerator is a Python integer and the division the true division of two integers (correctly
+    rounded); sse = 0 gives inf."""
+    import math
+    _, _, L = _ycc_peak(sample_format, "psnr_ycc_from_sse")
+    s = sse.detach().cpu().numpy() if isinstance(sse, torch.Tensor) else np.asarray(sse)
+    if s.ndim < 1 or s.shape[-1] != 3:
+        raise ValueError("psnr_ycc_from_sse: the sums of rcb_ycc_sse are [..., 3], got %r" % (s.shape,))
+    Hc, Wc = ycc_chroma_size(int(H), int(W), int(subsampling))
+    counts = (int(H) * int(W), Hc * Wc, Hc * Wc)
+    out = np.empty(s.shape[:-1] + (4,), dtype=np.float64)
+    flat_in, flat_out = s.reshape(-1, 3), out.reshape(-1, 4)
+    for row, res in zip(flat_in, flat_out):
+        for k in range(3):
+            v = int(row[k])
+            if v < 0:
+                raise ValueError("psnr_ycc_from_sse: a negative sum (%d)" % v)
+            res[k] = math.inf if v == 0 else 10.0 * math.log10((L * L * counts[k]) / v)
+        res[3] = (6.0 * res[0] + res[1] + res[2]) / 8.0
+    return out
+
+
+def ycc_device(a, b, matrix, subsampling=2, sample_format=None):
+    """Per-plane PSNR of integer RGB images a against b in Y'CbCr, fp64 [n, 4] = {Y, Cb, Cr, (6 Y + Cb + Cr) / 8}: a, b [n, H, W, 3]
+    GPU tensors of one integer dtype with ANY strides (ops.ycc_sse); only the sums are read back.  The twin of ssim_device."""
+    from . import ops
+    if a.dim() != 4:
+        raise ValueError("ycc_device: images are [n, H, W, 3], got %d axes" % a.dim())
+    if a.shape[0] == 0:
+        return np.zeros((0, 4), dtype=np.float64)
+    sse = ops.ycc_sse(a, b, matrix, subsampling, sample_format=sample_format)
+    return psnr_ycc_from_sse(sse, a.shape[1], a.shape[2], subsampling, sample_format)
+
+
+def ycc_frames_device(a, b, matrix, subsampling=2, sample_format=None):
+    """`ycc_device` per FRAME of integer clips a, b [n, T, H, W, 3] (any strides), fp64 [n, T, 4], in one call; the caller
+    averages.  The twin of ssim_frames_device."""
+    from . import ops
+    if a.dim() != 5:
+        raise ValueError("ycc_frames_device: clips are [n, T, H, W, 3], got %d axes" % a.dim())
+    if a.shape[0] * a.shape[1] == 0:
+        return np.zeros((int(a.shape[0]), int(a.shape[1]), 4), dtype=np.float64)
+    sse = ops.ycc_sse(a, b, matrix, subsampling, sample_format=sample_format)
+    return psnr_ycc_from_sse(sse, a.shape[2], a.shape[3], subsampling, sample_format)
