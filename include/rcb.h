@@ -7,7 +7,7 @@
  * (file:line relative to the reference root).  Conventions:
  *   - plain device pointers + explicit sizes; the caller (PyTorch, or any HIP host) allocates
  *     every buffer including outputs; nothing is allocated, freed or synchronised inside (but for the one table upload of the
- *     two per-signal entries of 413, of the list entry of 415 and of the resize entry of 416, which say so);
+ *     two per-signal entries of 413, of the list entry of 415, of the resize entry of 416 and of the resample entry of 419, which say so);
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it;
  *   - return value: 0 = ok, < 0 = argument/shape error (RCB_ERR_*), > 0 = hipError_t;
  *   - no global mutable state besides the thread-local last-error string; re-entrant per stream;
@@ -28,8 +28,9 @@ extern "C" {
  * rcb_recon_finish_fmt; 413: rcb_ragged_table_bytes, rcb_signal_patch_ragged, rcb_recon_finish_ragged; 414: rcb_ssim_workspace_bytes, rcb_ssim;
  * 415: rcb_ssim_list_table_bytes, rcb_ssim_list_workspace_bytes, rcb_ssim_list_plan, rcb_ssim_list;
  * 416: rcb_resize_taps, rcb_resize_table_bytes, rcb_resize; 417: rcb_recon_regions_workspace_bytes, rcb_recon_regions;
- * 418: rcb_ycc_to_rgb, rcb_rgb_to_ycc, rcb_ycc_sse).  A binding compares rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
-#define RCB_VERSION 418
+ * 418: rcb_ycc_to_rgb, rcb_rgb_to_ycc, rcb_ycc_sse; 419: rcb_resample_taps, rcb_resample_length, rcb_resample_table_bytes, rcb_resample).
+ * A binding compares rcb_version() with the RCB_VERSION it was written against and rcb_struct_bytes() with the size of each of its mirrors. */
+#define RCB_VERSION 419
 #define RCB_OK 0
 #define RCB_ERR_ARG (-1)
 #define RCB_ERR_SHAPE (-2)
@@ -968,7 +969,7 @@ int rcb_ssim_list(const void* a, int64_t a_elems, const void* b, int64_t b_elems
  *          stored 16-bit value above L goes in as it is and comes out clamped.
  *   kind 1 (fp32):  (float)a, one rounding, no clamp.  Non-finite values follow the arithmetic: a zero weight times an infinity
  *          is a NaN.
- *   kind 3 (s16) is refused: resampling audio is a different filter question.
+ *   kind 3 (s16) is refused: resampling audio is a different filter question, which rcb_resample (419, below) answers.
  * This is torch.nn.functional.interpolate(mode="bilinear", antialias=True, align_corners=False) evaluated in fp64 and rounded
  * once (tests/test_resize_emul_cpu.py holds the two together).  torchvision's uint8 path -- fixed-point weights, a rounding to
  * uint8 BETWEEN the two passes -- is NOT copied: it differs from this definition by at most one step in a share of the samples
@@ -1069,6 +1070,79 @@ int rcb_rgb_to_ycc(const void* src, int64_t src_elems, const int64_t* strides, i
 int rcb_ycc_sse(const void* a, int64_t a_elems, const int64_t* a_strides, int64_t a_offset, const void* b, int64_t b_elems,
                 const int64_t* b_strides, int64_t b_offset, int32_t kind, int32_t depth, int32_t ss, int64_t n, int32_t T, int32_t H,
                 int32_t W, const double* m, const double* off, int64_t* sse, rcb_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * N4 (419): resample PCM audio to the preset's rate.  The audio preset is a 16 kHz preset (data/audio.py:39-46 hard-codes
+ * LibriSpeech's rate; pixel_sizes x patch_nums = 48 000 samples are "3 s at 16 kHz"); audio elsewhere is 44.1 or 48 kHz and often
+ * stereo.  The resampled samples are the SOURCE the finish entries score against, as the resized integers of rcb_resize are.
+ *
+ * The filter is the polyphase windowed-sinc resampler of torchaudio.functional.resample at its defaults -- Hann-windowed sinc,
+ * lowpass_filter_width = 6, rolloff = 0.99 -- evaluated in fp64 with ONE rounding at the end.  Every step below is one IEEE fp64
+ * operation, no contraction, in the order the parentheses give.
+ * Rates:  g = gcd(rate_in, rate_out), o = rate_in / g, n = rate_out / g.
+ *   o == n is the identity: one phase, first = 0, count = 1, w = 1.0 -- every sample is returned bit for bit (-0.0 and the
+ *   non-finite ones included), as torchaudio returns its input.
+ *   Otherwise o <= 8 n (reductions up to 8 : 1), n <= 1024 and o <= 8192; anything else is RCB_ERR_UNSUPPORTED.  48 000 -> 16 000
+ *   (3 : 1), 44 100 -> 16 000 (441 : 160), 22 050 -> 16 000 (441 : 320), 8 000 -> 16 000 (1 : 2), 16 000 -> 44 100 (160 : 441) and
+ *   128 000 -> 16 000 (8 : 1) are legal.
+ * Taps, formed on the HOST:  base = (double)min(o, n) * 0.99;  width = (int)ceil(6.0 * o / base);  s = base / o
+ *   phase p in [0, n), offset k in [-width, width + o):  t = (-(double)p / n + (double)k / o) * base
+ *   a tap is kept where |t| < 6 STRICTLY; the kept k of a phase are contiguous: first[p] (which may be negative) and count[p]
+ *   c = cos(((t * pi) / 6) / 2);  tp = t * pi;  w = ((tp == 0 ? 1 : sin(tp) / tp) * (c * c)) * s      (pi = 3.14159265358979323846)
+ *   torchaudio clamps t to +-6 instead and keeps those taps, whose weight is about 4e-33 s: dropping them is this definition's one
+ *   departure from it (tests/test_resample_emul_cpu.py holds the two together within 1e-9 on 16-bit magnitudes).
+ *   The longest rows: 37 taps at 3 : 1, 34 at 441 : 160, 13 at every enlargement, 97 = RCB_RESAMPLE_MAX_TAPS at 8 : 1.
+ * Filter:  L_out = ceil(n L_in / o) in integer arithmetic.  The caller may ask for the first length_out <= L_out outputs only; they
+ *   are computed from the WHOLE source, so the first three seconds of a long recording have no artificial edge at their end.
+ *   output i = q n + p:  a = ((w_0 v(m_0) + w_1 v(m_0 + 1)) + ...),  m_0 = q o + first[p], the count[p] taps ascending, the first
+ *   product starting the sum.  A sample outside [0, L_in) is +0.0 and is multiplied and added like any other (zero padding,
+ *   torchaudio's).
+ * Channels:  mix == NULL: every channel is filtered on its own, C_out = C.  mix = HOST double[C]: ONE output channel, filtered
+ *   from v(m) = ((g_0 x_0(m) + g_1 x_1(m)) + ...), formed in fp64 before the filter (x_c the sample as an exact fp64 value).
+ * Affine:  after the filter a' = a * gain + bias, two operations; skipped altogether when gain == 1 && bias == 0.  gain = bias =
+ *   0.5 lets a zero-centred fp32 waveform leave as the preset's (x + 1) / 2.
+ * Output, the kind of the input:
+ *   kind 3 (s16):   q = (int)rint(fmin(fmax(a', -32768), 32767)), half to even, ONE rounding.
+ *   kind 1 (fp32):  (float)a', no clamp.  Non-finite values follow the arithmetic.
+ *   kinds 0 and 2 are RCB_ERR_ARG: images are rcb_resize's.
+ *
+ * rcb_resample_taps: the host arithmetic above, callable without a device.  *o, *n: the ratio.  first, count: int32 [n];
+ *   w: double [n][max_taps], row p holding its count[p] weights and then +0.0.  With first, count and w all NULL only *o and *n are
+ *   written (how a caller sizes the three).  -> the longest count, or an error (< 0): a rate below 1 (RCB_ERR_SHAPE), an illegal
+ *   ratio (RCB_ERR_UNSUPPORTED), null o or n, or only some of first, count, w null (RCB_ERR_ARG), max_taps below the longest count
+ *   (RCB_ERR_SHAPE).  Nothing is written on an error.
+ * rcb_resample_length: L_out of L_in samples (1 .. 2^31 - 1), or -1 for a refused length or pair of rates.
+ * rcb_resample_table_bytes: the device table of rcb_resample for these rates, 8 n (1 + K) bytes, K the longest count: int32 first
+ *   and count per phase, then the weights as [tap][phase] -- consecutive outputs are consecutive phases, so a wave reads a tap as
+ *   one run of doubles.  -1 for a refused pair.
+ * rcb_resample: src holds n_sig signals of L_in samples and C <= 8 channels.
+ *   strides  HOST int64[3]: ELEMENT strides of {signal, sample, channel}, all >= 0; `offset` (>= 0): the element of signal 0,
+ *            sample 0, channel 0.  The addressing rule of rcb_resize: channel-first storage, a window of a longer buffer and an
+ *            expanded channel are all this one call; nothing need be contiguous.
+ *   src_elems  elements of the source buffer from `src`; the farthest element read, offset + (n_sig - 1) s_0 + (L_in - 1) s_1 +
+ *            (C - 1) s_2, must lie below it (checked on the host): every read is inside.
+ *   dst      contiguous [n_sig][length_out][C_out] of the source's type.
+ *   table    device buffer of rcb_resample_table_bytes(rate_in, rate_out) bytes, 8-byte aligned, the caller's to allocate.  The
+ *            entry forms the taps, writes them there on `stream` and synchronises the stream ONCE for that upload -- the rule of
+ *            the entries of 413, 415 and 416: an I/O end, NOT for graph capture.
+ * One workgroup per tile of 256 consecutive outputs of one signal; the samples the tile needs are staged once in LDS as fp64,
+ * after the mix.  A signal's output is bitwise the same alone, in any batch and from run to run.  One pair of rates per call.
+ * n_sig = 0 succeeds and launches nothing.  Refused, nothing launched and nothing uploaded:
+ *   RCB_ERR_ARG          a kind other than 1, 3; a negative stride or offset; null src, dst, strides or table
+ *   RCB_ERR_SHAPE        C outside 1 .. 8; n_sig < 0; L_in < 1; a rate below 1; length_out outside 1 .. L_out; a reach past
+ *                        src_elems; a table that is too small or misaligned
+ *   RCB_ERR_UNSUPPORTED  o > 8 n, n > 1024 or o > 8192; L_out above 2^31 - 1; more than 2^31 - 1 workgroups.  (The entry also proves,
+ *                        for the table it is about to upload, what the kernel relies on -- the first and the last tap ascend with
+ *                        the output index, and no tile spans more samples than the LDS image holds -- and would refuse with this
+ *                        code; no legal ratio fails either.) */
+#define RCB_RESAMPLE_MAX_TAPS 97
+int rcb_resample_taps(int32_t rate_in, int32_t rate_out, int32_t* o, int32_t* n, int32_t* first, int32_t* count, double* w,
+                      int32_t max_taps);
+int64_t rcb_resample_length(int64_t L_in, int32_t rate_in, int32_t rate_out);
+int64_t rcb_resample_table_bytes(int32_t rate_in, int32_t rate_out);
+int rcb_resample(const void* src, int64_t src_elems, int32_t kind, int64_t n_sig, int32_t L_in, int32_t C, const int64_t* strides,
+                 int64_t offset, int32_t rate_in, int32_t rate_out, const double* mix, double gain, double bias, int32_t length_out,
+                 void* dst, void* table, int64_t table_bytes, rcb_stream_t stream);
 
 #ifdef __cplusplus
 }

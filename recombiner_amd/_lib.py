@@ -64,7 +64,7 @@ class LevelBwd(C.Structure):
 
 _lib = None
 # the header these mirrors were written against (include/rcb.h: RCB_VERSION) and the structures load() verifies by size
-ABI_VERSION = 418
+ABI_VERSION = 419
 _MIRRORS = {0: SirenDesc, 1: Level, 2: LevelBwd, 3: AdamCfg, 4: AdamTensor, 5: RecDesc}
 
 # The prototype of every entry point of include/rcb.h, in header order: name -> (restype, [argtypes]).  load() applies it, so
@@ -163,6 +163,10 @@ PROTOTYPES = {
     "rcb_ycc_to_rgb": (_int, [_p] * 7 + [_i32, _i32, _i32, _i64, _i32, _i32, _i32, _p, _p, _p, _p]),
     "rcb_rgb_to_ycc": (_int, [_p, _i64, _p, _i64, _i32, _i32, _i32, _i64, _i32, _i32, _i32] + [_p] * 6),
     "rcb_ycc_sse": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, _i64, _i32, _i32, _i32, _p, _p, _p, _p]),
+    "rcb_resample_taps": (_int, [_i32, _i32, _p, _p, _p, _p, _p, _i32]),
+    "rcb_resample_length": (_i64, [_i64, _i32, _i32]),
+    "rcb_resample_table_bytes": (_i64, [_i32, _i32]),
+    "rcb_resample": (_int, [_p, _i64, _i32, _i64, _i32, _i32, _p, _i64, _i32, _i32, _p, _f64, _f64, _i32, _p, _p, _i64, _p]),
 }
 EXPORTS = list(PROTOTYPES)
 

@@ -14,7 +14,7 @@ OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "librcb_hip.so")
 SOURCES = ["atrans.hip", "colour.hip", "phase_weight.hip", "phaseconv.hip", "posterior.hip", "rec_score.hip", "recon.hip", "recon_regions.hip", "siren_mlp.hip",
            "siren_mlp_bf16.hip", "siren_mlp_wave.hip", "siren_mlp_wide.hip", "siren_mlp_generic.hip",
-           "siren_mlp_rowwave.hip", "resize.hip", "signal.hip", "ssim.hip", "stage1.hip", "step_fused.hip", "tiles.hip", "upconv.hip", "upconv_weff.hip"]
+           "siren_mlp_rowwave.hip", "resample.hip", "resize.hip", "signal.hip", "ssim.hip", "stage1.hip", "step_fused.hip", "tiles.hip", "upconv.hip", "upconv_weff.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 
 

@@ -349,6 +349,31 @@ def compress_resized(config, dataset, checkpoint, signals, crop=None, channels_f
     return (*out, resized, by_region)
 
 
+def compress_resampled(config, dataset, checkpoint, signals, rate_in, rate_out=16000, channels_first=False, mix="mean",
+                       sample_format=None, regions=None, **kw):
+    """`compress_signals` on audio of any rate and channel count, brought to the preset's rate, channel count and grid on the device
+    first (utils.resample_to_preset, which documents rate_in / rate_out / channels_first / mix and the order of the steps: the
+    downmix, then one windowed-sinc resampling with one rounding, cut to the grid's length -- what a loader does before
+    data/audio.py:39-54 when the files are not LibriSpeech's).  -> what compress_signals returns, plus the resampled source
+    [n, grid, C] of the signals' dtype: the signal that was coded, hence the one the decoded integers are scored against
+    (report_signals).  The stream is that of a signal at the preset's grid and carries no rate: bitstream.decode_signal decodes
+    it.  Every other argument is `compress`'s.
+    regions ("patch", "row" or a box of one int: utils.region_of; None: nothing changes): one more element is appended, the
+    distortion figure per region of every resampled signal, fp64 [n, *nr] (the model's report_regions_signals)."""
+    from . import utils
+    device = kw.get("device", "cuda")
+    (moved,) = _signal_views("compress_resampled", [signals], sample_format, device)
+    resampled = utils.resample_to_preset(config, moved, rate_in, rate_out=rate_out, channels_first=channels_first, mix=mix,
+                                         sample_format=sample_format)
+    out = compress_signals(config, dataset, checkpoint, resampled, landscape=False, sample_format=sample_format, **kw)
+    if regions is None:
+        return (*out, resampled)
+    n_rows = resampled.shape[0] * int(np.prod(utils.preset_grid(config)[0]))
+    by_region = out[1].report_regions_signals(_default_x(kw.get("x"), config, device, n_rows), resampled, region=regions,
+                                              sample_format=sample_format)
+    return (*out, resampled, by_region)
+
+
 def compress_ycc(config, dataset, checkpoint, planes, layout_or_subsampling, matrix, crop=None, chroma="replicate", sample_format=None,
                  **kw):
     """`compress_resized` on Y'CbCr sources -- raw video and image planes as decoders and .yuv files deliver them -- converted to

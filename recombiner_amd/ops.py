@@ -1731,6 +1731,57 @@ def resize(src, size, sample_format=None, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------
+# N4 (419): resample PCM audio (rcb_resample)
+# ---------------------------------------------------------------------------------------------------
+def resample(src, rate_in, rate_out, sample_format=None, mix=None, gain=1.0, bias=0.0, length=None, out=None):
+    """Audio [n, L, C] on the GPU at rate_in -> the same at rate_out, a contiguous tensor [n, length, C_out] of the source's dtype
+    (rcb_resample; the definition is include/rcb.h's: torchaudio.functional.resample's Hann-windowed sinc at its defaults, in fp64,
+    ONE rounding at the end, zero padding at both ends).  src is int16 with sample_format=utils.SampleFormat.s16() (ValueError
+    without it, as everywhere) or fp32, C <= 8, with ANY strides and storage offset -- a channel-first view, a window of a longer
+    buffer, an expanded channel: the strides and the offset go to the kernel and nothing is copied.
+    mix: None -- every channel on its own, C_out = C -- or C weights: ONE output channel, filtered from their weighted sum (formed
+    in fp64 before the filter; [0.5, 0.5] is the usual stereo downmix).  gain, bias: a * gain + bias after the filter, skipped
+    when they are 1 and 0 (0.5, 0.5: a zero-centred fp32 waveform leaves as the preset's (x + 1) / 2).  length: only the first
+    `length` of the ceil(L * rate_out / rate_in) outputs, computed from the whole source (None: all).  Reductions up to 8 : 1,
+    n <= 1024 and o <= 8192 in lowest terms; one pair of rates per call.
+    out: optional preallocated contiguous tensor of the result's shape and dtype.  The only host sync is the table upload."""
+    what = "resample"
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise RcbError(f"{what}: src must be a GPU tensor (the HIP path has no CPU fallback)")
+    if sample_format is None and src.dtype in (torch.uint16, torch.int16):
+        raise ValueError("%s: %s signals need sample_format= (utils.SampleFormat.s16()): whether they are PCM is not in the dtype"
+                         % (what, src.dtype))
+    kind, _, _ = _sample_rule(what, src.dtype, sample_format)
+    if src.dim() != 3:
+        raise RcbError(f"{what}: src {tuple(src.shape)} must be [n, L, C]")
+    n, L, Cc = (int(v) for v in src.shape)
+    mix_arr, mix_ptr = None, C.c_void_p(0)
+    if mix is not None:
+        mix_arr = np.ascontiguousarray(mix, dtype=np.float64).reshape(-1)
+        if mix_arr.size != Cc:
+            raise ValueError(f"{what}: {mix_arr.size} mix weights for {Cc} channels")
+        mix_ptr = _np_ptr(mix_arr)
+    lib = _lib.load()
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    n_tab = int(lib.rcb_resample_table_bytes(rate_in, rate_out))
+    L_out = int(lib.rcb_resample_length(L, rate_in, rate_out)) if n_tab >= 0 and L >= 1 else -1
+    length = L_out if length is None else int(length)
+    fits = n_tab >= 0 and 1 <= length <= L_out < 2 ** 31
+    shape = (n, length, 1 if mix is not None else Cc)
+    if out is None:                                          # (a refused call: a one-element output, and the library says why)
+        out = torch.empty(shape if fits else (1,), device=src.device, dtype=src.dtype)
+    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise RcbError(f"{what}: output of shape {tuple(out.shape)} {out.dtype}, expected contiguous {shape} {src.dtype} on the "
+                       "device of src")
+    table = torch.empty(max(n_tab, 8), device=src.device, dtype=torch.uint8)
+    store = src.untyped_storage()
+    strides = (C.c_int64 * 3)(*(int(v) for v in src.stride()))
+    _launch("rcb_resample", C.c_void_p(store.data_ptr()), store.nbytes() // src.element_size(), kind, n, L, Cc, strides,
+            int(src.storage_offset()), rate_in, rate_out, mix_ptr, float(gain), float(bias), max(min(length, 2 ** 31 - 1), -1),
+            C.c_void_p(out.data_ptr()), ptr(table), max(n_tab, 0))
+    return out
+
 
 # ---------------------------------------------------------------------------------------------------
 # N4 (418): Y'CbCr on the device (rcb_ycc_to_rgb, rcb_rgb_to_ycc, rcb_ycc_sse)

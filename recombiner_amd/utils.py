@@ -745,6 +745,85 @@ def resize_to_preset(config, signals, crop=None, channels_first=False, sample_fo
 
 
 # ---------------------------------------------------------------------------------------------
+# resampling audio to a preset's rate (include/rcb.h, N4 419; data/audio.py:39-46)
+# ---------------------------------------------------------------------------------------------
+RESAMPLE_MAX_TAPS = 97                                       # RCB_RESAMPLE_MAX_TAPS
+
+
+def resample_taps(rate_in, rate_out):
+    """The polyphase tap table of rcb_resample, from the C planner (rcb_resample_taps; no device needed): -> (o, n, first int32
+    [n], count int32 [n], w float64 [n, 97]): rate_in : rate_out = o : n in lowest terms; output q n + p reads the samples from
+    q o + first[p] on (first may be negative: zero padding) with row p's count[p] Hann-windowed sinc weights, then +0.0.  A refused
+    pair (a rate below 1, a reduction steeper than 8 : 1, n > 1024 or o > 8192) is an RcbError."""
+    import ctypes
+    from . import _lib
+    lib = _lib.load()
+    o, n = ctypes.c_int32(0), ctypes.c_int32(0)
+    rc = lib.rcb_resample_taps(int(rate_in), int(rate_out), ctypes.byref(o), ctypes.byref(n), None, None, None, 0)
+    if rc < 0:
+        _lib.check(rc, "rcb_resample_taps")
+    first, count = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+    w = np.zeros((n.value, RESAMPLE_MAX_TAPS), dtype=np.float64)
+    rc = lib.rcb_resample_taps(int(rate_in), int(rate_out), ctypes.byref(o), ctypes.byref(n), ctypes.c_void_p(first.ctypes.data),
+                               ctypes.c_void_p(count.ctypes.data), ctypes.c_void_p(w.ctypes.data), RESAMPLE_MAX_TAPS)
+    if rc < 0:
+        _lib.check(rc, "rcb_resample_taps")
+    return o.value, n.value, first, count, w
+
+
+def resample_length(L, rate_in, rate_out):
+    """How many samples rcb_resample makes of L: ceil(L * rate_out / rate_in) in integer arithmetic (rcb_resample_length; no device
+    needed).  A refused length or pair of rates is an RcbError."""
+    from . import _lib
+    lib = _lib.load()
+    got = int(lib.rcb_resample_length(int(L), int(rate_in), int(rate_out)))
+    if got < 0:
+        raise _lib.RcbError("rcb_resample_length: " + (lib.rcb_last_error_string() or b"").decode())
+    return got
+
+
+def resample_to_preset(config, signals, rate_in, rate_out=16000, channels_first=False, mix="mean", sample_format=None):
+    """Audio of any rate and channel count -> the preset's grid, on the GPU: the resampled signals [n, grid, C] of the source's
+    dtype, which are both what compress_signals / patch_signals cut and the SOURCE report_signals scores against.  signals: [n, L,
+    C] (or [n, C, L] with channels_first) for a preset of data_dim 1, int16 with sample_format=SampleFormat.s16() or fp32 (zero-
+    centred: the padding at both ends is zeros).  In order: the channel axis is moved last (a view); the channels are mixed down
+    to the preset's output_dim -- mix "mean": weights 1 / C; a sequence of C weights; None: the counts must agree already, and
+    every channel is filtered on its own -- and resampled from rate_in to rate_out (16 000: the audio preset's, data/audio.py:39-46)
+    in ONE ops.resample call, which computes exactly the grid's pixel_sizes x patch_nums outputs (48 000: 3 s) from the whole
+    clip.  A clip that yields fewer is a ValueError: ops.resample + drivers.compress_signals_any code a signal of any length."""
+    from . import ops
+    dd = config["data_dim"]
+    if dd != 1:
+        raise ValueError("resample_to_preset: presets of data_dim 1 have a rate to resample to, not %d (resize_to_preset)" % dd)
+    if signals.dim() != 3:
+        raise ValueError("resample_to_preset: %d axes for a 1-D preset ([n, L, C] expected)" % signals.dim())
+    if channels_first:
+        signals = signals.movedim(1, -1)
+    Cc, want = int(signals.shape[-1]), int(config["output_dim"])
+    if isinstance(mix, str):
+        if mix != "mean":
+            raise ValueError("resample_to_preset: mix %r (\"mean\", C weights or None)" % (mix,))
+        weights = None if Cc == want == 1 else [1.0 / Cc] * Cc
+    else:
+        weights = mix
+    if weights is None and Cc != want:
+        raise ValueError("resample_to_preset: %d channels, the preset has %d: mix=\"mean\" or C weights" % (Cc, want))
+    if weights is not None:
+        if want != 1:
+            raise ValueError("resample_to_preset: a mix leaves 1 channel, the preset has %d" % want)
+        if len(weights) != Cc:
+            raise ValueError("resample_to_preset: %d mix weights for %d channels" % (len(weights), Cc))
+    pn, ps = preset_grid(config)
+    grid = pn[0] * ps[0]
+    have = resample_length(int(signals.shape[1]), rate_in, rate_out)
+    if have < grid:
+        raise ValueError("resample_to_preset: %d samples at %d Hz are %d at %d Hz, the preset's grid has %d; ops.resample + "
+                         "drivers.compress_signals_any code a signal of any length"
+                         % (signals.shape[1], rate_in, have, rate_out, grid))
+    return ops.resample(signals, rate_in, rate_out, sample_format=sample_format, mix=weights, length=grid)
+
+
+# ---------------------------------------------------------------------------------------------
 # Y'CbCr sources and per-plane scores (include/rcb.h, N4 418)
 # ---------------------------------------------------------------------------------------------
 YCC_STANDARDS = {"bt601": ("0.299", "0.114"), "bt709": ("0.2126", "0.0722"), "bt2020": ("0.2627", "0.0593")}   # (kr, kb)
